@@ -8,7 +8,13 @@ libvcrt.so (vcrt_comm_init; one grouped send/recv), and rank 0 re-interleaves th
 frame is fixed as N grows (strong scaling). torch.distributed (gloo) is only the control plane:
 the communicator id, barriers and the max-over-ranks time.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds what
+takes work of its own outside the timed steps: the `validated` record (rank 0's frame against the
+CPU oracle and, for N > 1, against a 1-GPU render) and the `cpu_baseline` sample. --dump-outputs
+DIR writes the frame the last timed step produced as DIR/framebuffer.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full]
+                       [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 """
 import argparse
@@ -61,7 +67,16 @@ def parse():
     p.add_argument("--variant", type=int, default=0)
     p.add_argument("--blocks-per-cu", type=int, default=0)
     p.add_argument("--chunk", type=int, default=0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also what a plain run leaves out because it takes work of its own "
+                        "outside the timed steps: the validation of rank 0's frame (--validate) "
+                        "and the cpu_baseline sample of the CPU oracle")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, rank 0 writes the frame the last timed step "
+                        "produced (what read_framebuffer returns: [H][W] RGBA, float32) to "
+                        "DIR/framebuffer.npy; above 64 MB, a fixed seeded sample of its rows")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: leave the cpu_baseline sample out")
     p.add_argument("--min-warmup-seconds", type=float, default=3.0,
                    help="after the W warmup steps, further untimed steps until the warmup has "
                         "kept the GPU busy this long: the shader clock follows the load (a lone "
@@ -73,11 +88,13 @@ def parse():
     p.add_argument("--max-warmup-steps", type=int, default=200,
                    help="upper bound on those extra steps")
     p.add_argument("--validate", action="store_true",
-                   help="(the default) after the timed steps, rank 0 checks its frame: bit for "
+                   help="(part of --full, and its default) after the timed steps, rank 0 checks "
+                        "its frame: bit for "
                         "bit against the CPU oracle on pixels of a few full-width rows at full "
                         "spp and depth, and (N > 1) against a 1-GPU render of the whole frame; "
                         "--no-validate turns it off")
-    p.add_argument("--no-validate", action="store_true")
+    p.add_argument("--no-validate", action="store_true",
+                   help="with --full: leave the validation out")
     p.add_argument("--validate-rows", type=int, default=2)
     p.add_argument("--validate-budget", type=float, default=1e10,
                    help="oracle sphere tests the row check may cost (~2 s on 16 threads): wider "
@@ -222,6 +239,33 @@ def validate(args, got, st, device, world):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 5489
+
+
+def dump_outputs(path, got):
+    """--dump-outputs: rank 0's frame after the last timed step, as the caller of
+    read_framebuffer receives it ([H][W] RGBA, float32), to path/framebuffer.npy. A frame above
+    64 MB is cut to a fixed sample of whole rows (seeded, so the same rows for the same frame
+    size, in ascending order). Scene, camera and jitter are deterministic, so two builds given
+    the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = np.ascontiguousarray(got, dtype=np.float32)
+    rows = None
+    row_bytes = out[0].nbytes
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // row_bytes
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(out.shape[0], keep, replace=False))
+        out = np.ascontiguousarray(out[rows])
+    np.save(os.path.join(path, "framebuffer.npy"), out)
+    log(f"dump: {path}/framebuffer.npy {out.shape} float32"
+        + (f", {len(rows)} sampled rows of {got.shape[0]}" if rows is not None else ""))
+    return {"framebuffer": {"shape": list(out.shape), "dtype": "float32",
+                            "rows": "all" if rows is None else
+                                    f"{len(rows)} of {got.shape[0]}, default_rng({DUMP_SEED})"}}
+
+
 def main():
     args = parse()
     import torch
@@ -343,15 +387,16 @@ def main():
     if world > 1:
         rank_ms = [None] * world
         dist.all_gather_object(rank_ms, k_mean)
-    # every line proves its own frame (outside the timed region) unless --no-validate
-    do_validate = not args.no_validate
+    # a --full line proves its own frame (outside the timed region) unless --no-validate
+    do_validate = args.full and not args.no_validate
     got = None
-    if do_validate and rank == 0:  # a host copy, before the renderer closes
+    if (do_validate or args.dump_outputs) and rank == 0:  # a host copy, before the renderer closes
         got = frame.cpu().numpy() if frame is not None else r.read_framebuffer()
     # close before validate(): libvcrt keeps one renderer per process, and validate() opens
     # its own (a second vcrt_begin would end this one, communicator included)
     r.close()
-    validated = validate(args, got, st, device, world) if got is not None else None
+    dumped = dump_outputs(args.dump_outputs, got) if args.dump_outputs and rank == 0 else None
+    validated = validate(args, got, st, device, world) if do_validate and rank == 0 else None
 
     if rank == 0:
         samples = args.width * args.height * args.spp * args.steps
@@ -441,9 +486,11 @@ def main():
             "per_rank_kernel_ms": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3),
                                    "ranks": [round(v, 3) for v in rank_ms]},
         }
+        if dumped is not None:
+            out["dumped"] = dumped
         if validated is not None:
             out["validated"] = validated
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args)
             except Exception as e:  # reported, never fatal to the GPU number

@@ -582,9 +582,9 @@ def test_bench_multirank_gather_bitwise():
     """bench.py's N-rank path end to end on one GPU (3 ranks rendering their tile shares in
     turn, gloo standing in for RCCL, which refuses two ranks on one device): the frame gathered
     to rank 0 and re-interleaved by vcrt_assemble is bit-identical to a default 1-GPU render.
-    At N > 1 the line validates itself without --validate (the driver's first
-    multi-GPU run must prove its gather): bitwise_vs_1gpu, the oracle rows, the per-rank kernel
-    times and gather_ms are in the JSON."""
+    At N > 1 the --full line validates itself without --validate (the driver's
+    first multi-GPU run must prove its gather): bitwise_vs_1gpu, the oracle rows, the per-rank
+    kernel times and gather_ms are in the JSON."""
     import json
     import socket
     import subprocess
@@ -597,7 +597,7 @@ def test_bench_multirank_gather_bitwise():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(root, "bench.py"),
            "--gpus", "3", "--steps", "1", "--warmup", "0", "--width", "200", "--height", "120",
-           "--spp", "40", "--depth", "10", "--scene", "final", "--no-cpu-baseline"]
+           "--spp", "40", "--depth", "10", "--scene", "final", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=100)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -629,7 +629,8 @@ def test_bench_rccl_init_failure_falls_back_to_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(root, "bench.py"),
            "--gpus", "2", "--steps", "1", "--warmup", "0", "--width", "160", "--height", "96",
-           "--spp", "8", "--depth", "10", "--scene", "final", "--no-cpu-baseline", "--validate"]
+           "--spp", "8", "--depth", "10", "--scene", "final", "--full", "--no-cpu-baseline",
+           "--validate"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=100)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -691,7 +692,7 @@ def test_rccl_comm_missing_peer_fails_within_deadline(oracle, monkeypatch):
 
 
 def test_bench_single_gpu_validates_against_oracle():
-    """bench.py at N = 1 validates its own frame by default (verdict r04 item 5): without
+    """bench.py --full at N = 1 validates its own frame by default (verdict r04 item 5): without
     --validate the line carries `validated`, whose two full-width rows at full spp are the
     oracle's bit for bit; --no-validate leaves it out."""
     import json
@@ -699,7 +700,7 @@ def test_bench_single_gpu_validates_against_oracle():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0",
-           "--config", "c3", "--no-cpu-baseline"]
+           "--config", "c3", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=100)
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -714,6 +715,36 @@ def test_bench_single_gpu_validates_against_oracle():
     assert "validated" not in res2
     assert res["roofline"]["frac"] <= 1.0
     assert res["roofline"]["speedup_vs_bruteforce_at_peak"] > 1.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_frame(oracle, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and leaves out the
+    validation and the CPU baseline; --dump-outputs writes the frame of the last timed step as
+    framebuffer.npy (float32, [H][W][4]), which is the oracle's bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    w, h, spp, depth = 200, 120, 8, 10
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
+           "--warmup", "1", "--min-warmup-seconds", "0", "--width", str(w), "--height", str(h),
+           "--spp", str(spp), "--depth", str(depth), "--scene", "final",
+           "--dump-outputs", str(tmp_path / "dump")]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=100)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert "validated" not in res and "cpu_baseline" not in res
+    assert res["steps"] == 2 and out.stderr.count("] step ") == 2
+    assert res["ms_per_step"] > 0 and res["unit"] == "Msamples/s" and res["dtype"] == "f32"
+    # value and ms_per_step are the same measurement, each rounded to 3 decimals
+    assert res["value"] == pytest.approx(w * h * spp / res["ms_per_step"] / 1e3,
+                                         rel=1e-3 + 5e-4 / res["ms_per_step"])
+    assert sorted(os.listdir(tmp_path / "dump")) == ["framebuffer.npy"]
+    got = np.load(tmp_path / "dump" / "framebuffer.npy")
+    assert got.dtype == np.float32 and got.shape == (h, w, 4)
+    want, _ = oracle.render(oracle.config(w, h, spp, depth, **chunk_of(w, h, spp)),
+                            oracle.scene("final"))
+    assert_bitwise(got, want, "bench.py --dump-outputs")
 
 
 @pytest.mark.parametrize("world", [3, 8])

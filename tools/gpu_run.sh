@@ -51,7 +51,7 @@ mode_test() {
 
 mode_bench() {
   for c in ${CFGS:-c4 c3 c2 c5}; do
-    timeout -k 10 300 python bench.py --config $c $(bench_steps $c) > $OUT/bench_$c.json \
+    timeout -k 10 300 python bench.py --full --config $c $(bench_steps $c) > $OUT/bench_$c.json \
       2> $OUT/bench_$c.err || { tail -20 $OUT/bench_$c.err; return 1; }
     python -c "import json,sys; d=json.load(open('$OUT/bench_$c.json')); print('$c', d['value'], d['ms_per_step'], d['roofline']['frac'])"
   done
@@ -112,12 +112,12 @@ mode_profile() {
   local P=$OUT/prof
   rm -rf $P && mkdir -p $P
   for c in c4 c3 c2 c5; do
-    timeout -k 10 300 python bench.py --config $c $(bench_steps $c) > $P/bench_$c.json \
+    timeout -k 10 300 python bench.py --full --config $c $(bench_steps $c) > $P/bench_$c.json \
       2> $P/bench_$c.err || { tail $P/bench_$c.err; return 1; }
   done
   for c in c4 c3 c2 c5; do
     (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/kt_$c \
-      -o bench -- python3 $ROOT/bench.py --config $c $(bench_steps $c) --no-cpu-baseline \
+      -o bench -- python3 $ROOT/bench.py --full --config $c $(bench_steps $c) --no-cpu-baseline \
       > $P/kt_$c.json 2> $P/kt_$c.err) || { tail $P/kt_$c.err; return 1; }
   done
   for c in c4 c3 c2 c5; do
