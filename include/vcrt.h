@@ -296,6 +296,13 @@ int32_t vcrt_cull_tables(const vcrt_sphere* spheres, int32_t count, float* geom,
                          float* node, float* top, int32_t* index, int32_t* big_groups,
                          float* margin4, int32_t cap_groups);
 
+/* The shared y slab of those tables (host only, no GPU): 1 when every group, node and chunk box
+ * that has members carries the same finite lo.y and hi.y, bit for bit -- written to lohi when it
+ * is not NULL -- so that the flat culled scans evaluate the two y planes once per ray instead of
+ * once per box (csrc/tracer.hip, fact (3a)); 0 otherwise, when culling does not apply, or with
+ * VCRT_SLAB=0 in the environment (the three-axis test everywhere: A/B runs and tests). */
+int32_t vcrt_cull_slab(const vcrt_sphere* spheres, int32_t count, float lohi[2]);
+
 /* The flat culled scan's camera-ray lists for a scene and render description (host only, no
  * GPU; csrc/primary.cpp): for each 4x4-pixel quarter (qx, qy) of each local tile lt of
  * desc->rank (in the kernels' local-tile order), info[4 lt + 2 qy + qx] = offset << 4 | count

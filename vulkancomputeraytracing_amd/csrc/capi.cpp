@@ -105,6 +105,8 @@ struct RendererState {
     // culled-scan tables (cluster.hpp); ncgroups == 0 when culling does not apply
     int32_t ncgroups = 0, ncbig = 0;
     float cmargin[4] = {0, 0, 0, 0};  // box margin constants (CullTables::margin)
+    bool cslab_on = false;            // the shared y slab (CullTables::slab, slab_lohi)
+    float cslab[2] = {0, 0};
     float4* d_cgroup = nullptr;
     float4* d_cbound = nullptr;
     float4* d_cbound_nf = nullptr;
@@ -1167,6 +1169,9 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
         g.ncgroups = ct.ngroups;
         g.ncbig = ct.nbig;
         std::memcpy(g.cmargin, ct.margin, sizeof(ct.margin));
+        g.cslab_on = ct.slab;
+        g.cslab[0] = ct.slab_lohi[0];
+        g.cslab[1] = ct.slab_lohi[1];
         if (g.primary_lists && g.local_tiles > 0) {
             // camera rays of a tile start from its quarter's lists (primary.cpp): the groups
             // for the main scan, the spheres for the camera fast trace; info interleaved
@@ -1340,6 +1345,8 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.ncgroups = g.ncgroups;
     p.nbig = g.ncbig;
     for (int k = 0; k < 4; k++) p.box_margin[k] = g.cmargin[k];
+    p.slab[0] = g.cslab[0];
+    p.slab[1] = g.cslab[1];
     p.nspheres = g.nspheres;
     p.width = g.desc.width;
     p.height = g.desc.height;
@@ -1361,6 +1368,7 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
               (g.radii_safe ? vcrt::kFlagRadiiSafe : 0u) |
               (g.direct ? vcrt::kFlagDirect : 0u) |
               (g.pixel_scale ? vcrt::kFlagPixelScale : 0u) |
+              (g.ncgroups > 0 && g.cslab_on ? vcrt::kFlagSlab : 0u) |
               (static_cast<uint32_t>(g.accum_log2 + vcrt::kFlagScaleBias)
                << vcrt::kFlagScaleShift);
     // outlier quanta (vcrt_math.h "Accumulation"); the kernel's quantizing retire writes them
@@ -1952,6 +1960,14 @@ int32_t vcrt_cull_tables(const vcrt_sphere* spheres, int32_t count, float* geom,
         if (index) std::memcpy(index, ct.index.data(), sizeof(int32_t) * ct.index.size());
     }
     return ct.ngroups;
+}
+
+int32_t vcrt_cull_slab(const vcrt_sphere* spheres, int32_t count, float lohi[2]) {
+    if (count < 0 || (count > 0 && !spheres)) return 0;
+    vcrt::CullTables ct;
+    if (!vcrt::build_cull_tables(spheres, count, ct) || !ct.slab) return 0;
+    if (lohi) std::memcpy(lohi, ct.slab_lohi, sizeof(ct.slab_lohi));
+    return 1;
 }
 
 namespace {

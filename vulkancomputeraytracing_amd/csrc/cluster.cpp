@@ -5,6 +5,7 @@
 #include <array>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 
 namespace vcrt {
@@ -209,13 +210,40 @@ bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
                 if (groups[gi][k] >= 0) m.push_back(groups[gi][k]);
         return m;
     };
-    for (size_t gi = 0; gi < ng; gi++) put_box(out.bound, gi, box_of(s, members_of(gi, gi + 1)));
+    // The shared y slab: do all boxes with members have the same finite y extent, bit for bit?
+    // (Padding boxes, the far point, are left out: their groups hold no member a ray can accept.)
+    int slab_boxes = 0;
+    bool slab_same = true;
+    float slab_lo = 0.0f, slab_hi = 0.0f;
+    auto box_at = [&](size_t g0, size_t g1) {
+        const std::vector<int32_t> m = members_of(g0, g1);
+        const Box b = box_of(s, m);
+        if (!m.empty()) {
+            if (slab_boxes++ == 0) {
+                slab_lo = b.lo[1];
+                slab_hi = b.hi[1];
+                slab_same = std::isfinite(slab_lo) && std::isfinite(slab_hi);
+            } else if (std::memcmp(&b.lo[1], &slab_lo, sizeof(float)) != 0 ||
+                       std::memcmp(&b.hi[1], &slab_hi, sizeof(float)) != 0) {
+                slab_same = false;
+            }
+        }
+        return b;
+    };
+    for (size_t gi = 0; gi < ng; gi++) put_box(out.bound, gi, box_at(gi, gi + 1));
     for (size_t ni = 0; ni < ng / kNodeGroups; ni++)
-        put_box(out.node, ni, box_of(s, members_of(ni * kNodeGroups, (ni + 1) * kNodeGroups)));
+        put_box(out.node, ni, box_at(ni * kNodeGroups, (ni + 1) * kNodeGroups));
     // top level: one box per chunk of 64 groups (the kernels' unit of work per pass)
     const size_t nt = (ng + 63) / 64, nt2 = nt + (nt & 1);
     out.top.assign(nt2 / 2 * 16, 0.0f);
-    for (size_t ti = 0; ti < nt2; ti++) put_box(out.top, ti, box_of(s, members_of(ti * 64, ti * 64 + 64)));
+    for (size_t ti = 0; ti < nt2; ti++) put_box(out.top, ti, box_at(ti * 64, ti * 64 + 64));
+    // VCRT_SLAB=0 keeps the three-axis box tests (A/B and tests)
+    const char* slab_env = std::getenv("VCRT_SLAB");
+    if (slab_boxes > 0 && slab_same && !(slab_env && std::atoi(slab_env) == 0)) {
+        out.slab = true;
+        out.slab_lohi[0] = slab_lo;
+        out.slab_lohi[1] = slab_hi;
+    }
     // the per-ray margin constants (tracer.hip, box_ray) over the hierarchy's spheres
     double rmax = 0.0, cmax = 0.0, lam = 0.0;
     for (int32_t j : normal) {

@@ -28,6 +28,12 @@ struct CullTables {
                                   // each 64-group chunk (8 nodes), same form
     float margin[4] = {0, 0, 0, 0};  // box-test constants over the hierarchy: max |centre|,
                                      // r_max^2, max |coordinate| of a box (rounded up), 0
+    // The shared y slab (tracer.hip "Culled scan", fact (3a)): set when every non-padding group,
+    // node and chunk box has the same finite lo[1] and hi[1], bit for bit (the generated scenes:
+    // every hierarchy sphere at one height with one radius). The flat scans then evaluate the
+    // y planes once per ray instead of once per box. VCRT_SLAB=0 leaves it unset (A/B).
+    bool slab = false;
+    float slab_lohi[2] = {0, 0};  // that lo[1], hi[1] (slab only)
 };
 
 // Builds the grouped tables. Returns false (tables empty) when culling does not apply: fewer

@@ -41,6 +41,13 @@
 
 using namespace vcrt;
 
+// A/B builds: 1 makes the boxes-in-LDS flat kernel branch on the slab flag once per segment (the
+// scan instantiated twice, as the LDS-table kernel does) instead of around each run of four box
+// pairs; one more SGPR spill than the parent's, see trace_impl (profiles/r07_ab_log.md).
+#ifndef VCRT_SLAB_BOXES_SCAN
+#define VCRT_SLAB_BOXES_SCAN 0
+#endif
+
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -274,6 +281,19 @@ __device__ __forceinline__ void scan_spheres(const TraceParams& p, const float4*
 //      c1's spare) and clamp the near end at 0: gap = fma(K_b, c2, (tf' - max(tn', 0)) + c1)
 //      rules a box out when its whole stretch of the line lies behind -tau as well.
 //      (tau = sqrt(3.2e-7 Q / a), 7% above 5.02u Q / a for the roundings of Q, 1/a and sqrt.)
+//  (3a) the shared slab (flat scans, kFlagSlab). When every group, node and chunk box that has
+//      members carries the same lo.y and hi.y, bit for bit (host-checked, TraceParams.slab: the
+//      generated scenes, whose hierarchy spheres all sit at one height with one radius), the two
+//      y-plane terms fma(lo.y, inv.y, c.y), fma(hi.y, inv.y, c.y) have the same operands in every
+//      box test of a ray, so they are the same two fp32 numbers: box_ray computes them once,
+//      t0 = max(min of the two, 0) and t1 = max of the two, and each box test takes tnear =
+//      max3(x near, z near, t0), tfar = min3(x far, z far, t1). max and min of these values (finite
+//      or +inf, never NaN) are exact, associative and commutative, so max3(tnx, tnz, max(tny, 0)) =
+//      max(max3(tnx, tny, tnz), 0): the gap is the three-axis gap of (3) and (4), the same boxes
+//      are ruled out, and the image, the segments and the issued tests do not change. A padding
+//      box (the far point 1e20, no member a ray can accept) gets the slab in place of its own y
+//      planes, so its gap may differ: it is ruled out by x and z as before, or its empty groups
+//      are tested for nothing.
 // Waves holding a ray outside the guarded range scan the original table in reference order.
 
 // t of one candidate as hit_sphere would accept it (finite case, fact (1)).
@@ -420,6 +440,8 @@ struct BoxRay {
     v2f ix, iy, iz;  // 1 / d'
     v2f cx, cy, cz;  // -o / d'
     v2f c1, c2;      // gap slack: c1 + K_b c2
+    // Slab rays (3a): iy holds t0 and cy holds t1, the near and far end of the shared y slab, in
+    // place of the y axis' two terms -- the same registers, and the passes fetch the same fields.
 };
 
 __device__ __forceinline__ float box_axis(float o, float d, float tau, v2f& i, v2f& c) {
@@ -431,8 +453,10 @@ __device__ __forceinline__ float box_axis(float o, float d, float tau, v2f& i, v
     return fabsf(iv);
 }
 
-// ya: recip_a(dot(d, d)), for tau of (4)
-__device__ __forceinline__ BoxRay box_ray(const TraceParams& p, const f3 o, const f3 d, float ya) {
+// ya: recip_a(dot(d, d)), for tau of (4). slab (wave-uniform; the flat scans on a scene whose
+// boxes share their y extent, TraceParams.slab): the y axis as the ray's interval of (3a).
+__device__ __forceinline__ BoxRay box_ray(const TraceParams& p, const f3 o, const f3 d, float ya,
+                                          bool slab = false) {
     BoxRay r;
     const float on = __builtin_amdgcn_sqrtf(dot(o, o)) + p.box_margin[0];
     const float Q = on * on + p.box_margin[1];
@@ -445,14 +469,36 @@ __device__ __forceinline__ BoxRay box_ray(const TraceParams& p, const f3 o, cons
     const float c2 = J * Q;
     r.c1 = (v2f){c1, c1};
     r.c2 = (v2f){c2, c2};
+    if (slab) {
+        const float tly = __builtin_fmaf(p.slab[0], r.iy.x, r.cy.x);
+        const float thy = __builtin_fmaf(p.slab[1], r.iy.x, r.cy.x);
+        const float t0 = fmaxf(fminf(tly, thy), 0.0f);  // with the clamp of (4)
+        const float t1 = fmaxf(tly, thy);
+        r.iy = (v2f){t0, t0};
+        r.cy = (v2f){t1, t1};
+    }
     return r;
 }
 
 // The box test's gap for a pair of boxes (TraceParams.cbound: (lox0,lox1,loy0,loy1)
 // (loz0,loz1,hix0,hix1) (hiy0,hiy1,hiz0,hiz1) (K0,K1,-,-)): negative when the ray rules the box
-// out. (All values finite or +inf, so the gap is never -0 or NaN.)
+// out. (All values finite or +inf, so the gap is never -0 or NaN.) kSlab: the ray's y interval
+// (3a) in place of the pair's own y planes.
+template <bool kSlab = false>
 __device__ __forceinline__ v2f box_gap(const BoxRay& r, float4 b0, float4 b1, float4 b2,
                                        float4 b3) {
+    if constexpr (kSlab) {
+        const v2f lox = {b0.x, b0.y}, loz = {b1.x, b1.y};
+        const v2f hix = {b1.z, b1.w}, hiz = {b2.z, b2.w}, K = {b3.x, b3.y};
+        const v2f tlx = vfma(lox, r.ix, r.cx), thx = vfma(hix, r.ix, r.cx);
+        const v2f tlz = vfma(loz, r.iz, r.cz), thz = vfma(hiz, r.iz, r.cz);
+        v2f tn, tf;
+        tn.x = fmaxf(fmaxf(fminf(tlx.x, thx.x), fminf(tlz.x, thz.x)), r.iy.x);
+        tn.y = fmaxf(fmaxf(fminf(tlx.y, thx.y), fminf(tlz.y, thz.y)), r.iy.y);
+        tf.x = fminf(fminf(fmaxf(tlx.x, thx.x), fmaxf(tlz.x, thz.x)), r.cy.x);
+        tf.y = fminf(fminf(fmaxf(tlx.y, thx.y), fmaxf(tlz.y, thz.y)), r.cy.y);
+        return vfma(K, r.c2, (tf - tn) + r.c1);
+    }
     const v2f lox = {b0.x, b0.y}, loy = {b0.z, b0.w}, loz = {b1.x, b1.y};
     const v2f hix = {b1.z, b1.w}, hiy = {b2.x, b2.y}, hiz = {b2.z, b2.w}, K = {b3.x, b3.y};
     const v2f tlx = vfma(lox, r.ix, r.cx), thx = vfma(hix, r.ix, r.cx);
@@ -684,9 +730,10 @@ __device__ __forceinline__ uint32_t push_sign(uint32_t acc, float v) {
 
 // Sign of the box gap for both boxes of a pair: set (negative) when this lane rules the box
 // out. Pushed high element first.
+template <bool kSlab = false>
 __device__ __forceinline__ uint32_t push_bound_pair(uint32_t acc, const BoxRay& r, float4 b0,
                                                     float4 b1, float4 b2, float4 b3) {
-    const v2f D = box_gap(r, b0, b1, b2, b3);
+    const v2f D = box_gap<kSlab>(r, b0, b1, b2, b3);
     return push_sign(push_sign(acc, D.y), D.x);
 }
 
@@ -721,9 +768,20 @@ __device__ __forceinline__ v2f ld2(const char* p) {
     return (v2f){v.x, v.y};
 }
 
+template <bool kSlab = false>
 __device__ __forceinline__ uint32_t push_bound_pair_nf(uint32_t acc, const BoxRay& r,
                                                        const NearFarAddr& a, int off) {
     const v2f tnx = vfma(ld2(a.x + off), r.ix, r.cx), tfx = vfma(ld2(a.x + off + 8), r.ix, r.cx);
+    if constexpr (kSlab) {  // (3a): the y axis is the ray's own interval, clamp included
+        const v2f tnz = vfma(ld2(a.z + off), r.iz, r.cz), tfz = vfma(ld2(a.z + off + 8), r.iz, r.cz);
+        v2f tn, tf;
+        tn.x = fmaxf(fmaxf(tnx.x, tnz.x), r.iy.x);
+        tn.y = fmaxf(fmaxf(tnx.y, tnz.y), r.iy.y);
+        tf.x = fminf(fminf(tfx.x, tfz.x), r.cy.x);
+        tf.y = fminf(fminf(tfx.y, tfz.y), r.cy.y);
+        const v2f D = vfma(ld2(a.k + off), r.c2, (tf - tn) + r.c1);
+        return push_sign(push_sign(acc, D.y), D.x);
+    }
     const v2f tny = vfma(ld2(a.y + off), r.iy, r.cy), tfy = vfma(ld2(a.y + off + 8), r.iy, r.cy);
     const v2f tnz = vfma(ld2(a.z + off), r.iz, r.cz), tfz = vfma(ld2(a.z + off + 8), r.iz, r.cz);
     v2f tn, tf;
@@ -735,6 +793,22 @@ __device__ __forceinline__ uint32_t push_bound_pair_nf(uint32_t acc, const BoxRa
     tn.y = fmaxf(tn.y, 0.0f);
     const v2f D = vfma(ld2(a.k + off), r.c2, (tf - tn) + r.c1);
     return push_sign(push_sign(acc, D.y), D.x);
+}
+
+// The four pairs of a node's groups or a chunk's nodes. kSlab 0 / 1: the form is known; -1: by
+// the wave-uniform `slab`, the four pairs in either form (not a branch per pair).
+template <int kSlab>
+__device__ __forceinline__ uint32_t push_bound_pairs4_nf(const BoxRay& r, const NearFarAddr& a,
+                                                         bool slab) {
+    uint32_t out = 0;
+    if (kSlab > 0 || (kSlab < 0 && slab)) {
+#pragma unroll
+        for (int k = 3; k >= 0; k--) out = push_bound_pair_nf<true>(out, r, a, 80 * k);
+    } else {
+#pragma unroll
+        for (int k = 3; k >= 0; k--) out = push_bound_pair_nf<false>(out, r, a, 80 * k);
+    }
+    return out;
 }
 
 // Sign bit set when a member may be accepted: disc >= 0 and (hb < 0 or cc < 0), by sign bits
@@ -878,12 +952,12 @@ struct FlatRay {  // this lane's ray, as the passes fetch it
 // 1: group, 2: node. Lanes ranked past the entries run on their own ray and push nothing.
 // kKind 0: cand, 1: group, 2: node. n: this stack's height; pushed: the height of the stack
 // this pass pushes onto (group for node passes, cand for group passes).
-template <int kKind, int kFmt, bool kGRec, uint32_t kNS, class WS>
+template <int kKind, int kFmt, bool kGRec, uint32_t kNS, int kSlab, class WS>
 __device__ __forceinline__ void flat_pass(uint32_t& n, uint32_t& pushed, uint32_t nact,
                                           uint32_t rank, uint32_t lane, WS* ws,
                                           const float4* tbound, const float4* tnode, uint32_t ncg,
                                           const GroupTab<kGRec>& tg, const FlatRay& my,
-                                          uint32_t* rrow = nullptr) {
+                                          bool slab, uint32_t* rrow = nullptr) {
     using F = FlatFmt<kFmt>;
     using entry_t = typename F::entry_t;
     const uint32_t m = min(n, nact), top = n - m;
@@ -916,9 +990,7 @@ __device__ __forceinline__ void flat_pass(uint32_t& n, uint32_t& pushed, uint32_
         // 4 pairs x 80 B: a node's 8 groups, or a chunk's 8 nodes (padded past the last one)
         const float4* gb = (kKind == 2 ? tbound : tnode) + kNS * (e & F::kMask);
         const NearFarAddr na = near_far_addr(gb, ix, iy, iz);
-        uint32_t gout = 0;
-#pragma unroll
-        for (int k = 3; k >= 0; k--) gout = push_bound_pair_nf(gout, r, na, 80 * k);
+        const uint32_t gout = push_bound_pairs4_nf<kSlab>(r, na, slab);
         uint32_t valid = 0xffu;
         if constexpr (kKind == 3)  // the last chunk may hold fewer than 8 nodes
             valid = (1u << min(8u, (ncg >> 3) - 8u * (e & F::kMask))) - 1u;
@@ -1014,13 +1086,13 @@ struct FlatStacks {  // wave-uniform stack heights
     uint32_t cand, group, node, chunk;
 };
 
-template <bool kStats, int kFmt, bool kGRec, uint32_t kNS, class WS>
+template <bool kStats, int kFmt, bool kGRec, uint32_t kNS, int kSlab, class WS>
 __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t rank, uint32_t lane,
                                            WS* ws, FlatStacks& h,
                                            const float4* tbound, const float4* tnode, uint32_t ncg,
                                            const GroupTab<kGRec>& tg, const FlatRay& my,
                                            uint32_t& n_groups, uint32_t& n_bounds,
-                                           PhaseTicks& pt, uint32_t* rrow = nullptr) {
+                                           PhaseTicks& pt, bool slab, uint32_t* rrow = nullptr) {
     uint32_t nc = h.cand, ng = h.group, nn = h.node, nk = h.chunk;
     for (;;) {
         __builtin_amdgcn_wave_barrier();  // the entries were written by other lanes
@@ -1051,8 +1123,8 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
         else if (th == 1u) kind = nk ? 3 : nn ? 2 : ng ? 1 : nc ? 0 : -1;
         if (kind == 0) {
             region(rrow, reg::kPassCand);
-            flat_pass<0, kFmt, kGRec, kNS>(nc, nc, nact, rank, lane, ws, tbound, tnode, ncg, tg, my,
-                                           rrow);
+            flat_pass<0, kFmt, kGRec, kNS, kSlab>(nc, nc, nact, rank, lane, ws, tbound, tnode, ncg,
+                                                  tg, my, slab, rrow);
             if constexpr (kStats) {
                 pt.cand += ticks() - t0;
                 ++pt.cand_passes;
@@ -1060,21 +1132,21 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
         } else if (kind == 1) {
             region(rrow, reg::kPassGroup);
             ++n_groups;
-            flat_pass<1, kFmt, kGRec, kNS>(ng, nc, nact, rank, lane, ws, tbound, tnode, ncg, tg, my,
-                                           rrow);
+            flat_pass<1, kFmt, kGRec, kNS, kSlab>(ng, nc, nact, rank, lane, ws, tbound, tnode, ncg,
+                                                  tg, my, slab, rrow);
             if constexpr (kStats) pt.group += ticks() - t0;
         } else if (kind == 2) {
             region(rrow, reg::kPassNode);
             n_bounds += 8;
-            flat_pass<2, kFmt, kGRec, kNS>(nn, ng, nact, rank, lane, ws, tbound, tnode, ncg, tg, my,
-                                           rrow);
+            flat_pass<2, kFmt, kGRec, kNS, kSlab>(nn, ng, nact, rank, lane, ws, tbound, tnode, ncg,
+                                                  tg, my, slab, rrow);
             if constexpr (kStats) pt.node += ticks() - t0;
         } else if (kind == 3) {
             if constexpr (WS::kHasChunks) {  // (nk stays 0 without the chunk stack)
                 region(rrow, reg::kPassChunk);
                 n_bounds += 8;
-                flat_pass<3, kFmt, kGRec, kNS>(nk, nn, nact, rank, lane, ws, tbound, tnode, ncg,
-                                                tg, my, rrow);
+                flat_pass<3, kFmt, kGRec, kNS, kSlab>(nk, nn, nact, rank, lane, ws, tbound,
+                                                       tnode, ncg, tg, my, slab, rrow);
                 if constexpr (kStats) pt.levels += ticks() - t0;
             }
         } else {
@@ -1090,7 +1162,9 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
 // kChunks: the chunk level as per-lane chunk passes over the near/far node boxes `tnode` (many
 // chunks: the stress scene), else wave-uniform node tests on scalar-loaded boxes (two chunks:
 // the final scene).
-template <bool kStats, int kFmt, bool kGRec, bool kChunks, uint32_t kNS, class WS>
+// kSlab: 1 = the boxes share their y extent (kFlagSlab), box tests by the ray's y interval (3a);
+// 0 = they do not; -1 = read the flag here and branch at each run of box tests.
+template <bool kStats, int kFmt, bool kGRec, bool kChunks, uint32_t kNS, int kSlab, class WS>
 __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const float4* tbound,
                                                  const float4* tnode,
                                                  const GroupTab<kGRec>& tg, WS* ws,
@@ -1113,7 +1187,8 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
     my.dz = d.z;
     my.a = dot(d, d);
     my.ya = recip_a(my.a);
-    my.br = box_ray(p, o, d, my.ya);
+    const bool slab = kSlab < 0 ? (p.flags & kFlagSlab) != 0u : kSlab != 0;  // wave-uniform
+    my.br = box_ray(p, o, d, my.ya, slab);
     const BoxRay& br = my.br;
     CullRay r;
     r.ox = (v2f){o.x, o.x};
@@ -1165,7 +1240,8 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
             if ((base & 127) == 0) {
                 region(rrow, reg::kLevelTop);
                 const BoundPair tp = load_bound_pair(top + 4 * (base >> 7));
-                tops = ~push_bound_pair(0u, br, tp.b0, tp.b1, tp.b2, tp.b3) & 3u;
+                tops = ~(slab ? push_bound_pair<true>(0u, br, tp.b0, tp.b1, tp.b2, tp.b3)
+                              : push_bound_pair<false>(0u, br, tp.b0, tp.b1, tp.b2, tp.b3)) & 3u;
                 n_bounds += 2;
             }
             const bool in_chunk = !listed && ((tops >> ((base >> 6) & 1)) & 1u) != 0;
@@ -1188,8 +1264,7 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
             {  // near/far planes from the LDS copy of the chunk's node boxes, by the ray's signs
                 const NearFarAddr na = near_far_addr(tnode + kNS * ((uint32_t)base >> 6),
                                                      br.ix.x, br.iy.x, br.iz.x);
-#pragma unroll
-                for (int k = 3; k >= 0; k--) out = push_bound_pair_nf(out, br, na, 80 * k);
+                out = push_bound_pairs4_nf<kSlab>(br, na, slab);
                 out &= (1u << nn) - 1u;
             }
             n_bounds += (uint32_t)nn;
@@ -1214,8 +1289,9 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
             if constexpr (kStats) pt.push += ticks() - t0;
             }
         }
-        flat_drain<kStats, kFmt, kGRec, kNS>(th, nact, rank, lane, ws, h, tbound, tnode,
-                                         (uint32_t)ncg, tg, my, n_groups, n_bounds, pt, rrow);
+        flat_drain<kStats, kFmt, kGRec, kNS, kSlab>(th, nact, rank, lane, ws, h, tbound, tnode,
+                                                    (uint32_t)ncg, tg, my, n_groups, n_bounds, pt,
+                                                    slab, rrow);
         if (base >= ncg) break;
     }
     __builtin_amdgcn_wave_barrier();
@@ -2262,10 +2338,26 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                 if constexpr (kCull == 1)
                     scan_culled<kStats>(P, o, d, max_t, best, w_halves, w_bounds, hit_groups,
                                         lane_cnt);
-                else if constexpr (kFlat)
-                    scan_culled_flat<kStats, kFmt, kGRec, kChunks, kNS>(
-                        P, tbound, tnode, tg, ws, o, d, pass == 0, q & kQMask, max_t, best, w_halves,
-                        w_bounds, pt, rrow);
+                else if constexpr (kFlat) {
+                    // Where the slab flag (wave-uniform) branches, chosen per kernel from the
+                    // register allocation each form gets (the spill counts of the code object's
+                    // notes): the LDS-table kernel holds the whole scan twice, one branch per
+                    // segment; the other two branch around each run of four box pairs (the scan
+                    // twice costs the global-table kernel 6 more VGPR spills, the branch per run
+                    // costs the LDS-table kernel 4).
+                    if constexpr (kCull != 4 && !(kCull == 6 && VCRT_SLAB_BOXES_SCAN))
+                        scan_culled_flat<kStats, kFmt, kGRec, kChunks, kNS, -1>(
+                            P, tbound, tnode, tg, ws, o, d, pass == 0, q & kQMask, max_t, best,
+                            w_halves, w_bounds, pt, rrow);
+                    else if ((P.flags & kFlagSlab) != 0u)
+                        scan_culled_flat<kStats, kFmt, kGRec, kChunks, kNS, 1>(
+                            P, tbound, tnode, tg, ws, o, d, pass == 0, q & kQMask, max_t, best,
+                            w_halves, w_bounds, pt, rrow);
+                    else
+                        scan_culled_flat<kStats, kFmt, kGRec, kChunks, kNS, 0>(
+                            P, tbound, tnode, tg, ws, o, d, pass == 0, q & kQMask, max_t, best,
+                            w_halves, w_bounds, pt, rrow);
+                }
                 else
                     scan_culled_lane<kStats>(P, tbound, tgroup, o, d, max_t, best, w_halves,
                                              w_bounds, lane_cnt, hit_groups);

@@ -126,6 +126,11 @@ struct TraceParams {
     // instead of the flags' scale
     uint32_t* pixel_emax;
     uint32_t* outlier_max;
+    // The shared y slab of the flat scans (cluster.hpp CullTables::slab): with kFlagSlab every
+    // non-padding group, node and chunk box has lo.y = slab[0] and hi.y = slab[1], and the flat
+    // scans compute the two y-plane terms once per ray (tracer.hip box_ray, fact (3a)). Last in
+    // the block, so a code object built before them reads the same layout.
+    float slab[2];
 };
 
 constexpr uint32_t kQueueStride = 32;  // u32s between the work-queue counters (128 B)
@@ -157,6 +162,9 @@ constexpr uint32_t kFlagRadiiSafe = 16u;  // every |radius| in [2^-40, 2^30] (ho
 constexpr uint32_t kFlagScaleShift = 24u;  // TraceParams.flags: s + kFlagScaleBias
 constexpr int32_t kFlagScaleBias = 128;
 constexpr uint32_t kFlagPixelScale = 32u;  // per-pixel scales from TraceParams.pixel_emax
+constexpr uint32_t kFlagSlab = 64u;  // the boxes share their y extent, TraceParams.slab (a bit
+                                     // of the flags word the scans hold anyway: no load, no
+                                     // register of its own)
 constexpr uint32_t kFlagDirect = 4u;  // one work item per pixel and frame, not progressive: the
                                       // lane writes the pixel itself (no sums, no resolve pass)
 

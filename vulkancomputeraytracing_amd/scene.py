@@ -92,6 +92,18 @@ def cull_tables(spheres: np.ndarray) -> dict | None:
             "margin": margin}
 
 
+def cull_slab(spheres: np.ndarray) -> tuple[np.float32, np.float32] | None:
+    """The shared y slab of `spheres`' culling tables (host computation, no GPU): (lo.y, hi.y)
+    when every group, node and chunk box with members has that same y extent bit for bit, so the
+    flat scans evaluate the y planes once per ray; None otherwise, without culling tables, or
+    with VCRT_SLAB=0 in the environment."""
+    spheres = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+    lohi = np.zeros(2, np.float32)
+    if N.lib().vcrt_cull_slab(spheres.ctypes.data, len(spheres), lohi.ctypes.data) == 0:
+        return None
+    return lohi[0], lohi[1]
+
+
 def primary_lists(spheres: np.ndarray, desc) -> dict | None:
     """The flat scan's camera-ray lists (host computation, no GPU; csrc/primary.cpp) for
     `spheres` and a RenderDesc: ``info`` [4 x local tiles] uint32, entry 4 lt + 2 qy + qx for the
