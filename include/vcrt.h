@@ -263,6 +263,54 @@ vcrt_result vcrt_read_framebuffer_srgb8(uint8_t* rgba8, size_t bytes);
 /* The 255 ascending linear thresholds behind that encode (byte = #{k : c >= t[k]}). */
 void vcrt_srgb8_thresholds(float thresholds[255]);
 
+/* Ray queries: the radiance (ray_color, functions.glsl:65-92) and the first hit of rays the caller
+ * supplies, against the scene of the last vcrt_set_scene -- any camera model, picking, probes,
+ * albedo and normal buffers. Added (the reference traces its own camera's rays only). */
+typedef struct vcrt_ray_hit {   /* 32 B; the path's first segment */
+    float    t;          /* accepted root; the reference's `infinity` (globals.glsl:26) when sphere < 0 */
+    int32_t  sphere;     /* index into the array given to vcrt_set_scene; -1: sky, or max_depth == 0 */
+    uint32_t segments;   /* sphere-list scans this ray's path ran, 0..max_depth */
+    uint32_t reserved;   /* 0 */
+    float    normal[3];  /* (point - centre) / radius as functions.glsl:33-35 computes it: not flipped,
+                            not renormalised; 0 when sphere < 0 */
+    float    reserved2;  /* 0 */
+} vcrt_ray_hit;
+
+typedef struct vcrt_ray_stats {
+    uint64_t segments;     /* sum over the batch */
+    uint64_t group_tests;  /* as vcrt_stats: groups of four put through the exact test, per wave */
+    uint64_t bound_tests;  /* group/node/chunk boxes tested, per wave (0: the linear scan only) */
+    double   kernel_ms;    /* HIP events on the render stream */
+    char     kernel[48];   /* code-object symbol that ran */
+} vcrt_ray_stats;
+
+/* origins, dirs: [count][3] floats, packed. radiance: [count][4] floats (rgb = ray_color, a = 1).
+ * radiance or hits may be NULL (not both); stats may be NULL. Host pointers; staged through device
+ * buffers that are kept (and grown) between calls and freed by vcrt_end.
+ *
+ * For a ray of six finite components and a direction that is not all zero, rgb and segments are
+ * ray_color's for (origin, dir, max_depth) bit for bit, and t, sphere and normal those of its
+ * first hit_sphere scan (strict <, the earliest index on ties); max_depth == 0 gives radiance 0,
+ * 0 segments and sphere -1. Any other ray is traced without a fault: its result is deterministic,
+ * otherwise unspecified, and changes no other ray's. Results do not depend on the order of the
+ * batch, on how it is split over calls, on the description's rank, world_size or kernel_variant,
+ * or on vcrt_comm_init (the call is local, not collective). The framebuffer, the progressive
+ * accumulation, vcrt_stats and the cost order are left alone: a frame drawn after a query has the
+ * bits it would have had without it. Exactly count entries of each output are written; count == 0
+ * succeeds and writes nothing.
+ * Errors: VCRT_ERROR_INITIALIZATION_FAILED before vcrt_begin, for NULL inputs with count > 0 and
+ * when both outputs are NULL; VCRT_ERROR_FORMAT_NOT_SUPPORTED for max_depth < 0 or count > 2^30;
+ * VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object has no vcrt_trace_rays kernel (an
+ * A/B build of an older tree). */
+vcrt_result vcrt_trace_rays(const float* origins, const float* dirs, uint32_t count,
+                            int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
+                            vcrt_ray_stats* stats);
+/* The same with device pointers (16-B aligned outputs, else VCRT_ERROR_INITIALIZATION_FAILED), on
+ * the render stream; returns when done. */
+vcrt_result vcrt_trace_rays_device(const float* origins, const float* dirs, uint32_t count,
+                                   int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
+                                   vcrt_ray_stats* stats);
+
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file
  * cannot be read or is not a gfx950 code object. Requires vcrt_begin. */

@@ -115,6 +115,27 @@ class vcrt_stats(ctypes.Structure):
     ]
 
 
+class vcrt_ray_hit(ctypes.Structure):
+    _fields_ = [
+        ("t", ctypes.c_float),
+        ("sphere", ctypes.c_int32),
+        ("segments", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("normal", ctypes.c_float * 3),
+        ("reserved2", ctypes.c_float),
+    ]
+
+
+class vcrt_ray_stats(ctypes.Structure):
+    _fields_ = [
+        ("segments", ctypes.c_uint64),
+        ("group_tests", ctypes.c_uint64),
+        ("bound_tests", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
 class vcrt_comm_id(ctypes.Structure):
     _fields_ = [("internal", ctypes.c_char * 128)]  # an ncclUniqueId
 
@@ -149,6 +170,12 @@ SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint32)]),
     "vcrt_srgb8_thresholds": (None, [ctypes.c_void_p]),
+    "vcrt_trace_rays": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.POINTER(vcrt_ray_stats)]),
+    "vcrt_trace_rays_device": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.POINTER(vcrt_ray_stats)]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

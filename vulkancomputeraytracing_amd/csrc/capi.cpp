@@ -65,6 +65,15 @@ struct RendererState {
     // the flat scans' cost-order builds (null: the code object predates them; no cost order)
     hipFunction_t k_trace_cull_flat_cost = nullptr, k_trace_cull_flat_global_cost = nullptr,
                   k_trace_cull_flat_boxes_cost = nullptr;
+    // ray queries (vcrt_trace_rays; null: the code object predates them). The host call stages
+    // through device buffers kept and grown between calls; the counters (the work index at 0,
+    // three u64 tallies from 8) are the query's own, so a frame's are left alone.
+    hipFunction_t k_trace_rays = nullptr;
+    float* d_rq_rays = nullptr;  // [cap][6]: the origins, then the directions
+    float4* d_rq_radiance = nullptr;
+    uint4* d_rq_hits = nullptr;
+    size_t rq_rays_cap = 0, rq_radiance_cap = 0, rq_hits_cap = 0;  // in rays
+    void* d_rq_counters = nullptr;
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -502,6 +511,11 @@ VkResult bind_kernels() {
             (void)hipGetLastError();
             *fp = nullptr;
         }
+    // optional: the ray-query kernel (vcrt_trace_rays answers VK_ERROR_FEATURE_NOT_PRESENT)
+    if (hipModuleGetFunction(&g.k_trace_rays, m, "vcrt_trace_rays") != hipSuccess) {
+        (void)hipGetLastError();
+        g.k_trace_rays = nullptr;
+    }
     VCRT_TRY(hipModuleGetFunction(&g.k_trace_cull_lane_lds_wide, m,
                                   "vcrt_trace_cull_lane_lds_wide"));
     VCRT_TRY(hipModuleGetFunction(&g.k_trace_cull_lane_lds_wide_stats, m,
@@ -1318,13 +1332,35 @@ VkResult build_block_order(uint32_t total_blocks) {
 // resolve pass) on the render stream, waited for; *outlier_max receives the float bits of the
 // largest |quantum sum| that did not fit its pixel's scale (0: none; vcrt_math.h
 // "Accumulation").
-static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
-    const uint32_t pixels = g.total_pixels;
-    vcrt::TraceParams p{};
+// The scene's part of a kernel's argument block: the scan tables, the shading rows, the margins
+// and the flags' scene bits (frames and ray queries).
+static void scene_params(vcrt::TraceParams& p) {
     p.geom = g.d_geom;
     p.center_radius = g.d_center_radius;
     p.shade = g.d_shade;
     p.material = g.d_material;
+    p.cgroup = g.d_cgroup;
+    p.cbound = g.d_cbound;
+    p.cbound_nf = g.d_cbound_nf;
+    p.cnode = g.d_cnode;
+    p.cnode_nf = g.d_cnode_nf;
+    p.ctop = g.d_ctop;
+    p.ncgroups = g.ncgroups;
+    p.nbig = g.ncbig;
+    for (int k = 0; k < 4; k++) p.box_margin[k] = g.cmargin[k];
+    p.slab[0] = g.cslab[0];
+    p.slab[1] = g.cslab[1];
+    p.nspheres = g.nspheres;
+    p.flags = (g.scene_bounded ? vcrt::kFlagSceneBounded : 0u) |
+              (g.radii_safe ? vcrt::kFlagRadiiSafe : 0u) |
+              (g.ncgroups > 0 && g.cslab_on ? vcrt::kFlagSlab : 0u);
+    for (int j = 0; j < 13; j++) p.sin_c[j] = vcrt::kSinC[j];
+}
+
+static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
+    const uint32_t pixels = g.total_pixels;
+    vcrt::TraceParams p{};
+    scene_params(p);
     p.jitter = g.d_jitter;
     p.corner = g.d_corner;
     p.out = g.d_fb;
@@ -1333,21 +1369,9 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.segments = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_counters) + 8);
     p.debug = static_cast<unsigned long long*>(g.d_debug);
     p.work_done = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_counters) + 16);
-    p.cgroup = g.d_cgroup;
-    p.cbound = g.d_cbound;
-    p.cbound_nf = g.d_cbound_nf;
-    p.cnode = g.d_cnode;
-    p.cnode_nf = g.d_cnode_nf;
-    p.ctop = g.d_ctop;
     p.prim_info = g.d_prim_info;
     p.prim_ids = g.d_prim_ids;
     p.cam_rec = g.d_cam_rec;
-    p.ncgroups = g.ncgroups;
-    p.nbig = g.ncbig;
-    for (int k = 0; k < 4; k++) p.box_margin[k] = g.cmargin[k];
-    p.slab[0] = g.cslab[0];
-    p.slab[1] = g.cslab[1];
-    p.nspheres = g.nspheres;
     p.width = g.desc.width;
     p.height = g.desc.height;
     p.spp = g.desc.samples_per_pixel;
@@ -1364,11 +1388,8 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.tail_chunk = g.tail_chunk;
     p.tail_nchunks = g.tail_nchunks;
     p.blocks_head = g.local_tiles * static_cast<uint32_t>(g.nchunks);
-    p.flags = g.work_flags | (g.scene_bounded ? vcrt::kFlagSceneBounded : 0u) |
-              (g.radii_safe ? vcrt::kFlagRadiiSafe : 0u) |
-              (g.direct ? vcrt::kFlagDirect : 0u) |
+    p.flags |= g.work_flags | (g.direct ? vcrt::kFlagDirect : 0u) |
               (g.pixel_scale ? vcrt::kFlagPixelScale : 0u) |
-              (g.ncgroups > 0 && g.cslab_on ? vcrt::kFlagSlab : 0u) |
               (static_cast<uint32_t>(g.accum_log2 + vcrt::kFlagScaleBias)
                << vcrt::kFlagScaleShift);
     // outlier quanta (vcrt_math.h "Accumulation"); the kernel's quantizing retire writes them
@@ -1380,7 +1401,6 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.region = nullptr;
     p.nch_magic[0] = g.nch_magic[0];
     p.nch_magic[1] = g.nch_magic[1];
-    for (int j = 0; j < 13; j++) p.sin_c[j] = vcrt::kSinC[j];
     const std::array<float, 12> cam = camera_array();
     for (int i = 0; i < 12; i++) p.cam[i] = cam[i];
     const KernelChoice kc = select_kernel();
@@ -1719,6 +1739,10 @@ vcrt_result vcrt_end(void) {
     if (g.d_region) (void)hipFree(g.d_region);
     if (g.d_pixel_cost) (void)hipFree(g.d_pixel_cost);
     if (g.d_block_order) (void)hipFree(g.d_block_order);
+    if (g.d_rq_rays) (void)hipFree(g.d_rq_rays);
+    if (g.d_rq_radiance) (void)hipFree(g.d_rq_radiance);
+    if (g.d_rq_hits) (void)hipFree(g.d_rq_hits);
+    if (g.d_rq_counters) (void)hipFree(g.d_rq_counters);
     DestroyShaderStage(&g.stage);
     if (g.ev_start) (void)hipEventDestroy(g.ev_start);
     if (g.ev_stop) (void)hipEventDestroy(g.ev_stop);
@@ -1730,6 +1754,130 @@ vcrt_result vcrt_end(void) {
     comm_release(false);
     if (g.stream) (void)hipStreamDestroy(g.stream);
     g = RendererState{};
+    return VCRT_SUCCESS;
+}
+
+// ---- ray queries --------------------------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kRayQueryMax = 1u << 30;
+constexpr size_t kRayCounterBytes = 32;  // u32 work index at 0, u64 tallies at 8, 16, 24
+
+// The arguments every form of the call checks, in the order of the header's table.
+vcrt_result ray_query_args(const float* origins, const float* dirs, uint32_t count,
+                           int32_t max_depth, const void* radiance, const void* hits) {
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (count > 0 && (!origins || !dirs)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!radiance && !hits) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (max_depth < 0 || count > kRayQueryMax) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (!g.k_trace_rays) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    return VCRT_SUCCESS;
+}
+
+// A staging buffer of at least `rays` elements of `bytes_each`, kept between calls.
+hipError_t grow(void** buf, size_t* cap, size_t rays, size_t bytes_each) {
+    if (rays <= *cap) return hipSuccess;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const hipError_t e = hipMalloc(buf, rays * bytes_each);
+    if (e == hipSuccess) *cap = rays;
+    return e;
+}
+
+// The launch on device pointers (checked by the callers): a persistent grid sized from the
+// occupancy query as a frame's is, capped at the batch; returns when the kernel is done.
+VkResult ray_query_device(const float* origins, const float* dirs, uint32_t count,
+                          int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
+                          vcrt_ray_stats* stats) {
+    if (stats) {
+        *stats = vcrt_ray_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_trace_rays");
+    }
+    if (count == 0) return VK_SUCCESS;
+    if (!g.d_rq_counters) VCRT_TRY(hipMalloc(&g.d_rq_counters, kRayCounterBytes));
+    vcrt::RayQueryParams p{};
+    scene_params(p.scene);
+    p.scene.max_depth = max_depth;
+    p.origins = origins;
+    p.dirs = dirs;
+    p.radiance = reinterpret_cast<float4*>(radiance);
+    p.hits = reinterpret_cast<uint4*>(hits);
+    p.count = count;
+    p.work = static_cast<uint32_t*>(g.d_rq_counters);
+    p.tallies = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_rq_counters) + 8);
+    const uint32_t block = 256;
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g.k_trace_rays, block, 0) !=
+            hipSuccess ||
+        per_cu <= 0)
+        per_cu = 1;
+    const uint32_t grid =
+        std::min<uint32_t>(static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(g.num_cus),
+                           (count + block - 1) / block);
+    VCRT_TRY(hipMemsetAsync(g.d_rq_counters, 0, kRayCounterBytes, g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
+    const VkResult r = launch(g.k_trace_rays, grid, block, 0, p);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
+    unsigned long long counters[4] = {0, 0, 0, 0};
+    if (stats)
+        VCRT_TRY(hipMemcpyAsync(counters, g.d_rq_counters, kRayCounterBytes,
+                                hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) {
+        float ms = 0.f;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+        stats->kernel_ms = ms;
+        stats->segments = counters[1];
+        stats->group_tests = counters[2];
+        stats->bound_tests = counters[3];
+    }
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_trace_rays_device(const float* origins, const float* dirs, uint32_t count,
+                                   int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
+                                   vcrt_ray_stats* stats) {
+    const vcrt_result a = ray_query_args(origins, dirs, count, max_depth, radiance, hits);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernel's 16-byte stores
+    if ((reinterpret_cast<uintptr_t>(radiance) | reinterpret_cast<uintptr_t>(hits)) & 15u)
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    return ray_query_device(origins, dirs, count, max_depth, radiance, hits, stats);
+}
+
+vcrt_result vcrt_trace_rays(const float* origins, const float* dirs, uint32_t count,
+                            int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
+                            vcrt_ray_stats* stats) {
+    static_assert(sizeof(vcrt_ray_hit) == 32, "two 16-byte stores per record");
+    const vcrt_result a = ray_query_args(origins, dirs, count, max_depth, radiance, hits);
+    if (a != VCRT_SUCCESS) return a;
+    const size_t n = count, in_bytes = 3 * sizeof(float) * n;
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_rays), &g.rq_rays_cap, n, 6 * sizeof(float)));
+    if (radiance) VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_radiance), &g.rq_radiance_cap, n, sizeof(float4)));
+    if (hits) VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_hits), &g.rq_hits_cap, n, sizeof(vcrt_ray_hit)));
+    float* d_origins = g.d_rq_rays;
+    float* d_dirs = g.d_rq_rays + 3 * n;
+    if (n) {
+        VCRT_TRY(hipMemcpyAsync(d_origins, origins, in_bytes, hipMemcpyHostToDevice, g.stream));
+        VCRT_TRY(hipMemcpyAsync(d_dirs, dirs, in_bytes, hipMemcpyHostToDevice, g.stream));
+    }
+    const VkResult r = ray_query_device(
+        d_origins, d_dirs, count, max_depth,
+        radiance ? reinterpret_cast<float*>(g.d_rq_radiance) : nullptr,
+        hits ? reinterpret_cast<vcrt_ray_hit*>(g.d_rq_hits) : nullptr, stats);
+    if (r != VK_SUCCESS || n == 0) return r;
+    if (radiance)
+        VCRT_TRY(hipMemcpyAsync(radiance, g.d_rq_radiance, sizeof(float4) * n,
+                                hipMemcpyDeviceToHost, g.stream));
+    if (hits)
+        VCRT_TRY(hipMemcpyAsync(hits, g.d_rq_hits, sizeof(vcrt_ray_hit) * n,
+                                hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
     return VCRT_SUCCESS;
 }
 

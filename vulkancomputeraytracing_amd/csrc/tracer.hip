@@ -2785,3 +2785,214 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_fill(FillParams p) {
         p.out[i] = p.value;
 }
 #endif
+
+// ---------------------------------------------------------------------------------------------
+// Ray queries: ray_color (functions.glsl:65-92) and the first hit_sphere scan of caller-supplied
+// rays, a code-generation unit of its own (Makefile, part 3).
+#if !defined(VCRT_PART) || VCRT_PART == 3
+namespace {
+
+// One traced segment shaded: the arithmetic of trace_impl's shade_and_advance, hit and sky
+// branches, on a ray that belongs to no pixel. A hit scatters the ray (o, d, atten), returns its
+// normal (functions.glsl:33-35: (point - centre) / radius, not flipped) and false; the sky
+// returns true with the path's radiance atten * sky in contrib.
+__device__ __forceinline__ bool shade_segment(const TraceParams& S, float max_t, int best, f3& o,
+                                              f3& d, f3& atten, f3& normal, f3& contrib) {
+    if (best < 0) {
+        const float len = sqrt_fast(dot(d, d));  // length(d)
+        contrib = mul(atten, sky_factor(d.y / len));
+        return true;
+    }
+    const float4 cr = S.center_radius[best], sh = S.shade[best], mat = S.material[best];
+    const f3 point = add(scale(max_t, d), o);
+    // the unscaled division with one reciprocal for numerators and radius in [2^-40, 2^30] (the
+    // radius by a host flag), else hipcc's full division in a real branch: the same bits
+    const f3 pcv = sub(point, mk(cr.x, cr.y, cr.z));
+    const float yr = recip_a(cr.w);
+    normal = mk(div_a(pcv.x, cr.w, yr), div_a(pcv.y, cr.w, yr), div_a(pcv.z, cr.w, yr));
+    const float nmin = fminf(fminf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+    const float nmax = fmaxf(fmaxf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+    if (!((S.flags & kFlagRadiiSafe) != 0u && nmin >= 0x1p-40f && nmax <= 0x1p30f)) {
+        asm volatile("");
+        normal = divs(pcv, cr.w);
+    }
+    const int type = (int)mat.x;
+    const f3 albedo = mk(sh.x, sh.y, sh.z);
+    const float param = sh.w;
+    // rand(dir.xy), rand(dir.xz), rand(dir.yz) for lambertian/metal (functions.glsl:43),
+    // rand(point.xy) for glass (textures.glsl:51)
+    float s1, s2, s3;
+    sin3<true>((type == 3) ? rand_arg(point.x, point.y) : rand_arg(d.x, d.y), rand_arg(d.x, d.z),
+               rand_arg(d.y, d.z), s1, s2, s3, (cdouble*)&S.sin_c[0], nullptr);
+    const float r1 = rand_of_sin(s1);
+    if (type == 1 || type == 2) {
+        const float r2 = rand_of_sin(s2);
+        const float r3 = rand_of_sin(s3);
+        const f3 ru = mk(r1, r2, r3);  // random_in_unit_sphere(dir): normalize
+        const f3 u = divs(ru, sqrt_fast(dot(ru, ru)));
+        if (type == 1) {
+            d = add(normal, u);
+            atten = scale(param, mul(atten, albedo));
+        } else {
+            d = add(reflect(d, normal), scale(param, u));
+            atten = mul(atten, albedo);
+        }
+        o = point;
+    } else if (type == 3) {
+        const f3 reflected = reflect(d, normal);
+        f3 outward;
+        float ni, cosine;
+        const float dn = dot(d, normal);
+        if (dn > 0.0f) {
+            outward = neg(normal);
+            ni = param;
+            cosine = sqrt_fast(1.0f - param * param * (1.0f - dn * dn));
+        } else {
+            outward = normal;
+            ni = mat.y;  // 1.0f / param
+            cosine = -dn;
+        }
+        f3 refracted = mk(0.f, 0.f, 0.f);
+        float reflect_prob = 1.0f;
+        const float dt = dot(d, outward);
+        const float disc = 1.0f - ni * ni * (1.0f - dt * dt);
+        if (disc > 0.0f) {
+            const float sd = sqrt_fast(disc);
+            refracted = sub(scale(ni, sub(d, scale(dt, outward))), scale(sd, outward));
+            reflect_prob = schlick_r0(cosine, mat.z);  // schlick(cosine, param)
+        }
+        o = point;
+        d = (r1 < reflect_prob) ? reflected : refracted;
+    }
+    return false;
+}
+
+}  // namespace
+
+// A persistent grid of lanes, one ray per lane: a lane whose path has ended takes the next ray
+// index, and a wave claims the indices of all its needing lanes with one atomic (adjacent lanes
+// of a claim get adjacent rays). Every segment runs the per-lane culled scan on the global tables
+// when the scene has them and every ray the wave holds is in the guarded range, else the linear
+// scan: the same sphere and t either way (facts (1)-(4) above), so a ray's result does not
+// depend on the rays it shares a wave with. Lanes with no ray left sit out (as trace_impl's done
+// lanes do: the scans' ballots see the active lanes only) and hold a guarded ray.
+extern "C" __global__ __launch_bounds__(256) void vcrt_trace_rays(RayQueryParams p_arg) {
+    // the arguments through a pointer to the kernarg segment, as trace_impl reads them (scalar
+    // loads from the constant cache; the sine's constant table is addressed there)
+    (void)p_arg;
+    const RayQueryParams& p = *reinterpret_cast<const RayQueryParams*>(
+        (__attribute__((address_space(4))) const RayQueryParams*)
+            __builtin_amdgcn_kernarg_segment_ptr());
+    const TraceParams& S = p.scene;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (S.max_depth <= 0) {  // ray_color's undefined return (canonical 0) without a scan
+        const uint4 h0 = make_uint4(__float_as_uint(kInfinity), 0xffffffffu, 0u, 0u);
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < p.count;
+             i += gridDim.x * blockDim.x) {
+            if (p.radiance) p.radiance[i] = make_float4(0.f, 0.f, 0.f, 1.f);
+            if (p.hits) {
+                p.hits[2u * (size_t)i] = h0;
+                p.hits[2u * (size_t)i + 1u] = make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        return;
+    }
+    const int n = S.nspheres;
+    const float4* tgroup = S.cgroup + 5 * S.nbig;  // the hierarchy's group records
+    bool need = true, done = false;
+    uint32_t idx = 0u;
+    f3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 1.f, 0.f), atten = mk(1.f, 1.f, 1.f);
+    int pass = 0;
+    // the first segment's record (vcrt_ray_hit)
+    float hit_t = kInfinity;
+    int hit_sphere = -1;
+    f3 hit_normal = mk(0.f, 0.f, 0.f);
+    uint32_t segs = 0u;  // this lane's segments, all its rays
+    uint32_t w_halves = 0u, w_bounds = 0u;
+    for (;;) {
+        // ---- lanes whose path has ended take the next rays: one atomic per wave ----
+        const uint64_t need_mask = __ballot(need && !done);
+        if (need_mask != 0u) {
+            const int leader = __builtin_ctzll(need_mask);
+            uint32_t base = 0u;
+            if ((int)lane == leader) base = atomicAdd(p.work, (uint32_t)__popcll(need_mask));
+            base = __builtin_amdgcn_readfirstlane(__shfl(base, leader));
+            if (need && !done) {
+                idx = base + lanes_below(need_mask);
+                if (idx < p.count) {
+                    const float* po = p.origins + 3u * (size_t)idx;
+                    const float* pd = p.dirs + 3u * (size_t)idx;
+                    o = mk(po[0], po[1], po[2]);
+                    d = mk(pd[0], pd[1], pd[2]);
+                    atten = mk(1.f, 1.f, 1.f);
+                    pass = 0;
+                    need = false;
+                } else {  // no ray left: nothing more is stored, and the ray held is guarded
+                    done = true;
+                    o = mk(0.f, 0.f, 0.f);
+                    d = mk(0.f, 1.f, 0.f);
+                }
+            }
+        }
+        if (__ballot(!done) == 0u) break;
+        if (done) continue;
+
+        // ---- one segment: scan the whole sphere list (functions.glsl:73-81) ----
+        ++segs;
+        float max_t = kInfinity;
+        int best = -1;
+        uint32_t hit_groups = 0u, lane_cnt = 0u;
+        const float aa = dot(d, d);
+        const bool guarded = (S.flags & kFlagSceneBounded) != 0 && aa >= 0x1p-20f &&
+                             aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f && fabsf(o.y) <= 0x1p30f &&
+                             fabsf(o.z) <= 0x1p30f;
+        if (S.ncgroups > 0 && __ballot(!guarded) == 0u) {
+            scan_culled_lane<false>(S, S.cbound, tgroup, o, d, max_t, best, w_halves, w_bounds,
+                                    lane_cnt, hit_groups);
+        } else {
+            scan_spheres<false>(S, nullptr, n, o, d, max_t, best, hit_groups);
+            tally(w_halves, 2u * (uint32_t)((n + 3) >> 2));
+        }
+
+        // ---- shade (textures.glsl) or sky (functions.glsl:85-89) ----
+        f3 normal = mk(0.f, 0.f, 0.f), contrib = mk(0.f, 0.f, 0.f);
+        const bool first = pass == 0;
+        bool ended = shade_segment(S, max_t, best, o, d, atten, normal, contrib);
+        if (first) {
+            hit_t = best >= 0 ? max_t : kInfinity;
+            hit_sphere = best;
+            hit_normal = normal;
+        }
+        if (!ended) {
+            ++pass;
+            ended = pass >= S.max_depth;  // undefined GLSL return -> vec3(0)
+        }
+        if (ended) {
+            if (p.radiance) p.radiance[idx] = make_float4(contrib.x, contrib.y, contrib.z, 1.0f);
+            if (p.hits) {
+                // the path's scans: one per hit, and the sky's
+                const uint32_t nseg = (uint32_t)pass + (best < 0 ? 1u : 0u);
+                p.hits[2u * (size_t)idx] = make_uint4(__float_as_uint(hit_t), (uint32_t)hit_sphere,
+                                                      nseg, 0u);
+                p.hits[2u * (size_t)idx + 1u] =
+                    make_uint4(__float_as_uint(hit_normal.x), __float_as_uint(hit_normal.y),
+                               __float_as_uint(hit_normal.z), 0u);
+            }
+            need = true;
+        }
+    }
+    // one atomic per wave and tally
+    unsigned long long total = segs, wh = w_halves, wb = w_bounds;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        total += __shfl_xor(total, off);
+        wh += __shfl_xor(wh, off);
+        wb += __shfl_xor(wb, off);
+    }
+    if (lane == 0) {
+        if (total) atomicAdd(p.tallies + 0, total);
+        atomicAdd(p.tallies + 1, wh / 2u);
+        atomicAdd(p.tallies + 2, wb);
+    }
+}
+#endif

@@ -168,6 +168,25 @@ constexpr uint32_t kFlagSlab = 64u;  // the boxes share their y extent, TracePar
 constexpr uint32_t kFlagDirect = 4u;  // one work item per pixel and frame, not progressive: the
                                       // lane writes the pixel itself (no sums, no resolve pass)
 
+// Ray queries (vcrt_trace_rays): ray_color and the first hit of caller-supplied rays. The scene
+// block is a TraceParams filled as a frame's is (the scan tables, the shading rows, the flags'
+// scene bits, box_margin, slab, sin_c, nspheres, ncgroups, nbig) with max_depth the query's
+// depth; the frame fields (out, accum, work, jitter, corner, the camera lists, ...) are null.
+// The scan helpers of tracer.hip take it as they take a frame's.
+struct RayQueryParams {
+    TraceParams scene;
+    const float* origins;  // [count][3]
+    const float* dirs;     // [count][3]
+    float4* radiance;      // [count] (ray_color.rgb, 1), or null
+    uint4* hits;           // [count][2] vcrt_ray_hit: (t, sphere, segments, 0) (normal.xyz, 0),
+                           //   or null
+    uint32_t count;        // <= 2^30
+    uint32_t* work;        // the next ray index to hand out, zeroed before the launch (it ends
+                           //   below count + 64 * the grid's waves)
+    unsigned long long* tallies;  // [3] segments, groups of four put through the exact test (per
+                                  //   wave), boxes tested (per wave); zeroed before the launch
+};
+
 // TraceParams.jitter from the host's jitter (vcrt_math.h rand2) and the camera: run at
 // vcrt_begin and for each progressive frame.
 struct SetupJitterParams {

@@ -123,6 +123,54 @@ def tile_pixel_map(width: int, height: int, world: int) -> np.ndarray:
                      local_of[y // 8, x // 8] * 64 + (y % 8) * 8 + x % 8], axis=-1)
 
 
+# ---- ray queries --------------------------------------------------------------------------
+
+# vcrt_ray_hit (include/vcrt.h), 32 bytes: the first segment of a queried ray's path
+RAY_HIT_DTYPE = np.dtype([
+    ("t", np.float32),
+    ("sphere", np.int32),
+    ("segments", np.uint32),
+    ("reserved", np.uint32),
+    ("normal", np.float32, (3,)),
+    ("reserved2", np.float32),
+])
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _check_rays(origins, dirs):
+    """The two ray arrays of Renderer.trace_rays, validated before any native call: numpy
+    float32 C-contiguous [n, 3] (converted), or torch float32 contiguous [n, 3] on one CUDA
+    device (as they are). Raises ValueError."""
+    if _is_torch(origins) != _is_torch(dirs):
+        raise ValueError("origins and dirs must both be numpy arrays or both torch tensors")
+    if _is_torch(origins):
+        import torch
+        for name, a in (("origins", origins), ("dirs", dirs)):
+            if a.dtype != torch.float32:
+                raise ValueError(f"{name}: torch tensors must be float32, not {a.dtype}")
+            if not a.is_cuda or a.device != origins.device:
+                raise ValueError(f"{name}: torch tensors must be on one CUDA device")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: torch tensors must be contiguous")
+    else:
+        try:
+            origins = np.ascontiguousarray(origins, dtype=np.float32)
+            dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"origins, dirs: not convertible to float32 arrays ({e})") from None
+    for name, a in (("origins", origins), ("dirs", dirs)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: shape [n, 3] expected, got {tuple(a.shape)}")
+    if origins.shape[0] != dirs.shape[0]:
+        raise ValueError(f"origins has {origins.shape[0]} rays, dirs {dirs.shape[0]}")
+    if origins.shape[0] > 1 << 30:
+        raise ValueError("at most 2^30 rays per call")
+    return origins, dirs
+
+
 # ---- reference-named lifecycle (VkResult codes, no exceptions) ----------------------------
 
 _desc = RenderDesc()
@@ -285,6 +333,59 @@ class Renderer:
         N.check("vcrt_assemble_tiles", self._L().vcrt_assemble_tiles(
             ctypes.c_void_p(gathered_ptr), ctypes.c_void_p(frame_ptr), d.width, d.height,
             d.world_size, tiles_per_rank))
+
+    def trace_rays(self, origins, dirs, max_depth: int | None = None, hits: bool = False,
+                   stats: bool = False):
+        """Radiance and first hit of caller-supplied rays against the current scene
+        (vcrt_trace_rays): any camera model, picking, probes, albedo and normal buffers.
+
+        numpy inputs [n, 3] (anything np.ascontiguousarray(..., float32) takes) go through the
+        host call and return the radiance as float32 [n, 4] (rgb = ray_color, alpha 1) and, with
+        hits=True, a RAY_HIT_DTYPE array [n]. torch float32 tensors [n, 3] on the renderer's device
+        go through the device call on their data_ptr(), after the caller's current stream is
+        synchronised, and return a torch float32 [n, 4] and, with hits=True, an int32 [n, 8]
+        tensor of the records' raw words: column 1 is the sphere index and column 2 the segment
+        count; columns 0 (t) and 4..6 (normal) hold float bits, read them as
+        h[:, [0, 4, 5, 6]].view(torch.float32); columns 3 and 7 are 0.
+
+        max_depth=None takes the description's depth. Returns the radiance alone, or a tuple
+        (radiance[, hits][, stats dict]) in that order. Shape and dtype errors raise ValueError
+        before any native call. The framebuffer and the frame statistics are left alone."""
+        origins, dirs = _check_rays(origins, dirs)
+        depth = self.desc.max_depth if max_depth is None else int(max_depth)
+        if depth < 0:
+            raise ValueError("max_depth must be >= 0")
+        n = int(origins.shape[0])
+        st = N.vcrt_ray_stats()
+        if _is_torch(origins):
+            import torch
+            dev = origins.device
+            if self.desc.device >= 0 and dev.index != self.desc.device:
+                raise ValueError(f"rays on {dev}, the renderer on device {self.desc.device}")
+            lib = self._L()
+            rad = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            rec = torch.empty((n, 8), dtype=torch.int32, device=dev) if hits else None
+            if n:
+                torch.cuda.current_stream(dev).synchronize()
+                N.check("vcrt_trace_rays_device", lib.vcrt_trace_rays_device(
+                    origins.data_ptr(), dirs.data_ptr(), n, depth, rad.data_ptr(),
+                    rec.data_ptr() if hits else None, ctypes.byref(st)))
+        else:
+            lib = self._L()
+            rad = np.empty((n, 4), dtype=np.float32)
+            rec = np.empty(n, dtype=RAY_HIT_DTYPE) if hits else None
+            if n:
+                N.check("vcrt_trace_rays", lib.vcrt_trace_rays(
+                    origins.ctypes.data, dirs.ctypes.data, n, depth, rad.ctypes.data,
+                    rec.ctypes.data if hits else None, ctypes.byref(st)))
+        out = [rad]
+        if hits:
+            out.append(rec)
+        if stats:
+            out.append({"segments": st.segments, "group_tests": st.group_tests,
+                        "bound_tests": st.bound_tests, "kernel_ms": st.kernel_ms,
+                        "kernel": st.kernel.decode() or "vcrt_trace_rays"})
+        return out[0] if len(out) == 1 else tuple(out)
 
     def shader_load(self, path: str) -> None:
         N.check("vcrt_shader_load", self._L().vcrt_shader_load(path.encode()))
