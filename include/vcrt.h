@@ -351,6 +351,15 @@ int32_t vcrt_cull_tables(const vcrt_sphere* spheres, int32_t count, float* geom,
  * VCRT_SLAB=0 in the environment (the three-axis test everywhere: A/B runs and tests). */
 int32_t vcrt_cull_slab(const vcrt_sphere* spheres, int32_t count, float lohi[2]);
 
+/* The footprint tables of those tables' node level (host only, no GPU; csrc/cluster.hpp
+ * CullTables::fp_tab, csrc/tracer.hip fact (5)), as the LDS-table flat scan gets them: tables =
+ * [4][N] node bit masks (x: lo.x <= cell, hi.x >= cell; then z), params8 = {x scale, x offset,
+ * z scale, z offset, y lo, y hi, 2 Kmax, 0} and *always = the nodes every ray keeps. Returns N,
+ * the cells per table (0: culling does not apply); any pointer may be NULL. They do not depend
+ * on VCRT_SLAB. */
+int32_t vcrt_cull_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t* tables,
+                            float* params8, uint32_t* always);
+
 /* The flat culled scan's camera-ray lists for a scene and render description (host only, no
  * GPU; csrc/primary.cpp): for each 4x4-pixel quarter (qx, qy) of each local tile lt of
  * desc->rank (in the kernels' local-tile order), info[4 lt + 2 qy + qx] = offset << 4 | count

@@ -143,6 +143,8 @@ def phase(chain, mk):
             return "scan: big list"
         if "box_ray" in text or "recip_a" in text:
             return "scan: ray set-up (box ray)"
+        if "foot_mask" in text or "foot_cell" in text:
+            return "scan: node level (footprint table lookups)"
         if "push_bound_pair_nf" in text or "near_far_addr" in text:
             return "scan: node level (chunk's 8 node boxes)"
         return "scan: set-up, lists, pushes, key"

@@ -122,6 +122,10 @@ struct RendererState {
     float4* d_cnode = nullptr;
     float4* d_cnode_nf = nullptr;  // node-pair boxes, near/far layout, padded to whole chunks
     float4* d_ctop = nullptr;
+    // the footprint tables of the LDS-table flat scan (CullTables::fp_*), packed to their width
+    uint32_t* d_fp_tab = nullptr;
+    float cfp_x[2] = {1, 0}, cfp_z[2] = {1, 0}, cfp_y[2] = {0, 0}, cfp_k2 = 0;
+    uint32_t cfp_always = 0xffffffffu;
     uint32_t* d_prim_info = nullptr;  // camera-ray tile lists (primary.cpp), flat scan only
     uint16_t* d_prim_ids = nullptr;
     float4* d_cam_rec = nullptr;  // camera-relative records: big groups, sphere lists
@@ -422,6 +426,8 @@ void free_scene() {
     if (g.d_cnode) (void)hipFree(g.d_cnode);
     if (g.d_cnode_nf) (void)hipFree(g.d_cnode_nf);
     if (g.d_ctop) (void)hipFree(g.d_ctop);
+    if (g.d_fp_tab) (void)hipFree(g.d_fp_tab);
+    g.d_fp_tab = nullptr;
     if (g.d_prim_info) (void)hipFree(g.d_prim_info);
     if (g.d_prim_ids) (void)hipFree(g.d_prim_ids);
     if (g.d_cam_rec) (void)hipFree(g.d_cam_rec);
@@ -437,6 +443,19 @@ void free_scene() {
     g.ncgroups = 0;
     g.ncbig = 0;
     g.nspheres = 0;
+}
+
+// CullTables::fp_tab as the LDS-table kernel copies it (vcrt::foot_lds_bytes): two 16-bit masks
+// per word when the scene has at most 16 nodes, else one 32-bit mask per word.
+std::vector<uint32_t> pack_footprint(const vcrt::CullTables& ct) {
+    static_assert(vcrt::kFootCells == static_cast<uint32_t>(vcrt::kFootprintCells) &&
+                      vcrt::kFootCells % 2u == 0u,
+                  "footprint cells");
+    if (ct.ngroups > 128) return ct.fp_tab;
+    std::vector<uint32_t> out(ct.fp_tab.size() / 2);
+    for (size_t i = 0; i < out.size(); i++)
+        out[i] = (ct.fp_tab[2 * i] & 0xffffu) | (ct.fp_tab[2 * i + 1] << 16);
+    return out;
 }
 
 // A pair-SoA box table (cluster.hpp: 16 floats per pair of boxes) in the near/far layout of
@@ -765,10 +784,11 @@ KernelChoice select_kernel() {
     // copy for 16 waves); beyond that from global memory.
     const uint32_t tab_lds = static_cast<uint32_t>(16 * (g.ncgroups / 2 * 4 + g.ncgroups * 5));
     // flat: near/far boxes (80 B per pair, 336 B per node of 4 pairs: 16 B of bank padding),
-    // 80-B group records (the uint16 member indices inside), the chunks' node boxes (near/far,
-    // 336 B per chunk: the node level of a tracer.hip VCRT_LEVELS_NF build)
-    const uint32_t tab_lds_flat = static_cast<uint32_t>(
-        16 * (g.ncgroups / 8 * 21 + g.ncgroups * 5 + (g.ncgroups + 63) / 64 * 21));
+    // 80-B group records (the uint16 member indices inside), the footprint tables of the node
+    // level (672 B, or 1344 B beyond 16 nodes)
+    const uint32_t tab_lds_flat =
+        static_cast<uint32_t>(16 * (g.ncgroups / 8 * 21 + g.ncgroups * 5)) +
+        vcrt::foot_lds_bytes(g.ncgroups);
     const bool lane_lds = tab_lds <= g.max_lds && g.cull_lane_tables != 2;
     const bool lane_wide = lane_lds && tab_lds > 32768u;
     int variant = g.desc.kernel_variant;
@@ -1186,6 +1206,18 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
         g.cslab_on = ct.slab;
         g.cslab[0] = ct.slab_lohi[0];
         g.cslab[1] = ct.slab_lohi[1];
+        {
+            // footprint tables: 16-bit masks up to 16 nodes, as the kernel's LDS image holds them
+            const std::vector<uint32_t> packed = pack_footprint(ct);
+            VCRT_TRY(hipMalloc(&g.d_fp_tab, sizeof(uint32_t) * packed.size()));
+            VCRT_TRY(hipMemcpy(g.d_fp_tab, packed.data(), sizeof(uint32_t) * packed.size(),
+                               hipMemcpyHostToDevice));
+            std::memcpy(g.cfp_x, ct.fp_x, sizeof(g.cfp_x));
+            std::memcpy(g.cfp_z, ct.fp_z, sizeof(g.cfp_z));
+            std::memcpy(g.cfp_y, ct.fp_y, sizeof(g.cfp_y));
+            g.cfp_k2 = ct.fp_k2;
+            g.cfp_always = ct.fp_always;
+        }
         if (g.primary_lists && g.local_tiles > 0) {
             // camera rays of a tile start from its quarter's lists (primary.cpp): the groups
             // for the main scan, the spheres for the camera fast trace; info interleaved
@@ -1350,6 +1382,14 @@ static void scene_params(vcrt::TraceParams& p) {
     for (int k = 0; k < 4; k++) p.box_margin[k] = g.cmargin[k];
     p.slab[0] = g.cslab[0];
     p.slab[1] = g.cslab[1];
+    p.fp_tab = g.d_fp_tab;
+    for (int k = 0; k < 2; k++) {
+        p.fp_x[k] = g.cfp_x[k];
+        p.fp_z[k] = g.cfp_z[k];
+        p.fp_y[k] = g.cfp_y[k];
+    }
+    p.fp_k2 = g.cfp_k2;
+    p.fp_always = g.cfp_always;
     p.nspheres = g.nspheres;
     p.flags = (g.scene_bounded ? vcrt::kFlagSceneBounded : 0u) |
               (g.radii_safe ? vcrt::kFlagRadiiSafe : 0u) |
@@ -2108,6 +2148,21 @@ int32_t vcrt_cull_tables(const vcrt_sphere* spheres, int32_t count, float* geom,
         if (index) std::memcpy(index, ct.index.data(), sizeof(int32_t) * ct.index.size());
     }
     return ct.ngroups;
+}
+
+int32_t vcrt_cull_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t* tables,
+                            float* params8, uint32_t* always) {
+    if (count < 0 || (count > 0 && !spheres)) return 0;
+    vcrt::CullTables ct;
+    if (!vcrt::build_cull_tables(spheres, count, ct) || ct.fp_tab.empty()) return 0;
+    if (tables) std::memcpy(tables, ct.fp_tab.data(), sizeof(uint32_t) * ct.fp_tab.size());
+    if (params8) {
+        const float v[8] = {ct.fp_x[0], ct.fp_x[1], ct.fp_z[0], ct.fp_z[1],
+                            ct.fp_y[0], ct.fp_y[1], ct.fp_k2,   0.0f};
+        std::memcpy(params8, v, sizeof(v));
+    }
+    if (always) *always = ct.fp_always;
+    return vcrt::kFootprintCells;
 }
 
 int32_t vcrt_cull_slab(const vcrt_sphere* spheres, int32_t count, float lohi[2]) {

@@ -261,7 +261,110 @@ bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
     out.margin[1] = round_up(rmax * rmax * (1.0 + 1e-6));
     out.margin[2] = round_up(lam * (1.0 + 1e-6));
     out.margin[3] = 0.0f;
+
+    // The footprint tables (cluster.hpp): the node boxes exactly as uploaded, compared in double
+    // with the exact edges of the kernel's own cell function.
+    constexpr int N = kFootprintCells;
+    out.fp_tab.assign(4 * N, 0xffffffffu);
+    out.fp_always = 0xffffffffu;
+    const size_t nnodes = ng / kNodeGroups;
+    std::vector<Box> nb;
+    std::vector<uint32_t> nbit;
+    for (size_t ni = 0; ni < nnodes; ni++) {
+        const std::vector<int32_t> m = members_of(ni * kNodeGroups, (ni + 1) * kNodeGroups);
+        if (m.empty()) continue;
+        nb.push_back(box_of(s, m));
+        nbit.push_back(ni < 32 ? 1u << ni : 0u);
+    }
+    if (nb.empty()) return true;
+    double xlo[3], xhi[3];
+    for (int a = 0; a < 3; a++) {
+        xlo[a] = std::numeric_limits<double>::infinity();
+        xhi[a] = -xlo[a];
+        for (const Box& b : nb) {
+            xlo[a] = std::min(xlo[a], static_cast<double>(b.lo[a]));
+            xhi[a] = std::max(xhi[a], static_cast<double>(b.hi[a]));
+        }
+    }
+    out.fp_y[0] = static_cast<float>(xlo[1]);  // box coordinates: exact
+    out.fp_y[1] = static_cast<float>(xhi[1]);
+    float kmax = 0.0f;
+    uint32_t always = 0u;
+    for (size_t k = 0; k < nb.size(); k++) {
+        if (std::isinf(nb[k].K))
+            always |= nbit[k];
+        else
+            kmax = std::max(kmax, nb[k].K);
+    }
+    out.fp_k2 = round_up(2.0 * static_cast<double>(kmax));
+    bool ok = nnodes <= 32 && out.margin[2] >= 0x1p-20f;
+    for (int a = 0; a < 3 && ok; a += 2) {
+        float* so = a == 0 ? out.fp_x : out.fp_z;
+        const double w = xhi[a] - xlo[a];
+        so[0] = static_cast<float>(N / w);
+        so[1] = static_cast<float>(-xlo[a] * static_cast<double>(so[0]));
+        ok = w > 0.0 && std::isnormal(so[0]) && std::isfinite(so[1]);
+    }
+    if (!ok) {
+        out.fp_x[0] = out.fp_z[0] = 1.0f;
+        out.fp_x[1] = out.fp_z[1] = 0.0f;
+        return true;
+    }
+    out.fp_always = always;
+    // floats in order: key(x) rises with x (-inf .. +inf, -0 below +0)
+    auto key_of = [](float x) {
+        uint32_t b;
+        std::memcpy(&b, &x, sizeof b);
+        return (b & 0x80000000u) ? static_cast<int64_t>(0x7fffffffu) - static_cast<int64_t>(b & 0x7fffffffu)
+                                 : static_cast<int64_t>(0x80000000u) + static_cast<int64_t>(b);
+    };
+    auto float_of = [](int64_t k) {
+        const uint32_t b = k >= static_cast<int64_t>(0x80000000u)
+                               ? static_cast<uint32_t>(k - static_cast<int64_t>(0x80000000u))
+                               : 0x80000000u | static_cast<uint32_t>(static_cast<int64_t>(0x7fffffffu) - k);
+        float x;
+        std::memcpy(&x, &b, sizeof x);
+        return x;
+    };
+    const double inf = std::numeric_limits<double>::infinity();
+    for (int a = 0; a < 3; a += 2) {
+        const float* so = a == 0 ? out.fp_x : out.fp_z;
+        uint32_t* A = &out.fp_tab[(a == 0 ? 0 : 2) * N];
+        uint32_t* B = A + N;
+        double prev_ue = -inf;  // the largest float of the cell before
+        for (int i = 0; i < N; i++) {
+            double ue = inf;
+            if (i < N - 1) {  // the largest float whose cell is <= i: the cell never falls as x rises
+                int64_t lo = key_of(-std::numeric_limits<float>::infinity());
+                int64_t hi = key_of(std::numeric_limits<float>::infinity());
+                while (hi - lo > 1) {  // cell(lo) <= i < cell(hi)
+                    const int64_t mid = lo + (hi - lo) / 2;
+                    (footprint_cell(float_of(mid), so) <= i ? lo : hi) = mid;
+                }
+                ue = float_of(lo);
+            }
+            // the smallest float of cell i is the one after prev_ue; comparing against prev_ue
+            // itself only widens the mask
+            const double le = prev_ue;
+            const double up = ue + (8.0 * kU * std::fabs(ue) + 0x1p-100);
+            const double dn = le - (8.0 * kU * std::fabs(le) + 0x1p-100);
+            uint32_t ma = 0u, mb = 0u;
+            for (size_t k = 0; k < nb.size(); k++) {
+                if (static_cast<double>(nb[k].lo[a]) <= up) ma |= nbit[k];
+                if (static_cast<double>(nb[k].hi[a]) >= dn) mb |= nbit[k];
+            }
+            A[i] = ma;
+            B[i] = mb;
+            prev_ue = ue;
+        }
+    }
     return true;
+}
+
+int footprint_cell(float x, const float so[2]) {
+    const float f = std::fmaf(x, so[0], so[1]);
+    const float c = std::fmin(std::fmax(f, 0.0f), static_cast<float>(kFootprintCells - 1));
+    return static_cast<int>(c);  // truncation, as v_cvt_u32_f32
 }
 
 }  // namespace vcrt

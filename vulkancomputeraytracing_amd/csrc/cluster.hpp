@@ -34,7 +34,27 @@ struct CullTables {
     // y planes once per ray instead of once per box. VCRT_SLAB=0 leaves it unset (A/B).
     bool slab = false;
     float slab_lohi[2] = {0, 0};  // that lo[1], hi[1] (slab only)
+    // The footprint tables of the LDS-table flat scan (tracer.hip "Culled scan", fact (5)): node
+    // bit masks by the cell of one x or z coordinate, cell(X) = trunc(med3(fma(X, scale, offset),
+    // 0, kFootprintCells - 1)) in fp32. With ue(i) the largest and le(i) the smallest float of
+    // cell i (found with that very function; -+inf at the ends) and g = 8u |e| + 2^-100:
+    //   fp_tab[0][i] = nodes with lo.x <= ue(i) + g,   fp_tab[1][i] = nodes with hi.x >= le(i) - g,
+    // [2] and [3] the same for z; over the node boxes that have members (bit = node index, at most
+    // 32 nodes; a padding node has no bit). A scene they cannot describe (more than 32 nodes, a
+    // degenerate extent, a coordinate bound below 2^-20) gets all-ones masks. They do not depend
+    // on VCRT_SLAB.
+    std::vector<uint32_t> fp_tab;  // [4][kFootprintCells]
+    float fp_x[2] = {1, 0};        // scale, offset of the x cells
+    float fp_z[2] = {1, 0};
+    float fp_y[2] = {0, 0};        // y extent of all those node boxes (= slab_lohi on a slab scene)
+    float fp_k2 = 0;               // 2 x the largest finite K of those boxes, rounded up
+    uint32_t fp_always = 0;        // nodes whose K is +inf: every ray keeps them
 };
+
+constexpr int kFootprintCells = 84;  // = vcrt::kFootCells (vcrt_kernel_abi.h)
+
+// The cell of coordinate x, as the kernel computes it.
+int footprint_cell(float x, const float scale_offset[2]);
 
 // Builds the grouped tables. Returns false (tables empty) when culling does not apply: fewer
 // than 16 spheres or any centre/radius outside +-2^30 (or not finite).

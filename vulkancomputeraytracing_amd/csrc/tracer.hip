@@ -294,6 +294,40 @@ __device__ __forceinline__ void scan_spheres(const TraceParams& p, const float4*
 //      box (the far point 1e20, no member a ray can accept) gets the slab in place of its own y
 //      planes, so its gap may differ: it is ruled out by x and z as before, or its empty groups
 //      are tested for nothing.
+//  (5) the footprint (the LDS-table flat scan's node level, foot_mask; cluster.hpp fp_tab). If
+//      the box test of (3), (3a), (4) keeps node k for a ray (gap >= 0), bit k of the ray's mask
+//      is set; so (2)-(4) carry over and only the issued tests change. Let t0, t1 be the ray's y
+//      interval over [Ylo, Yhi], the y extent of all node boxes with members, computed as (3a)
+//      does (on a slab scene they are (3a)'s own numbers, the operands being bit-equal; otherwise
+//      Ylo <= lo.y and hi.y <= Yhi and fma(., inv, c) is monotone in its first operand, so t0 <=
+//      the box's clamped near y term and t1 >= its far one). With tn, tf the test's near and far
+//      end, t0 <= tn and tf <= t1. gap >= 0 means RN(K c2 + RN(RN(tf - tn) + c1)) >= 0, hence tf
+//      - tn >= -E, E = 1.001 (c1 + K c2) (three roundings of relative u and flushes below 2^-123,
+//      against c1 >= 2^-71: the host requires L >= 2^-20). So for x (and the same for z), with
+//      tnx, tfx the computed near and far plane terms: tnx <= tn <= tf + E <= t1 + E and tfx >=
+//      tf >= tn - E >= t0 - E. The kernel takes S = RN(RN(2 c1) + (2 Kmax) c2) >= 1.99 (c1 + K
+//      c2) for every finite K (K = +inf: the node is in `always`), ta = RN(t0 - S), tb = RN(t1 +
+//      S). |t0|, |t1| <= 1.001 (J / 2) (L + |o|_inf) + tau, so rounding ta and tb costs at most
+//      0.1 c1 + u tau, within c1's spare as the shift of (4): ta < t0 - E and t1 + E < tb, i.e.
+//      tnx < tb and tfx > ta, strictly. If tb < ta then t0 - t1 > E and no box is kept: the mask
+//      is `always`. Otherwise let p = RN(t - cx), X(t) = RN(p d'x) for t = ta, tb: with ix =
+//      (1 + e) / d'x, |e| <= 2u, X(t) ix + cx = t + (t - cx) th, |th| <= 4.01u, so Xu(t) = X(t) +
+//      8u |X(t)| and Xd(t) = X(t) - 8u |X(t)| satisfy fma(Xu(tb), ix, cx) >= tb and fma(Xd(ta),
+//      ix, cx) <= ta for ix > 0 (for ix < 0 with ta and tb exchanged); an underflowing product
+//      moves X by at most 2^-126, the host's 2^-100. For ix > 0 the near plane is lo.x: fma(lo.x,
+//      ix, cx) = tnx < tb <= fma(Xu(tb), ix, cx) gives lo.x < Xu(tb) by monotonicity, and
+//      likewise hi.x > Xd(ta); for ix < 0 the planes swap and lo.x < Xu(ta), hi.x > Xd(tb). X(ta)
+//      and X(tb) are ordered by the sign of d'x (RN is monotone), so with Xlo, Xhi the smaller and
+//      larger of the two: lo.x <= Xhi + 8u |Xhi| and hi.x >= Xlo - 8u |Xlo|. The cell function
+//      cell(X) = trunc(med3(fma(X, scale, offset), 0, N - 1)) never falls as X rises, so cell(Xhi)
+//      is the larger cell, and the host, which finds each cell's largest float ue and smallest
+//      float le with the same function and sets A[i] = {k: lo.x <= ue + 8u |ue| + 2^-100}, B[i] =
+//      {k: hi.x >= le - 8u |le| - 2^-100} (X + 8u |X| is monotone; the end cells reach +-inf),
+//      has bit k in A[cell(Xhi)] and B[cell(Xlo)]. The mask is the AND of the four lookups, OR
+//      `always`. All of ta, tb, p are finite or, when K c2 overflows, ta = -inf and tb = +inf: no
+//      inf - inf (t0, t1, cx finite), no 0 x inf (d'x != 0, scale > 0), and med3 clamps +-inf.
+//      The node pass then runs the exact line test (3) on each group box, so a node entered for
+//      nothing costs eight group-box tests and pushes what the line test lets through.
 // Waves holding a ray outside the guarded range scan the original table in reference order.
 
 // t of one candidate as hit_sphere would accept it (finite case, fact (1)).
@@ -1159,9 +1193,42 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
     h.chunk = nk;
 }
 
+// The node mask of one ray from the footprint tables (fact (5); the LDS-table kernel's node
+// level): bit k set for every node k whose box test would keep it, and for few others. t0, t1:
+// the ray's y interval over all node boxes (the slab's on a slab scene); ddx, ddz: d' of box_axis;
+// ft: the four tables in LDS (TraceParams.fp_tab), 32-bit masks when `wide` (wave-uniform).
+__device__ __forceinline__ uint32_t foot_cell(float x, const float so[2]) {
+    const float f = __builtin_fmaf(x, so[0], so[1]);  // +-inf stays +-inf: scale > 0, offset finite
+    return (uint32_t)__builtin_amdgcn_fmed3f(f, 0.0f, (float)(kFootCells - 1u));
+}
+
+__device__ __forceinline__ uint32_t foot_mask(const TraceParams& p, const BoxRay& br, float t0,
+                                              float t1, float ddx, float ddz, const float4* ft,
+                                              bool wide) {
+    const float S = __builtin_fmaf(p.fp_k2, br.c2.x, br.c1.x + br.c1.x);
+    const float ta = t0 - S, tb = t1 + S;  // t0, t1 finite; S finite or +inf
+    // where the line is at ta and at tb (cx, cz finite; d' never 0: no inf - inf, no 0 x inf)
+    const float xa = (ta - br.cx.x) * ddx, xb = (tb - br.cx.x) * ddx;
+    const float za = (ta - br.cz.x) * ddz, zb = (tb - br.cz.x) * ddz;
+    const uint32_t ixa = foot_cell(xa, p.fp_x), ixb = foot_cell(xb, p.fp_x);
+    const uint32_t iza = foot_cell(za, p.fp_z), izb = foot_cell(zb, p.fp_z);
+    // the cell rises with the coordinate: the footprint's ends are the smaller and larger cell
+    const uint32_t x0 = min(ixa, ixb), x1 = max(ixa, ixb), z0 = min(iza, izb), z1 = max(iza, izb);
+    uint32_t m;
+    if (wide) {
+        const uint32_t* t = reinterpret_cast<const uint32_t*>(ft);
+        m = t[x1] & t[kFootCells + x0] & t[2u * kFootCells + z1] & t[3u * kFootCells + z0];
+    } else {
+        const uint16_t* t = reinterpret_cast<const uint16_t*>(ft);
+        m = (uint32_t)(t[x1] & t[kFootCells + x0] & t[2u * kFootCells + z1] &
+                       t[3u * kFootCells + z0]);
+    }
+    return (tb < ta ? 0u : m) | p.fp_always;
+}
+
 // kChunks: the chunk level as per-lane chunk passes over the near/far node boxes `tnode` (many
-// chunks: the stress scene), else wave-uniform node tests on scalar-loaded boxes (two chunks:
-// the final scene).
+// chunks: the stress scene), else each lane's node mask from the footprint tables in `tnode`'s
+// place (the LDS-table kernel: two chunks at the final scene).
 // kSlab: 1 = the boxes share their y extent (kFlagSlab), box tests by the ray's y interval (3a);
 // 0 = they do not; -1 = read the flag here and branch at each run of box tests.
 template <bool kStats, int kFmt, bool kGRec, bool kChunks, uint32_t kNS, int kSlab, class WS>
@@ -1229,6 +1296,21 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
     cfloat4* top = (cfloat4*)p.ctop;
     const int ncg = p.ncgroups;
     uint32_t tops = 0;
+    // (LDS-table kernel) the lane's node mask, once per segment: no box test at the levels
+    uint32_t fmask = 0;
+    if constexpr (!kChunks) {
+        float ty0 = br.iy.x, ty1 = br.cy.x;
+        if (!slab) {  // the y interval over all node boxes, by box_ray's operations (3a)
+            const float tly = __builtin_fmaf(p.fp_y[0], br.iy.x, br.cy.x);
+            const float thy = __builtin_fmaf(p.fp_y[1], br.iy.x, br.cy.x);
+            ty0 = fmaxf(fminf(tly, thy), 0.0f);
+            ty1 = fmaxf(tly, thy);
+        }
+        const float ddx = copysignf(fmaxf(fabsf(d.x), 0x1p-40f), d.x);  // d' of box_axis
+        const float ddz = copysignf(fmaxf(fabsf(d.z), 0x1p-40f), d.z);
+        fmask = foot_mask(p, br, ty0, ty1, ddx, ddz, tnode, ncg > 128);
+        fmask = listed ? 0u : fmask;
+    }
     for (int base = 0;; base += 64) {
         uint32_t th = 1u;  // past the last chunk: drain everything
         if (base < ncg) {
@@ -1236,15 +1318,24 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
             th = nact;
             uint64_t t0 = 0;
             if constexpr (kStats) t0 = ticks();
-            // level 0, wave-uniform: the chunk's own bound (two chunks per test), per-lane bits
-            if ((base & 127) == 0) {
-                region(rrow, reg::kLevelTop);
-                const BoundPair tp = load_bound_pair(top + 4 * (base >> 7));
-                tops = ~(slab ? push_bound_pair<true>(0u, br, tp.b0, tp.b1, tp.b2, tp.b3)
-                              : push_bound_pair<false>(0u, br, tp.b0, tp.b1, tp.b2, tp.b3)) & 3u;
-                n_bounds += 2;
+            const int nn = min(8, (ncg - base) >> 3);
+            uint32_t nodes = 0;
+            bool in_chunk;
+            if constexpr (kChunks) {
+                // level 0, wave-uniform: the chunk's own bound (two chunks per test), per-lane bits
+                if ((base & 127) == 0) {
+                    region(rrow, reg::kLevelTop);
+                    const BoundPair tp = load_bound_pair(top + 4 * (base >> 7));
+                    tops = ~(slab ? push_bound_pair<true>(0u, br, tp.b0, tp.b1, tp.b2, tp.b3)
+                                  : push_bound_pair<false>(0u, br, tp.b0, tp.b1, tp.b2, tp.b3)) & 3u;
+                    n_bounds += 2;
+                }
+                in_chunk = !listed && ((tops >> ((base >> 6) & 1)) & 1u) != 0;
+            } else {
+                // the chunk's nodes of the lane's mask (bit = node index = 8 chunk + j)
+                nodes = (fmask >> ((uint32_t)base >> 3)) & ((1u << nn) - 1u);
+                in_chunk = nodes != 0u;
             }
-            const bool in_chunk = !listed && ((tops >> ((base >> 6) & 1)) & 1u) != 0;
             const uint64_t want = __ballot(in_chunk);
             if (want == 0) continue;
             region(rrow, reg::kLevelNodes);
@@ -1257,18 +1348,8 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
             h.chunk += (uint32_t)__popcll(want);
             if constexpr (kStats) pt.push += ticks() - t0;
             } else {
-            // level 1 (LDS tables: two chunks at the final scene), wave-uniform: nodes of this
-            // chunk, per-lane bits -> node entries
-            const int nn = min(8, (ncg - base) >> 3);
-            uint32_t out = 0;
-            {  // near/far planes from the LDS copy of the chunk's node boxes, by the ray's signs
-                const NearFarAddr na = near_far_addr(tnode + kNS * ((uint32_t)base >> 6),
-                                                     br.ix.x, br.iy.x, br.iz.x);
-                out = push_bound_pairs4_nf<kSlab>(br, na, slab);
-                out &= (1u << nn) - 1u;
-            }
-            n_bounds += (uint32_t)nn;
-            uint32_t nodes = in_chunk ? ~out & ((1u << nn) - 1u) : 0u;
+            // level 1 (LDS tables: two chunks at the final scene): the mask's nodes of this chunk
+            // -> node entries (no box test issued: nothing counted)
             if constexpr (kStats) {
                 const uint64_t t1 = ticks();
                 pt.levels += t1 - t0;
@@ -1578,10 +1659,11 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
     }
     if constexpr (kCull == 4) {  // LDS: near/far boxes, 80-B group records with uint16 indices
         const int nb = (P.ncgroups >> 3) * kNS, ng = P.ncgroups * 5;
-        {  // and the chunks' node boxes (near/far, padded records) after the group records
-            const int nn = ((P.ncgroups + 63) >> 6) * kNS;
-            for (int i = threadIdx.x; i < nn; i += blockDim.x)
-                if (i % kNS != 20u) lds_geom[nb + ng + i] = tnode[i - i / kNS];
+        // and the node level's footprint tables (fact (5)) after the group records
+        const int nf = (int)(foot_lds_bytes(P.ncgroups) >> 4);
+        {
+            uint32_t* ft = reinterpret_cast<uint32_t*>(lds_geom + nb + ng);
+            for (int i = threadIdx.x; i < 4 * nf; i += blockDim.x) ft[i] = P.fp_tab[i];
         }
         for (int i = threadIdx.x; i < nb; i += blockDim.x)
             if (i % kNS != 20u) lds_geom[i] = tbound[i - i / kNS];
@@ -1599,9 +1681,10 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         __syncthreads();
         tbound = lds_geom;
         tg.geom = lds_geom + nb;
-        tnode = lds_geom + nb + ng;
-        ws = reinterpret_cast<WS*>(lds_geom + nb + ng + ((P.ncgroups + 63) >> 6) * kNS) +
-             (threadIdx.x >> 6);
+        tnode = lds_geom + nb + ng;  // (this kernel: the footprint tables)
+        ws = reinterpret_cast<WS*>(lds_geom + nb + ng + nf) + (threadIdx.x >> 6);
+        static_assert(foot_lds_bytes(128) % 16u == 0u && foot_lds_bytes(256) % 16u == 0u,
+                      "whole float4s");
         static_assert(kNS == 21u && sizeof(WS) == kWaveScratchBytes8,
                       "host LDS size (capi.cpp select_kernel)");
     }

@@ -131,6 +131,16 @@ struct TraceParams {
     // scans compute the two y-plane terms once per ray (tracer.hip box_ray, fact (3a)). Last in
     // the block, so a code object built before them reads the same layout.
     float slab[2];
+    // The footprint tables of the LDS-table flat scan (cluster.hpp CullTables::fp_*; tracer.hip
+    // fact (5)): fp_tab holds four tables of kFootCells node masks (x: lo <= cell, hi >= cell; z
+    // the same), 16-bit when the scene has at most 16 nodes (ncgroups <= 128), else 32-bit;
+    // fp_x / fp_z the cells' (scale, offset); fp_y the y extent of all node boxes with members;
+    // fp_k2 twice their largest finite K; fp_always the nodes every ray keeps. After the slab,
+    // for the same reason.
+    const uint32_t* fp_tab;
+    float fp_x[2], fp_z[2], fp_y[2];
+    float fp_k2;
+    uint32_t fp_always;
 };
 
 constexpr uint32_t kQueueStride = 32;  // u32s between the work-queue counters (128 B)
@@ -150,7 +160,13 @@ static_assert(kRingMaxEntries + 1u <= (1u << (32u - kRingQBits)), "ring entry fi
 
 constexpr int32_t kFlatMaxGroups = 1024;   // CULL_FLAT 16-bit entries: 10-bit group / node fields
 constexpr int32_t kFlatMaxGroups8 = 256;   // the LDS-table kernel: 8-bit fields, 16-bit candidates
-constexpr uint32_t kWaveScratchBytes = 4360;   // CULL_FLAT per-wave LDS stacks, 16-bit entries
+constexpr uint32_t kFootCells = 84;  // cells per footprint table: 4 x 84 16-bit masks take the
+                                     // 672 B of the final scene's two chunk records they replace
+// bytes of the footprint tables in the LDS-table kernel's image
+constexpr uint32_t foot_lds_bytes(int32_t ncgroups) {
+    return 4u * kFootCells * (ncgroups > 128 ? 4u : 2u);
+}
+constexpr uint32_t kWaveScratchBytes = 4360;  // CULL_FLAT per-wave LDS stacks, 16-bit entries
 constexpr uint32_t kWaveScratchBytes8 = 3464;  // 16-bit candidates, no chunk stack (LDS tables)
 constexpr uint32_t kWaveScratchBytesWide = 6920;  // the same with 32-bit entries (global tables)
 constexpr uint32_t kFlagReverseOrder = 1u;  // hand out work items last-to-first

@@ -104,6 +104,27 @@ def cull_slab(spheres: np.ndarray) -> tuple[np.float32, np.float32] | None:
     return lohi[0], lohi[1]
 
 
+def cull_footprint(spheres: np.ndarray) -> dict | None:
+    """The footprint tables of `spheres`' node level (host computation, no GPU), as the LDS-table
+    flat scan gets them: ``tables`` [4, N] uint32 node masks (x: lo <= cell, hi >= cell; then z),
+    ``x`` / ``z`` the cells' (scale, offset) -- cell(X) = trunc(clamp(fma(X, scale, offset), 0,
+    N - 1)) in fp32 --, ``y`` the y extent of the node boxes with members, ``k2`` twice their
+    largest finite K and ``always`` the mask of nodes every ray keeps. None without culling
+    tables. Independent of VCRT_SLAB."""
+    spheres = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+    lib = N.lib()
+    n = lib.vcrt_cull_footprint(spheres.ctypes.data, len(spheres), None, None, None)
+    if n == 0:
+        return None
+    tables = np.zeros((4, n), np.uint32)
+    par = np.zeros(8, np.float32)
+    always = ctypes.c_uint32(0)
+    lib.vcrt_cull_footprint(spheres.ctypes.data, len(spheres), tables.ctypes.data,
+                            par.ctypes.data, ctypes.byref(always))
+    return {"tables": tables, "x": par[0:2].copy(), "z": par[2:4].copy(), "y": par[4:6].copy(),
+            "k2": par[6], "always": int(always.value)}
+
+
 def primary_lists(spheres: np.ndarray, desc) -> dict | None:
     """The flat scan's camera-ray lists (host computation, no GPU; csrc/primary.cpp) for
     `spheres` and a RenderDesc: ``info`` [4 x local tiles] uint32, entry 4 lt + 2 qy + qx for the
