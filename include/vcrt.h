@@ -18,7 +18,9 @@
  *                            globals.glsl:9-24, include/Common.hpp:23-24
  *
  * Added (the reference has no equivalents): read-back of the rgba32f framebuffer, statistics,
- * rank/world tile sharding and the tile re-assembly used after a multi-GPU gather.
+ * rank/world tile sharding and the tile re-assembly used after a multi-GPU gather; ray queries
+ * on rays the caller supplies (vcrt_trace_rays: radiance and first hit) and occlusion queries
+ * (vcrt_occlude_rays: is anything in the way within a per-ray reach).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -310,6 +312,39 @@ vcrt_result vcrt_trace_rays(const float* origins, const float* dirs, uint32_t co
 vcrt_result vcrt_trace_rays_device(const float* origins, const float* dirs, uint32_t count,
                                    int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
                                    vcrt_ray_stats* stats);
+
+/* Occlusion queries: is anything in the way within a ray's reach? Shadow rays, ambient occlusion,
+ * line of sight, probe visibility. Added.
+ * origins, dirs: [count][3] floats, packed; dirs are not normalised and t is in units of dir, as
+ * in the reference. tmax: [count] floats, each ray's reach T, or NULL: the reference's `infinity`
+ * (1e5, globals.glsl:26) for every ray. occluded: [count] bytes. stats may be NULL.
+ *
+ * occluded[i] = 1 iff hit_sphere (functions.glsl:14-40) with min_t = 0.001 and max_t = T accepts
+ * some sphere of the array given to vcrt_set_scene, every fp32 operation rounded on its own in
+ * the reference's order; else 0: one bit per ray, bit for bit. With tmax NULL, occluded[i] ==
+ * (the first hit of vcrt_trace_rays has sphere >= 0). T may be any float that is not NaN:
+ * T <= 0.001 gives 0; +inf and values above 1e5 are allowed and see hits the first-hit query
+ * cannot. This holds for rays of six finite components, a direction that is not all zero and a
+ * T that is not NaN; any other ray is traced without a fault and writes 0 or 1, deterministic,
+ * otherwise unspecified, changing no other ray's answer. As for vcrt_trace_rays, results do not
+ * depend on the order of the batch, on how it is split over calls, on the description's rank,
+ * world_size or kernel_variant, or on vcrt_comm_init; the framebuffer, the progressive
+ * accumulation, vcrt_stats and the cost order are left alone; exactly count bytes are written;
+ * count == 0 succeeds and writes nothing.
+ * stats: segments = count (one scan per ray), group_tests and bound_tests as for vcrt_trace_rays
+ * (a scan stops once every ray of its wave is occluded), kernel = "vcrt_occlude_rays".
+ * Host pointers; staged through device buffers that are kept (and grown) between calls and freed
+ * by vcrt_end.
+ * Errors: VCRT_ERROR_INITIALIZATION_FAILED before vcrt_begin and for NULL origins, dirs or
+ * occluded with count > 0; VCRT_ERROR_FORMAT_NOT_SUPPORTED for count > 2^30;
+ * VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object has no vcrt_occlude_rays kernel (an
+ * A/B build of an older tree). */
+vcrt_result vcrt_occlude_rays(const float* origins, const float* dirs, const float* tmax,
+                              uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats);
+/* The same with device pointers (no alignment requirement), on the render stream; returns when
+ * done. */
+vcrt_result vcrt_occlude_rays_device(const float* origins, const float* dirs, const float* tmax,
+                                     uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats);
 
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file

@@ -9,8 +9,13 @@ gap is what the query's own parts cost -- ray loads, refill, stores, no LDS tabl
 default variant (what the flat scan would still buy); the CULL_LANE frames are also timed with
 their tables left in global memory, where the query reads them. Prints one JSON object and,
 with --out, writes it to a file (profiles/ray_query_bench.json).
+
+--occlusion instead times the occlusion query (vcrt_occlude_rays) on the same rays: against the
+depth-1 closest-hit query, alternating, and on shadow rays from the first-hit points to a point
+light (profiles/occlusion_bench.json).
 """
 import argparse
+import ctypes
 import json
 import math
 import os
@@ -98,6 +103,80 @@ def frame_rate(a, variant, tables=None):
             "block_threads": st["block_threads"]}
 
 
+def summary(ms, st, rays):
+    med = statistics.median(ms)
+    return {"kernel": st["kernel"], "rays": rays, "kernel_ms_median": med,
+            "kernel_ms_min": min(ms), "kernel_ms_max": max(ms), "rays_per_s": rays / (med * 1e-3),
+            "group_tests_per_ray": st["group_tests"] / rays,
+            "bound_tests_per_ray": st["bound_tests"] / rays}
+
+
+def occlusion(a, origins, dirs):
+    """--occlusion: vcrt_occlude_rays against vcrt_trace_rays at depth 1 (hits only) on the same
+    rays, the two alternating launch by launch in one renderer; then shadow rays from each first
+    hit to a point light. The answers are compared too (the same rays, the same scene)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    n = len(dirs)
+    res = {"workload": {"width": a.width, "height": a.height, "spp": a.spp, "scene": a.scene,
+                        "rays": n, "ray_order": a.order, "launches": a.launches,
+                        "warmup": a.warmup, "light": list(a.light)}}
+    desc = vc.RenderDesc(width=a.width, height=a.height, samples_per_pixel=a.spp,
+                         max_depth=a.depth, device=0)
+    lib = vc._native.lib()
+    with vc.Renderer(desc, a.scene) as r:
+        to, td = torch.from_numpy(origins).to(dev), torch.from_numpy(dirs).to(dev)
+        # (a) is anything hit at all: the closest-hit query at depth 1 against the any-hit one
+        hits_t = torch.empty((n, 8), dtype=torch.int32, device=dev)
+        ms_hit, ms_occ = [], []
+        st_hit = vc._native.vcrt_ray_stats()
+        for i in range(a.warmup + a.launches):
+            torch.cuda.synchronize(dev)
+            vc._native.check("vcrt_trace_rays_device", lib.vcrt_trace_rays_device(
+                to.data_ptr(), td.data_ptr(), n, 1, None, hits_t.data_ptr(),
+                ctypes.byref(st_hit)))
+            occ, st_occ = r.occluded(to, td, stats=True)
+            if i >= a.warmup:
+                ms_hit.append(st_hit.kernel_ms)
+                ms_occ.append(st_occ["kernel_ms"])
+        hit = {"kernel": st_hit.kernel.decode(), "group_tests": st_hit.group_tests,
+               "bound_tests": st_hit.bound_tests}
+        res["first_hit_depth1"] = summary(ms_hit, hit, n)
+        res["occluded_default_reach"] = summary(ms_occ, st_occ, n)
+        rec = hits_t.cpu().numpy()
+        occ = occ.cpu().numpy()
+        sphere = rec[:, 1]
+        res["same_answers"] = bool(np.array_equal(occ, sphere >= 0))
+        res["occluded_fraction"] = float(occ.mean())
+        res["occluded_over_first_hit"] = (res["first_hit_depth1"]["kernel_ms_median"] /
+                                          res["occluded_default_reach"]["kernel_ms_median"])
+        # (b) shadow rays: from each first-hit point o + t d (fp32) to the light, reach 1
+        sel = sphere >= 0
+        t = np.ascontiguousarray(rec[:, 0]).view(f32)[sel].reshape(-1, 1)
+        so = np.ascontiguousarray(origins[sel] + t * dirs[sel], dtype=f32)
+        sd = np.ascontiguousarray(np.array(a.light, f32) - so, dtype=f32)
+        del to, td, hits_t
+        to, td = torch.from_numpy(so).to(dev), torch.from_numpy(sd).to(dev)
+        ms, st = [], {}
+        for i in range(a.warmup + a.launches):
+            shadow, st = r.occluded(to, td, 1.0, stats=True)
+            if i >= a.warmup:
+                ms.append(st["kernel_ms"])
+        res["shadow_rays"] = summary(ms, st, len(so))
+        res["shadow_rays"]["occluded_fraction"] = float(shadow.cpu().numpy().mean())
+        del to, td
+    return res
+
+
+def write(res, out):
+    text = json.dumps(res, indent=1)
+    print(text)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--width", type=int, default=1920)
@@ -109,12 +188,19 @@ def main():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--order", choices=("tile", "row"), default="tile")
     p.add_argument("--out", default=None)
+    p.add_argument("--occlusion", action="store_true",
+                   help="time vcrt_occlude_rays against vcrt_trace_rays at depth 1, and shadow "
+                        "rays to --light (profiles/occlusion_bench.json)")
+    p.add_argument("--light", type=float, nargs=3, default=(0.0, 20.0, 0.0))
     a = p.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("ray_query_bench: no GPU (there is no CPU path to time)")
     dev = torch.device("cuda", 0)
     origins, dirs = camera_rays(a.width, a.height, a.spp, a.order)
+    if a.occlusion:
+        write(occlusion(a, origins, dirs), a.out)
+        return
     res = {"workload": {"width": a.width, "height": a.height, "spp": a.spp, "depth": a.depth,
                         "scene": a.scene, "rays": len(dirs), "ray_order": a.order,
                         "launches": a.launches, "warmup": a.warmup}}
@@ -142,12 +228,7 @@ def main():
     res["query_over_default"] = q / res["frame_default"]["segments_per_s"]
     # the same rays: the frame path counts the same segments
     res["same_segments"] = res["query"]["segments"] == res["frame_cull_lane"]["segments"]
-    text = json.dumps(res, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    write(res, a.out)
 
 
 if __name__ == "__main__":

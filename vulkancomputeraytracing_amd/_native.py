@@ -176,6 +176,13 @@ SIGNATURES = {
     "vcrt_trace_rays_device": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.POINTER(vcrt_ray_stats)]),
+    "vcrt_occlude_rays": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_uint32, ctypes.c_void_p,
+                                           ctypes.POINTER(vcrt_ray_stats)]),
+    "vcrt_occlude_rays_device": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.c_void_p,
+                                                  ctypes.POINTER(vcrt_ray_stats)]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

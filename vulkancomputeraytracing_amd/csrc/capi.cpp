@@ -74,6 +74,12 @@ struct RendererState {
     uint4* d_rq_hits = nullptr;
     size_t rq_rays_cap = 0, rq_radiance_cap = 0, rq_hits_cap = 0;  // in rays
     void* d_rq_counters = nullptr;
+    // occlusion queries (vcrt_occlude_rays; null: the code object predates them): the host call
+    // stages its rays in d_rq_rays and the reaches and answers here; tallies in d_rq_counters
+    hipFunction_t k_occlude_rays = nullptr;
+    float* d_oq_tmax = nullptr;
+    uint8_t* d_oq_occluded = nullptr;
+    size_t oq_tmax_cap = 0, oq_occluded_cap = 0;  // in rays
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -534,6 +540,11 @@ VkResult bind_kernels() {
     if (hipModuleGetFunction(&g.k_trace_rays, m, "vcrt_trace_rays") != hipSuccess) {
         (void)hipGetLastError();
         g.k_trace_rays = nullptr;
+    }
+    // optional: the occlusion-query kernel (vcrt_occlude_rays answers the same)
+    if (hipModuleGetFunction(&g.k_occlude_rays, m, "vcrt_occlude_rays") != hipSuccess) {
+        (void)hipGetLastError();
+        g.k_occlude_rays = nullptr;
     }
     VCRT_TRY(hipModuleGetFunction(&g.k_trace_cull_lane_lds_wide, m,
                                   "vcrt_trace_cull_lane_lds_wide"));
@@ -1783,6 +1794,8 @@ vcrt_result vcrt_end(void) {
     if (g.d_rq_radiance) (void)hipFree(g.d_rq_radiance);
     if (g.d_rq_hits) (void)hipFree(g.d_rq_hits);
     if (g.d_rq_counters) (void)hipFree(g.d_rq_counters);
+    if (g.d_oq_tmax) (void)hipFree(g.d_oq_tmax);
+    if (g.d_oq_occluded) (void)hipFree(g.d_oq_occluded);
     DestroyShaderStage(&g.stage);
     if (g.ev_start) (void)hipEventDestroy(g.ev_start);
     if (g.ev_stop) (void)hipEventDestroy(g.ev_stop);
@@ -1826,6 +1839,19 @@ hipError_t grow(void** buf, size_t* cap, size_t rays, size_t bytes_each) {
     return e;
 }
 
+// A query's grid: the blocks of kQueryBlock threads the occupancy query admits per CU, on every
+// CU, capped at the blocks the batch fills.
+constexpr uint32_t kQueryBlock = 256;
+uint32_t query_grid(hipFunction_t f, uint32_t count) {
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, kQueryBlock, 0) !=
+            hipSuccess ||
+        per_cu <= 0)
+        per_cu = 1;
+    return std::min<uint32_t>(static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(g.num_cus),
+                              (count + kQueryBlock - 1) / kQueryBlock);
+}
+
 // The launch on device pointers (checked by the callers): a persistent grid sized from the
 // occupancy query as a frame's is, capped at the batch; returns when the kernel is done.
 VkResult ray_query_device(const float* origins, const float* dirs, uint32_t count,
@@ -1847,18 +1873,10 @@ VkResult ray_query_device(const float* origins, const float* dirs, uint32_t coun
     p.count = count;
     p.work = static_cast<uint32_t*>(g.d_rq_counters);
     p.tallies = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_rq_counters) + 8);
-    const uint32_t block = 256;
-    int per_cu = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g.k_trace_rays, block, 0) !=
-            hipSuccess ||
-        per_cu <= 0)
-        per_cu = 1;
-    const uint32_t grid =
-        std::min<uint32_t>(static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(g.num_cus),
-                           (count + block - 1) / block);
+    const uint32_t grid = query_grid(g.k_trace_rays, count);
     VCRT_TRY(hipMemsetAsync(g.d_rq_counters, 0, kRayCounterBytes, g.stream));
     VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
-    const VkResult r = launch(g.k_trace_rays, grid, block, 0, p);
+    const VkResult r = launch(g.k_trace_rays, grid, kQueryBlock, 0, p);
     if (r != VK_SUCCESS) return r;
     VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
     unsigned long long counters[4] = {0, 0, 0, 0};
@@ -1917,6 +1935,95 @@ vcrt_result vcrt_trace_rays(const float* origins, const float* dirs, uint32_t co
     if (hits)
         VCRT_TRY(hipMemcpyAsync(hits, g.d_rq_hits, sizeof(vcrt_ray_hit) * n,
                                 hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    return VCRT_SUCCESS;
+}
+
+// ---- occlusion queries --------------------------------------------------------------------
+
+namespace {
+
+vcrt_result occlusion_args(const float* origins, const float* dirs, uint32_t count,
+                           const uint8_t* occluded) {
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (count > 0 && (!origins || !dirs || !occluded)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (count > kRayQueryMax) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (!g.k_occlude_rays) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    return VCRT_SUCCESS;
+}
+
+// The launch on device pointers (checked by the callers): every ray is one scan, so the grid
+// holds no more waves than the occupancy query admits and no more blocks than the batch fills;
+// returns when the kernel is done.
+VkResult occlusion_device(const float* origins, const float* dirs, const float* tmax,
+                          uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats) {
+    if (stats) {
+        *stats = vcrt_ray_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_occlude_rays");
+    }
+    if (count == 0) return VK_SUCCESS;
+    if (!g.d_rq_counters) VCRT_TRY(hipMalloc(&g.d_rq_counters, kRayCounterBytes));
+    vcrt::OcclusionParams p{};
+    scene_params(p.scene);
+    p.origins = origins;
+    p.dirs = dirs;
+    p.tmax = tmax;
+    p.occluded = occluded;
+    p.count = count;
+    p.tallies = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_rq_counters) + 8);
+    const uint32_t grid = query_grid(g.k_occlude_rays, count);
+    VCRT_TRY(hipMemsetAsync(g.d_rq_counters, 0, kRayCounterBytes, g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
+    const VkResult r = launch(g.k_occlude_rays, grid, kQueryBlock, 0, p);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
+    unsigned long long counters[4] = {0, 0, 0, 0};
+    if (stats)
+        VCRT_TRY(hipMemcpyAsync(counters, g.d_rq_counters, kRayCounterBytes,
+                                hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) {
+        float ms = 0.f;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+        stats->kernel_ms = ms;
+        stats->segments = count;  // one scan per ray
+        stats->group_tests = counters[1];
+        stats->bound_tests = counters[2];
+    }
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_occlude_rays_device(const float* origins, const float* dirs, const float* tmax,
+                                     uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats) {
+    const vcrt_result a = occlusion_args(origins, dirs, count, occluded);
+    if (a != VCRT_SUCCESS) return a;
+    return occlusion_device(origins, dirs, tmax, count, occluded, stats);
+}
+
+vcrt_result vcrt_occlude_rays(const float* origins, const float* dirs, const float* tmax,
+                              uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats) {
+    const vcrt_result a = occlusion_args(origins, dirs, count, occluded);
+    if (a != VCRT_SUCCESS) return a;
+    const size_t n = count, in_bytes = 3 * sizeof(float) * n;
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_rays), &g.rq_rays_cap, n, 6 * sizeof(float)));
+    if (tmax)
+        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_oq_tmax), &g.oq_tmax_cap, n, sizeof(float)));
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_oq_occluded), &g.oq_occluded_cap, n, 1));
+    float* d_origins = g.d_rq_rays;
+    float* d_dirs = g.d_rq_rays + 3 * n;
+    if (n) {
+        VCRT_TRY(hipMemcpyAsync(d_origins, origins, in_bytes, hipMemcpyHostToDevice, g.stream));
+        VCRT_TRY(hipMemcpyAsync(d_dirs, dirs, in_bytes, hipMemcpyHostToDevice, g.stream));
+        if (tmax)
+            VCRT_TRY(hipMemcpyAsync(g.d_oq_tmax, tmax, sizeof(float) * n, hipMemcpyHostToDevice,
+                                    g.stream));
+    }
+    const VkResult r = occlusion_device(d_origins, d_dirs, tmax ? g.d_oq_tmax : nullptr, count,
+                                        g.d_oq_occluded, stats);
+    if (r != VK_SUCCESS || n == 0) return r;
+    VCRT_TRY(hipMemcpyAsync(occluded, g.d_oq_occluded, n, hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     return VCRT_SUCCESS;
 }

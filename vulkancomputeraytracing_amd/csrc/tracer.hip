@@ -328,6 +328,17 @@ __device__ __forceinline__ void scan_spheres(const TraceParams& p, const float4*
 //      inf - inf (t0, t1, cx finite), no 0 x inf (d'x != 0, scale > 0), and med3 clamps +-inf.
 //      The node pass then runs the exact line test (3) on each group box, so a node entered for
 //      nothing costs eight group-box tests and pushes what the line test lets through.
+//  (6) any hit (occlusion queries, occlude_culled_lane). The question "does hit_sphere accept
+//      some sphere with min_t and a fixed max_t = T" is an OR over the spheres, each term a
+//      function of that sphere and the ray alone (max_t never shrinks), so the visiting order and
+//      the point at which a lane stops do not matter. (2)-(4) do not involve max_t: a box that is
+//      ruled out holds no member with disc_f >= 0 and (hb_f < 0 or cc_f < 0), hence none that
+//      hit_sphere could accept for any T, +inf included. For a member that passes may_hit,
+//      hit_sphere takes root1 = RN((-hb - sq) / a) unless root1 <= min_t or T <= root1, then
+//      root2 = RN((-hb + sq) / a) under the same test. sq >= 0 and a > 0, and rounding is
+//      monotone, so root2 >= root1: a root1 rejected for T <= root1 (and not for root1 <= min_t)
+//      leaves T <= root2, rejected too. So the member is accepted exactly when t = candidate_t
+//      (root1 if root1 > min_t, else root2) satisfies min_t < t < T.
 // Waves holding a ray outside the guarded range scan the original table in reference order.
 
 // t of one candidate as hit_sphere would accept it (finite case, fact (1)).
@@ -3076,6 +3087,256 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_trace_rays(RayQueryParams
         if (total) atomicAdd(p.tallies + 0, total);
         atomicAdd(p.tallies + 1, wh / 2u);
         atomicAdd(p.tallies + 2, wb);
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// Occlusion queries: is any sphere accepted by hit_sphere between min_t and the ray's own reach
+// (fact (6))? A code-generation unit of its own (Makefile, part 4).
+#if !defined(VCRT_PART) || VCRT_PART == 4
+namespace {
+
+// min_t < t < T: hit_sphere's strict comparisons on the candidate's t (fact (6))
+__device__ __forceinline__ bool reaches(float t, float T) { return (t > kMinT) & (t < T); }
+
+// exact_group_uniform for an any-hit query: true when the lane's ray accepts a member of the
+// group (the big-sphere list; candidate_t_fast returns candidate_t's t wherever that t is above
+// min_t, whatever the far limit).
+__device__ __forceinline__ bool occlude_group_uniform(cfloat4* rec, const CullRay& r, v2f dx,
+                                                      v2f dy, v2f dz, v2f a2, float a, float ya,
+                                                      float T) {
+    const float4 q0 = rec[0], q1 = rec[1], idf = rec[4];
+    v2f hb01, cc01, d01, hb23 = {0.f, 0.f}, cc23 = {0.f, 0.f}, d23 = {-1.f, -1.f};
+    pair_disc_cc(r.ox, r.oy, r.oz, dx, dy, dz, a2, q0, q1, hb01, cc01, d01);
+    // members 2 and 3 only when the group has them (wave-uniform)
+    if (__float_as_int(idf.z) >= 0 || __float_as_int(idf.w) >= 0)
+        pair_disc_cc(r.ox, r.oy, r.oz, dx, dy, dz, a2, rec[2], rec[3], hb23, cc23, d23);
+    const float m4 = fmaxf(fmaxf(d01.x, d01.y), fmaxf(d23.x, d23.y));
+    bool occ = false;
+    if (__ballot(!(m4 < 0.0f))) {
+        if (may_hit(hb01.x, cc01.x, d01.x))
+            occ |= reaches(candidate_t_fast(hb01.x, d01.x, a, ya), T);
+        if (may_hit(hb01.y, cc01.y, d01.y))
+            occ |= reaches(candidate_t_fast(hb01.y, d01.y, a, ya), T);
+        if (may_hit(hb23.x, cc23.x, d23.x))
+            occ |= reaches(candidate_t_fast(hb23.x, d23.x, a, ya), T);
+        if (may_hit(hb23.y, cc23.y, d23.y))
+            occ |= reaches(candidate_t_fast(hb23.y, d23.y, a, ya), T);
+    }
+    return occ;
+}
+
+// scan_culled_lane for an any-hit query with the far limit T (fact (6)): the same big-group
+// list and the same chunk, node and group box tests on the global tables, but a lane that has
+// found an accepted member (occ) asks for nothing more -- it drops out of the chunk, node and
+// group ballots -- and the wave leaves the chunk loop once every lane is occluded. Lanes that
+// enter occluded (the lanes past the batch's end) never ask for anything.
+__device__ __forceinline__ bool occlude_culled_lane(const TraceParams& p, const float4* tbound,
+                                                    const float4* tgroup, const f3 o, const f3 d,
+                                                    const float T, bool occ,
+                                                    uint32_t& groups_tested,
+                                                    uint32_t& bounds_tested) {
+    const float a = dot(d, d);
+    const float ya = recip_a(a);
+    CullRay r;
+    r.ox = (v2f){o.x, o.x};
+    r.oy = (v2f){o.y, o.y};
+    r.oz = (v2f){o.z, o.z};
+    const BoxRay br = box_ray(p, o, d, ya);
+    const v2f dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z}, a2 = {a, a};
+    cfloat4* node = (cfloat4*)p.cnode;
+    cfloat4* top = (cfloat4*)p.ctop;
+    const int ncg = p.ncgroups;
+    // per-query pass counters, wave-uniform
+    uint32_t n_bounds = 0, n_groups = 0;
+    for (int gb = 0; gb < p.nbig; ++gb) {  // the big spheres (scalar loads)
+        if (__ballot(!occ) == 0) break;
+        ++n_groups;
+        occ |= occlude_group_uniform((cfloat4*)p.cgroup + 5 * gb, r, dx, dy, dz, a2, a, ya, T);
+    }
+    uint32_t tops = 0;
+    for (int base = 0; base < ncg; base += 64) {
+        if (__ballot(!occ) == 0) break;
+        // level 0, wave-uniform: the chunk's own bound (two chunks per test), per-lane bits
+        if ((base & 127) == 0) {
+            const BoundPair tp = load_bound_pair(top + 4 * (base >> 7));
+            tops = ~push_bound_pair(0u, br, tp.b0, tp.b1, tp.b2, tp.b3) & 3u;
+            n_bounds += 2;
+        }
+        const bool in_chunk = !occ && ((tops >> ((base >> 6) & 1)) & 1u) != 0;
+        if (__ballot(in_chunk) == 0) continue;
+        // level 1, wave-uniform: nodes of this chunk, per-lane bits
+        const int nn = min(8, (ncg - base) >> 3);
+        cfloat4* nb = node + 4 * (base >> 4);
+        // sign bits pushed from the last node down, so bit j ends up = node j ruled out
+        uint32_t out = 0;
+        BoundPair cur = load_bound_pair(nb + 4 * ((nn - 2) >> 1));
+        for (int j = nn - 2; j >= 0; j -= 2) {
+            const BoundPair nxt = load_bound_pair(nb + 4 * ((j >= 2 ? j - 2 : j) >> 1));
+            out = push_bound_pair(out, br, cur.b0, cur.b1, cur.b2, cur.b3);
+            cur = nxt;
+        }
+        uint32_t nodes = in_chunk ? ~out & ((1u << nn) - 1u) : 0u;
+        n_bounds += (uint32_t)nn;
+        // level 2, per lane: the groups of this lane's nodes
+        uint64_t need = 0;
+        while (__ballot(nodes != 0)) {
+            n_bounds += 8;  // one wave pass = 8 bound tests
+            if (nodes) {
+                const int j = __builtin_ctz(nodes);
+                nodes &= nodes - 1;
+                const float4* gb = tbound + 4 * (base >> 1) + __umul24((uint32_t)j, 16u);
+                uint32_t gout = 0;
+#pragma unroll
+                for (int k = 3; k >= 0; k--) {
+                    gout = push_bound_pair(gout, br, gb[4 * k], gb[4 * k + 1], gb[4 * k + 2],
+                                           gb[4 * k + 3]);
+                }
+                need |= (uint64_t)(~gout & 0xffu) << (8 * j);
+            }
+        }
+        // the exact test, per lane on its own groups, until the lane is occluded
+        while (__ballot(need != 0)) {
+            ++n_groups;
+            if (need) {
+                const int k = __builtin_ctzll(need);
+                need &= need - 1;
+                const float4* g = tgroup + 5 * base + __umul24((uint32_t)k, 5u);
+                const float4 q0 = g[0], q1 = g[1], q2 = g[2], q3 = g[3];
+                v2f hb01, cc01, d01, hb23, cc23, d23;
+                pair_disc_cc(r.ox, r.oy, r.oz, dx, dy, dz, a2, q0, q1, hb01, cc01, d01);
+                pair_disc_cc(r.ox, r.oy, r.oz, dx, dy, dz, a2, q2, q3, hb23, cc23, d23);
+                // bit s = member s may be accepted (sign bits, pushed from member 3 down)
+                uint32_t hits = push_sign(0u, hit_sign(hb23.y, cc23.y, d23.y));
+                hits = push_sign(hits, hit_sign(hb23.x, cc23.x, d23.x));
+                hits = push_sign(hits, hit_sign(hb01.y, cc01.y, d01.y));
+                hits = push_sign(hits, hit_sign(hb01.x, cc01.x, d01.x));
+                while (hits) {
+                    const int s = __builtin_ctz(hits);
+                    hits &= hits - 1;
+                    const float hb = s == 0 ? hb01.x : s == 1 ? hb01.y : s == 2 ? hb23.x : hb23.y;
+                    const float ds = s == 0 ? d01.x : s == 1 ? d01.y : s == 2 ? d23.x : d23.y;
+                    if (reaches(candidate_t(hb, ds, a), T)) {
+                        occ = true;
+                        hits = 0u;
+                        need = 0u;
+                    }
+                }
+            }
+        }
+    }
+    tally(bounds_tested, __builtin_amdgcn_readfirstlane(n_bounds));
+    tally(groups_tested, 2u * __builtin_amdgcn_readfirstlane(n_groups));  // half-groups
+    return occ;
+}
+
+// hit_sphere's acceptance (functions.glsl:14-40) after the discriminant test passed, against a
+// far limit that does not shrink: accept_root's logic, literally.
+__device__ __forceinline__ bool accepts_root(float hb, float disc, float a, float T) {
+    const float min_t = kMinT;
+    const float sq = __builtin_sqrtf(disc);
+    float root = (-hb - sq) / a;
+    bool ok = true;
+    if (root <= min_t || T <= root) {
+        root = (-hb + sq) / a;
+        ok = !(root <= min_t || T <= root);
+    }
+    return ok;
+}
+
+// The linear scan for an any-hit query, any ray: four spheres per step from the original table
+// (scalar loads, the next group prefetched), every sphere whose discriminant is not negative put
+// through accepts_root, until the whole wave is occluded. Padding spheres (index >= n) never
+// accept.
+__device__ __forceinline__ bool occlude_linear(const TraceParams& p, int n, const f3 o,
+                                               const f3 d, const float T, bool occ,
+                                               uint32_t& groups_tested) {
+    const float a = dot(d, d);
+    const v2f ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z};
+    const v2f dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z}, a2 = {a, a};
+    const int ngroups = (n + 3) >> 2;
+    uint32_t n_groups = 0;
+    Group g = load_group<false>(nullptr, p, 0);
+    for (int gi = 0; gi < ngroups; ++gi) {
+        if (__ballot(!occ) == 0) break;
+        ++n_groups;
+        const Group nx = load_group<false>(nullptr, p, gi + 1);  // table padded by one group
+        v2f hb01, d01, hb23, d23;
+        pair_disc(ox, oy, oz, dx, dy, dz, a2, g.q[0], g.q[1], hb01, d01);
+        pair_disc(ox, oy, oz, dx, dy, dz, a2, g.q[2], g.q[3], hb23, d23);
+        const int j = 4 * gi;
+        const bool e0 = !occ && !(d01.x < 0.0f), e1 = !occ && !(d01.y < 0.0f) && j + 1 < n,
+                   e2 = !occ && !(d23.x < 0.0f) && j + 2 < n,
+                   e3 = !occ && !(d23.y < 0.0f) && j + 3 < n;
+        if (__ballot(e0 || e1 || e2 || e3)) {
+            if (e0) occ |= accepts_root(hb01.x, d01.x, a, T);
+            if (e1) occ |= accepts_root(hb01.y, d01.y, a, T);
+            if (e2) occ |= accepts_root(hb23.x, d23.x, a, T);
+            if (e3) occ |= accepts_root(hb23.y, d23.y, a, T);
+        }
+        g = nx;
+    }
+    tally(groups_tested, 2u * __builtin_amdgcn_readfirstlane(n_groups));  // half-groups
+    return occ;
+}
+
+}  // namespace
+
+// One scan per ray and no work counter: wave w of the grid takes rays 64 w + lane, then strides
+// by the grid's waves (coalesced loads of 3 + 3 + 1 dwords per ray, one byte stored per lane).
+// A wave takes the culled scan when the scene has tables and all its rays are in the guarded
+// range, else the linear scan: the same answer either way (fact (6)), so a ray's result does not
+// depend on the rays it shares a wave with. Lanes past the end of the batch hold a guarded ray,
+// start as occluded -- they never keep the wave in a loop -- and store nothing. No LDS.
+extern "C" __global__ __launch_bounds__(256) void vcrt_occlude_rays(OcclusionParams p_arg) {
+    // the arguments through a pointer to the kernarg segment, as trace_impl reads them
+    (void)p_arg;
+    const OcclusionParams& p = *reinterpret_cast<const OcclusionParams*>(
+        (__attribute__((address_space(4))) const OcclusionParams*)
+            __builtin_amdgcn_kernarg_segment_ptr());
+    const TraceParams& S = p.scene;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t count = p.count;
+    const uint32_t stride = gridDim.x * blockDim.x;  // a multiple of 64
+    const float4* tgroup = S.cgroup + 5 * S.nbig;    // the hierarchy's group records
+    uint32_t w_halves = 0u, w_bounds = 0u;
+    // count <= 2^30 and the stride is far below 2^30: the index does not wrap
+    for (uint32_t base = __builtin_amdgcn_readfirstlane(
+             (blockIdx.x * blockDim.x + threadIdx.x) & ~63u);
+         base < count; base += stride) {
+        const uint32_t idx = base + lane;
+        const bool live = idx < count;
+        f3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 1.f, 0.f);
+        float T = kInfinity;
+        if (live) {
+            const float* po = p.origins + 3u * (size_t)idx;
+            const float* pd = p.dirs + 3u * (size_t)idx;
+            o = mk(po[0], po[1], po[2]);
+            d = mk(pd[0], pd[1], pd[2]);
+            if (p.tmax) T = p.tmax[idx];
+        }
+        const float aa = dot(d, d);
+        const bool guarded = (S.flags & kFlagSceneBounded) != 0 && aa >= 0x1p-20f &&
+                             aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f && fabsf(o.y) <= 0x1p30f &&
+                             fabsf(o.z) <= 0x1p30f;
+        bool occ = !live;
+        if (S.ncgroups > 0 && __ballot(!guarded) == 0u)
+            occ = occlude_culled_lane(S, S.cbound, tgroup, o, d, T, occ, w_halves, w_bounds);
+        else
+            occ = occlude_linear(S, S.nspheres, o, d, T, occ, w_halves);
+        if (live) p.occluded[idx] = occ ? (uint8_t)1 : (uint8_t)0;
+    }
+    // one atomic per wave and tally
+    unsigned long long wh = w_halves, wb = w_bounds;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        wh += __shfl_xor(wh, off);
+        wb += __shfl_xor(wb, off);
+    }
+    if (lane == 0) {
+        atomicAdd(p.tallies + 0, wh / 2u);
+        atomicAdd(p.tallies + 1, wb);
     }
 }
 #endif

@@ -203,6 +203,21 @@ struct RayQueryParams {
                                   //   wave), boxes tested (per wave); zeroed before the launch
 };
 
+// Occlusion queries (vcrt_occlude_rays): does hit_sphere accept any sphere for a caller-supplied
+// ray with min_t = kMinT and the ray's own max_t? The scene block is filled as RayQueryParams'
+// is (the shading rows and max_depth are not read). No work counter: ray i belongs to wave
+// (i / 64) mod the grid's waves.
+struct OcclusionParams {
+    TraceParams scene;
+    const float* origins;  // [count][3]
+    const float* dirs;     // [count][3]
+    const float* tmax;     // [count] each ray's max_t, or null: kInfinity for every ray
+    uint8_t* occluded;     // [count] 0 or 1
+    uint32_t count;        // <= 2^30
+    unsigned long long* tallies;  // [2] groups of four put through the exact test (per wave),
+                                  //   boxes tested (per wave); zeroed before the launch
+};
+
 // TraceParams.jitter from the host's jitter (vcrt_math.h rand2) and the camera: run at
 // vcrt_begin and for each progressive frame.
 struct SetupJitterParams {

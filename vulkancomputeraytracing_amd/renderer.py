@@ -171,6 +171,43 @@ def _check_rays(origins, dirs):
     return origins, dirs
 
 
+def _check_reach(tmax, n: int, origins):
+    """Renderer.occluded's tmax for n rays held like `origins` (validated by _check_rays): None,
+    or float32 [n] where the rays are -- numpy C-contiguous, or a torch tensor on their device. A
+    scalar is broadcast (on the host, then copied: no torch kernel runs). Raises ValueError."""
+    if tmax is None:
+        return None
+    rays_torch = _is_torch(origins)
+    if _is_torch(tmax):
+        import torch
+        if not rays_torch:
+            raise ValueError("tmax: a torch tensor with numpy rays")
+        if tmax.dtype != torch.float32:
+            raise ValueError(f"tmax: torch tensors must be float32, not {tmax.dtype}")
+        if tmax.device != origins.device:
+            raise ValueError("tmax: must be on the rays' device")
+        if not tmax.is_contiguous():
+            raise ValueError("tmax: torch tensors must be contiguous")
+        if tmax.ndim != 1 or tmax.shape[0] != n:
+            raise ValueError(f"tmax: shape [{n}] expected, got {tuple(tmax.shape)}")
+        return tmax
+    try:
+        t = np.asarray(tmax, dtype=np.float32)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"tmax: not convertible to float32 ({e})") from None
+    if t.ndim == 0:
+        t = np.full(n, t, dtype=np.float32)
+    elif rays_torch:
+        raise ValueError("tmax: a scalar or a torch tensor with torch rays")
+    if t.ndim != 1 or t.shape[0] != n:
+        raise ValueError(f"tmax: shape [{n}] expected, got {tuple(t.shape)}")
+    t = np.ascontiguousarray(t)
+    if rays_torch:
+        import torch
+        return torch.from_numpy(t).to(origins.device)
+    return t
+
+
 # ---- reference-named lifecycle (VkResult codes, no exceptions) ----------------------------
 
 _desc = RenderDesc()
@@ -386,6 +423,65 @@ class Renderer:
                         "bound_tests": st.bound_tests, "kernel_ms": st.kernel_ms,
                         "kernel": st.kernel.decode() or "vcrt_trace_rays"})
         return out[0] if len(out) == 1 else tuple(out)
+
+    def occluded(self, origins, dirs, tmax=None, stats: bool = False):
+        """Is anything in the way within each ray's reach (vcrt_occlude_rays)? Shadow rays,
+        ambient occlusion, line of sight, probe visibility.
+
+        origins, dirs as for trace_rays (dirs are not normalised; t is in units of dirs). tmax is
+        the reach T: None (the reference's infinity, 1e5: the answer is then "trace_rays finds a
+        first hit"), a scalar for every ray, or float32 [n]; with torch rays a tensor tmax must be
+        float32, contiguous and on the rays' device. A ray is occluded when hit_sphere with
+        min_t = 0.001 and max_t = T accepts some sphere of the scene; T <= 0.001 never is, +inf
+        is allowed.
+
+        numpy inputs go through the host call and return a numpy bool_ [n]; torch tensors go
+        through the device call on their data_ptr(), after the caller's current stream is
+        synchronised, and return a torch bool [n] on the rays' device. With stats=True the result
+        is (occluded, stats dict). Shape and dtype errors raise ValueError before any native
+        call. The framebuffer and the frame statistics are left alone."""
+        origins, dirs = _check_rays(origins, dirs)
+        n = int(origins.shape[0])
+        tmax = _check_reach(tmax, n, origins)
+        st = N.vcrt_ray_stats()
+        if _is_torch(origins):
+            import torch
+            dev = origins.device
+            if self.desc.device >= 0 and dev.index != self.desc.device:
+                raise ValueError(f"rays on {dev}, the renderer on device {self.desc.device}")
+            lib = self._L()
+            occ = torch.empty((n,), dtype=torch.uint8, device=dev)
+            if n:
+                torch.cuda.current_stream(dev).synchronize()
+                N.check("vcrt_occlude_rays_device", lib.vcrt_occlude_rays_device(
+                    origins.data_ptr(), dirs.data_ptr(),
+                    None if tmax is None else tmax.data_ptr(), n, occ.data_ptr(),
+                    ctypes.byref(st)))
+            occ = occ.view(torch.bool)
+        else:
+            lib = self._L()
+            occ = np.empty(n, dtype=np.uint8)
+            if n:
+                N.check("vcrt_occlude_rays", lib.vcrt_occlude_rays(
+                    origins.ctypes.data, dirs.ctypes.data,
+                    None if tmax is None else tmax.ctypes.data, n, occ.ctypes.data,
+                    ctypes.byref(st)))
+            occ = occ.view(np.bool_)
+        if stats:
+            return occ, {"segments": st.segments, "group_tests": st.group_tests,
+                         "bound_tests": st.bound_tests, "kernel_ms": st.kernel_ms,
+                         "kernel": st.kernel.decode() or "vcrt_occlude_rays"}
+        return occ
+
+    def visible(self, a, b):
+        """Line of sight between the points a[i] and b[i] ([n, 3], numpy or torch as for
+        occluded): ~occluded(a, b - a, tmax=1.0), the subtraction in fp32.
+
+        min_t = 0.001 is in units of b - a: a segment ignores occluders in its first thousandth,
+        whatever its length, and an endpoint exactly on a surface may land on either side of
+        T = 1, so a point on a sphere may or may not see itself blocked by that sphere."""
+        a, b = _check_rays(a, b)
+        return ~self.occluded(a, b - a, tmax=1.0)
 
     def shader_load(self, path: str) -> None:
         N.check("vcrt_shader_load", self._L().vcrt_shader_load(path.encode()))
