@@ -209,7 +209,9 @@ def _same_bits_or_both_nan(got, want, what):
                                   "narrow_fov", "eye_on_target", "many_samples", "deep"])
 def test_edge_inputs_bitwise(oracle, case):
     """Inputs at the edge of the reference's arithmetic: a sphere too large for the culling
-    guard (the linear scan then), a NaN centre (never hit), a zero radius, fields of view of 170
+    guard (the linear scan then), a NaN centre (its NaN discriminant passes `disc < 0` and its
+    NaN root passes the range test, so in the reference's arithmetic it is hit by every ray:
+    tests/golden/reference_shader.npz, case mat_nancentre), a zero radius, fields of view of 170
     and 0.5 degrees, the camera on its target (normalize(0) gives a NaN basis; hit_sphere's
     `disc < 0` rejection lets a NaN ray through, so every segment "hits" and the path ends at
     the depth limit with the canonical black), 2^16 samples (quantum 128: 512 quanta per pixel)
