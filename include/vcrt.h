@@ -395,6 +395,19 @@ int32_t vcrt_cull_slab(const vcrt_sphere* spheres, int32_t count, float lohi[2])
 int32_t vcrt_cull_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t* tables,
                             float* params8, uint32_t* always);
 
+/* The group-level footprint tables of the LDS-table flat scan (host only, no GPU): tables =
+ * [4][N][4] uint32, 128-bit group masks (low word first; bit = hierarchy group index) by cell of
+ * x (lo <= cell, hi >= cell) and of z, params8 = {x scale, x offset, z scale, z offset, y lo,
+ * y hi, 2 Kmax, 0}, always4 = the groups every ray keeps. Returns N, the cells per table, chosen
+ * so that the tables fill the LDS bytes of the group boxes and node tables they replace (0: no
+ * tables: culling does not apply, more than 128 hierarchy groups or a degenerate extent).
+ * *eligible = 1 when a frame of this scene takes its groups from them in place of the node level:
+ * every group box with members has one y extent, bit for bit (whatever VCRT_SLAB says), and
+ * VCRT_GROUP_FOOT is not 0; a renderer further needs its camera-ray lists (VCRT_PRIMARY_LISTS).
+ * Any pointer may be NULL. */
+int32_t vcrt_cull_group_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t* tables,
+                                  float* params8, uint32_t* always4, int32_t* eligible);
+
 /* The flat culled scan's camera-ray lists for a scene and render description (host only, no
  * GPU; csrc/primary.cpp): for each 4x4-pixel quarter (qx, qy) of each local tile lt of
  * desc->rank (in the kernels' local-tile order), info[4 lt + 2 qy + qx] = offset << 4 | count

@@ -143,6 +143,8 @@ def phase(chain, mk):
             return "scan: big list"
         if "box_ray" in text or "recip_a" in text:
             return "scan: ray set-up (box ray)"
+        if "group_foot_mask" in text:
+            return "scan: group level (group footprint table lookups)"
         if "foot_mask" in text or "foot_cell" in text:
             return "scan: node level (footprint table lookups)"
         if "push_bound_pair_nf" in text or "near_far_addr" in text:

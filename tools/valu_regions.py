@@ -208,13 +208,30 @@ def main():
     p.add_argument("--kind", choices=("valu", "salu"), default="valu",
                    help="salu: scalar ALU and branch instructions (s_* but memory, waits, "
                         "nops), against SQ_INSTS_SALU given as --sq-valu")
+    p.add_argument("--scan", choices=("all", "slab", "axes", "groups"), default="all",
+                   help="the flat scan's instantiation the frame ran (wave-uniform flags: slab, "
+                        "three-axis, group footprint): instructions of the other instantiations "
+                        "are left out instead of being charged with the shared regions' counts")
     p.add_argument("--detail", action="append", default=[],
                    help="region name: also list its static VALU per innermost source line")
     a = p.parse_args()
     insts_r, label, chains = assign_regions(a.hsaco, a.product, a.kernel)
     static = collections.Counter()
     where = collections.defaultdict(collections.Counter)
+    def scan_kind(chain):
+        """slab / axes / groups of the scan_culled_flat instantiation in the chain, or None."""
+        for f, _, _ in chain:
+            m = re.search(r"scan_culled_flat<([^>]*?), \(anonymous|scan_culled_flat<([^>]*)>", f)
+            if m:
+                args = [t.strip() for t in (m.group(1) or m.group(2)).split(",")]
+                if len(args) > 6 and args[6] == "true":
+                    return "groups"
+                return "slab" if args[5] == "1" else "axes" if args[5] == "0" else "all"
+        return None
+
     for ad, mn, _, r in insts_r:
+        if a.scan != "all" and scan_kind(chains[ad]) not in (None, "all", a.scan):
+            continue
         if (V.is_valu(mn) if a.kind == "valu" else is_salu(mn)):
             static[r] += 1
             f, fl, ln = chains[ad][0]

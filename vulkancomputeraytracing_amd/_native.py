@@ -194,6 +194,9 @@ SIGNATURES = {
     "vcrt_cull_slab": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "vcrt_cull_footprint": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p]),
+    "vcrt_cull_group_footprint": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p]),
     "vcrt_primary_lists": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32,
                                             ctypes.POINTER(vcrt_render_desc), ctypes.c_void_p,
                                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),

@@ -132,6 +132,11 @@ struct RendererState {
     uint32_t* d_fp_tab = nullptr;
     float cfp_x[2] = {1, 0}, cfp_z[2] = {1, 0}, cfp_y[2] = {0, 0}, cfp_k2 = 0;
     uint32_t cfp_always = 0xffffffffu;
+    // the group-level footprint tables (CullTables::gf_*) and whether a frame may use them
+    uint4* d_gf_tab = nullptr;
+    float cgf_x[2] = {1, 0}, cgf_z[2] = {1, 0}, cgf_k2 = 0;
+    uint32_t cgf_n = 0, cgf_always[4] = {0, 0, 0, 0};
+    bool cgf_ok = false;
     uint32_t* d_prim_info = nullptr;  // camera-ray tile lists (primary.cpp), flat scan only
     uint16_t* d_prim_ids = nullptr;
     float4* d_cam_rec = nullptr;  // camera-relative records: big groups, sphere lists
@@ -434,6 +439,10 @@ void free_scene() {
     if (g.d_ctop) (void)hipFree(g.d_ctop);
     if (g.d_fp_tab) (void)hipFree(g.d_fp_tab);
     g.d_fp_tab = nullptr;
+    if (g.d_gf_tab) (void)hipFree(g.d_gf_tab);
+    g.d_gf_tab = nullptr;
+    g.cgf_ok = false;
+    g.cgf_n = 0;
     if (g.d_prim_info) (void)hipFree(g.d_prim_info);
     if (g.d_prim_ids) (void)hipFree(g.d_prim_ids);
     if (g.d_cam_rec) (void)hipFree(g.d_cam_rec);
@@ -1229,6 +1238,24 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
             g.cfp_k2 = ct.fp_k2;
             g.cfp_always = ct.fp_always;
         }
+        if (ct.gf_cells > 0) {
+            // group-level footprint tables (fact (5g)): in the LDS image they take the place of
+            // the group boxes and the node tables
+            static_assert(vcrt::kGroupFootMaxGroups ==
+                              static_cast<uint32_t>(vcrt::kGroupFootprintMaxGroups),
+                          "group footprint limit");
+            if (static_cast<uint32_t>(ct.gf_cells) != vcrt::group_foot_cells(ct.ngroups))
+                return VCRT_ERROR_INITIALIZATION_FAILED;
+            VCRT_TRY(hipMalloc(&g.d_gf_tab, sizeof(uint32_t) * ct.gf_tab.size()));
+            VCRT_TRY(hipMemcpy(g.d_gf_tab, ct.gf_tab.data(), sizeof(uint32_t) * ct.gf_tab.size(),
+                               hipMemcpyHostToDevice));
+            std::memcpy(g.cgf_x, ct.gf_x, sizeof(g.cgf_x));
+            std::memcpy(g.cgf_z, ct.gf_z, sizeof(g.cgf_z));
+            std::memcpy(g.cgf_always, ct.gf_always, sizeof(g.cgf_always));
+            g.cgf_k2 = ct.gf_k2;
+            g.cgf_n = static_cast<uint32_t>(ct.gf_cells);
+            g.cgf_ok = ct.gf_ok;
+        }
         if (g.primary_lists && g.local_tiles > 0) {
             // camera rays of a tile start from its quarter's lists (primary.cpp): the groups
             // for the main scan, the spheres for the camera fast trace; info interleaved
@@ -1401,6 +1428,14 @@ static void scene_params(vcrt::TraceParams& p) {
     }
     p.fp_k2 = g.cfp_k2;
     p.fp_always = g.cfp_always;
+    p.gf_tab = g.d_gf_tab;
+    for (int k = 0; k < 2; k++) {
+        p.gf_x[k] = g.cgf_x[k];
+        p.gf_z[k] = g.cgf_z[k];
+    }
+    p.gf_k2 = g.cgf_k2;
+    p.gf_n = g.cgf_n;
+    for (int k = 0; k < 4; k++) p.gf_always[k] = g.cgf_always[k];
     p.nspheres = g.nspheres;
     p.flags = (g.scene_bounded ? vcrt::kFlagSceneBounded : 0u) |
               (g.radii_safe ? vcrt::kFlagRadiiSafe : 0u) |
@@ -1443,6 +1478,11 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
               (g.pixel_scale ? vcrt::kFlagPixelScale : 0u) |
               (static_cast<uint32_t>(g.accum_log2 + vcrt::kFlagScaleBias)
                << vcrt::kFlagScaleShift);
+    // the group-level footprint (fact (5g)) takes the node level's place when the scene allows
+    // it (CullTables::gf_ok) and the camera rays have their lists: without them camera rays
+    // cross the scan on long grazing stretches, where a rectangle is loose
+    if (g.cgf_ok && g.d_gf_tab != nullptr && g.d_prim_info != nullptr)
+        p.flags |= vcrt::kFlagGroupFoot;
     // outlier quanta (vcrt_math.h "Accumulation"); the kernel's quantizing retire writes them
     p.pixel_emax = g.d_pixel_emax;
     p.outlier_max = static_cast<uint32_t*>(g.d_counters);  // u32 at 0 (zeroed every launch)
@@ -2270,6 +2310,23 @@ int32_t vcrt_cull_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t*
     }
     if (always) *always = ct.fp_always;
     return vcrt::kFootprintCells;
+}
+
+int32_t vcrt_cull_group_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t* tables,
+                                  float* params8, uint32_t* always4, int32_t* eligible) {
+    if (eligible) *eligible = 0;
+    if (count < 0 || (count > 0 && !spheres)) return 0;
+    vcrt::CullTables ct;
+    if (!vcrt::build_cull_tables(spheres, count, ct) || ct.gf_cells == 0) return 0;
+    if (tables) std::memcpy(tables, ct.gf_tab.data(), sizeof(uint32_t) * ct.gf_tab.size());
+    if (params8) {
+        const float v[8] = {ct.gf_x[0], ct.gf_x[1], ct.gf_z[0], ct.gf_z[1],
+                            ct.fp_y[0], ct.fp_y[1], ct.gf_k2,   0.0f};
+        std::memcpy(params8, v, sizeof(v));
+    }
+    if (always4) std::memcpy(always4, ct.gf_always, sizeof(ct.gf_always));
+    if (eligible) *eligible = ct.gf_ok ? 1 : 0;
+    return ct.gf_cells;
 }
 
 int32_t vcrt_cull_slab(const vcrt_sphere* spheres, int32_t count, float lohi[2]) {

@@ -110,7 +110,137 @@ void put_box(std::vector<float>& table, size_t i, const Box& b) {
     t[12 + e] = b.K;
 }
 
+// floats in order: key(x) rises with x (-inf .. +inf, -0 below +0)
+int64_t float_key(float x) {
+    uint32_t b;
+    std::memcpy(&b, &x, sizeof b);
+    return (b & 0x80000000u) ? static_cast<int64_t>(0x7fffffffu) - static_cast<int64_t>(b & 0x7fffffffu)
+                             : static_cast<int64_t>(0x80000000u) + static_cast<int64_t>(b);
+}
+
+float key_float(int64_t k) {
+    const uint32_t b = k >= static_cast<int64_t>(0x80000000u)
+                           ? static_cast<uint32_t>(k - static_cast<int64_t>(0x80000000u))
+                           : 0x80000000u | static_cast<uint32_t>(static_cast<int64_t>(0x7fffffffu) - k);
+    float x;
+    std::memcpy(&x, &b, sizeof x);
+    return x;
+}
+
+// The group-level footprint tables (cluster.hpp gf_*), by the node tables' rule over the group
+// boxes exactly as uploaded (out.bound): per cell i of n, with ue(i) the largest and le(i) the
+// smallest float of the cell by the kernel's own cell function and g = 8u |e| + 2^-100,
+//   A[i] = groups with lo <= ue(i) + g,   B[i] = groups with hi >= le(i) - g     (in double).
+void build_group_footprint(CullTables& out) {
+    const int32_t ng = out.ngroups;
+    const int n = group_footprint_cells(ng);
+    if (ng <= 0 || ng > kGroupFootprintMaxGroups || n < 2) return;
+    struct GBox {
+        float lo[3], hi[3], K;
+        int32_t index;
+    };
+    std::vector<GBox> gb;
+    for (int32_t gi = 0; gi < ng; gi++) {
+        bool members = false;
+        for (int k = 0; k < 4; k++) members |= out.index[(out.nbig + gi) * 4 + k] >= 0;
+        if (!members) continue;  // a padding group never gets a bit
+        const float* t = &out.bound[static_cast<size_t>(gi / 2) * 16];
+        const int e = gi % 2;
+        gb.push_back(GBox{{t[0 + e], t[2 + e], t[4 + e]}, {t[6 + e], t[8 + e], t[10 + e]},
+                          t[12 + e], gi});
+    }
+    if (gb.empty()) return;
+    out.gf_cells = n;
+    // one height: the same y extent in every group box with members, bit for bit (whatever
+    // VCRT_SLAB says: that only chooses how box tests are evaluated)
+    bool same = std::isfinite(gb[0].lo[1]) && std::isfinite(gb[0].hi[1]);
+    for (const GBox& b : gb)
+        same = same && std::memcmp(&b.lo[1], &gb[0].lo[1], sizeof(float)) == 0 &&
+               std::memcmp(&b.hi[1], &gb[0].hi[1], sizeof(float)) == 0;
+    out.gf_one_height = same;
+    const char* env = std::getenv("VCRT_GROUP_FOOT");
+    out.gf_ok = same && !(env && std::atoi(env) == 0);
+    // A scene the cells cannot describe (a degenerate extent, a coordinate bound below the 2^-20
+    // of the proof) keeps every group with members for every ray, as the node tables do.
+    auto keep_all = [&out, &gb, n]() {
+        uint32_t real[4] = {0, 0, 0, 0};
+        for (const GBox& b : gb) real[b.index >> 5] |= 1u << (b.index & 31);
+        out.gf_tab.resize(static_cast<size_t>(16) * n);
+        for (size_t i = 0; i < out.gf_tab.size(); i++) out.gf_tab[i] = real[i & 3];
+        std::memcpy(out.gf_always, real, sizeof(real));
+        out.gf_x[0] = out.gf_z[0] = 1.0f;
+        out.gf_x[1] = out.gf_z[1] = 0.0f;
+    };
+    if (!(out.margin[2] >= 0x1p-20f)) return keep_all();
+    double xlo[3], xhi[3];
+    for (int a = 0; a < 3; a++) {
+        xlo[a] = std::numeric_limits<double>::infinity();
+        xhi[a] = -xlo[a];
+        for (const GBox& b : gb) {
+            xlo[a] = std::min(xlo[a], static_cast<double>(b.lo[a]));
+            xhi[a] = std::max(xhi[a], static_cast<double>(b.hi[a]));
+        }
+    }
+    for (int a = 0; a < 3; a += 2) {
+        float* so = a == 0 ? out.gf_x : out.gf_z;
+        const double w = xhi[a] - xlo[a];
+        so[0] = static_cast<float>(n / w);
+        so[1] = static_cast<float>(-xlo[a] * static_cast<double>(so[0]));
+        if (!(w > 0.0 && std::isnormal(so[0]) && std::isfinite(so[1]))) return keep_all();
+    }
+    float kmax = 0.0f;
+    for (const GBox& b : gb) {
+        if (std::isinf(b.K))
+            out.gf_always[b.index >> 5] |= 1u << (b.index & 31);
+        else
+            kmax = std::max(kmax, b.K);
+    }
+    out.gf_k2 = round_up(2.0 * static_cast<double>(kmax));
+    out.gf_tab.assign(static_cast<size_t>(16) * n, 0u);
+    const double inf = std::numeric_limits<double>::infinity();
+    for (int a = 0; a < 3; a += 2) {
+        const float* so = a == 0 ? out.gf_x : out.gf_z;
+        uint32_t* A = &out.gf_tab[static_cast<size_t>(a == 0 ? 0 : 2) * n * 4];
+        uint32_t* B = A + static_cast<size_t>(n) * 4;
+        double prev_ue = -inf;  // the largest float of the cell before
+        for (int i = 0; i < n; i++) {
+            double ue = inf;
+            if (i < n - 1) {  // the largest float whose cell is <= i: the cell never falls as x rises
+                int64_t lo = float_key(-std::numeric_limits<float>::infinity());
+                int64_t hi = float_key(std::numeric_limits<float>::infinity());
+                while (hi - lo > 1) {  // cell(lo) <= i < cell(hi)
+                    const int64_t mid = lo + (hi - lo) / 2;
+                    (footprint_cell_n(key_float(mid), so, n) <= i ? lo : hi) = mid;
+                }
+                ue = key_float(lo);
+            }
+            // the smallest float of cell i is the one after prev_ue; comparing against prev_ue
+            // itself only widens the mask
+            const double le = prev_ue;
+            const double up = ue + (8.0 * kU * std::fabs(ue) + 0x1p-100);
+            const double dn = le - (8.0 * kU * std::fabs(le) + 0x1p-100);
+            for (const GBox& b : gb) {
+                if (static_cast<double>(b.lo[a]) <= up) A[4 * i + (b.index >> 5)] |= 1u << (b.index & 31);
+                if (static_cast<double>(b.hi[a]) >= dn) B[4 * i + (b.index >> 5)] |= 1u << (b.index & 31);
+            }
+            prev_ue = ue;
+        }
+    }
+}
+
 }  // namespace
+
+int group_footprint_cells(int32_t ngroups) {
+    if (ngroups <= 0) return 0;
+    const int node_tables = 4 * kFootprintCells * (ngroups > 128 ? 4 : 2);
+    return (ngroups / kNodeGroups * 336 + node_tables) / 64;
+}
+
+int footprint_cell_n(float x, const float so[2], int n) {
+    const float f = std::fmaf(x, so[0], so[1]);
+    const float c = std::fmin(std::fmax(f, 0.0f), static_cast<float>(n - 1));
+    return static_cast<int>(c);  // truncation, as v_cvt_u32_f32
+}
 
 bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
     out = CullTables{};
@@ -261,6 +391,8 @@ bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
     out.margin[1] = round_up(rmax * rmax * (1.0 + 1e-6));
     out.margin[2] = round_up(lam * (1.0 + 1e-6));
     out.margin[3] = 0.0f;
+
+    build_group_footprint(out);  // the group-level tables (fact (5g)), from out.bound
 
     // The footprint tables (cluster.hpp): the node boxes exactly as uploaded, compared in double
     // with the exact edges of the kernel's own cell function.

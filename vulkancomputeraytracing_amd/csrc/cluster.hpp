@@ -49,9 +49,32 @@ struct CullTables {
     float fp_y[2] = {0, 0};        // y extent of all those node boxes (= slab_lohi on a slab scene)
     float fp_k2 = 0;               // 2 x the largest finite K of those boxes, rounded up
     uint32_t fp_always = 0;        // nodes whose K is +inf: every ray keeps them
+    // The group-level footprint tables (tracer.hip fact (5g)): the same rule over the group boxes
+    // that have members, bit = hierarchy group index, masks of 128 bits (four words, low first);
+    // gf_cells cells per table (group_footprint_cells: the LDS bytes of the group boxes and node
+    // tables they replace). Built for every scene of at most 128 groups whose extent the cells
+    // can describe (else gf_cells = 0); gf_ok says whether a frame may use them in place of the
+    // node level: additionally every group box with members has one y extent, bit for bit (the
+    // geometric condition: it does not depend on VCRT_SLAB), and VCRT_GROUP_FOOT is not 0. The
+    // renderer further needs the camera-ray lists (capi.cpp).
+    std::vector<uint32_t> gf_tab;  // [4][gf_cells][4]
+    int32_t gf_cells = 0;
+    float gf_x[2] = {1, 0};        // scale, offset of the x cells
+    float gf_z[2] = {1, 0};
+    float gf_k2 = 0;               // 2 x the largest finite K of those boxes, rounded up
+    uint32_t gf_always[4] = {0, 0, 0, 0};  // groups whose K is +inf
+    bool gf_one_height = false;    // every group box with members has the y extent fp_y
+    bool gf_ok = false;
 };
 
 constexpr int kFootprintCells = 84;  // = vcrt::kFootCells (vcrt_kernel_abi.h)
+constexpr int kGroupFootprintMaxGroups = 128;  // = vcrt::kGroupFootMaxGroups
+
+// Cells per group-level table for a hierarchy of ngroups (= vcrt::group_foot_cells).
+int group_footprint_cells(int32_t ngroups);
+
+// The cell of coordinate x among n cells, as the kernel computes it.
+int footprint_cell_n(float x, const float scale_offset[2], int n);
 
 // The cell of coordinate x, as the kernel computes it.
 int footprint_cell(float x, const float scale_offset[2]);

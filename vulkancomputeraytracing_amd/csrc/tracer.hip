@@ -90,6 +90,8 @@ enum : uint32_t {
     kShGlassIn, kShGlassOut, kShGlassRefract, kShSky, kShEnded, kShNewRay, kShItemEnd,
     // sub-blocks of the flat scan's regions that run only on some of their entries
     kPrefixSlow = 72, kLevelTop, kPushNode, kPushGroup, kPushLevel, kListedTrip,
+    // the group-footprint level (fact (5g)): entries, push trips, slices of the rare sliced push
+    kLevelGroups, kPushGroups0, kPushGroups1, kPushGroups2, kPushGroups3, kSliceGroups, kPushSlice,
     kCount = 88
 };
 }  // namespace reg
@@ -328,6 +330,22 @@ __device__ __forceinline__ void scan_spheres(const TraceParams& p, const float4*
 //      inf - inf (t0, t1, cx finite), no 0 x inf (d'x != 0, scale > 0), and med3 clamps +-inf.
 //      The node pass then runs the exact line test (3) on each group box, so a node entered for
 //      nothing costs eight group-box tests and pushes what the line test lets through.
+//  (5g) the group footprint (the LDS-table flat scan with kFlagGroupFoot, group_foot_mask;
+//      cluster.hpp gf_tab). (5) word for word with the group boxes in place of the node boxes: if
+//      the box test of (3), (3a), (4) keeps group g for a ray (gap >= 0), bit g of the ray's
+//      128-bit mask is set. The cells, the cell function (over gf_n cells), ta, tb and the slack
+//      rule are (5)'s; S = RN(RN(2 c1) + (2 Kmax) c2) takes Kmax over the group boxes' own finite
+//      K (a larger S is only more conservative), groups with K = +inf are in `always`, padding
+//      groups never get a bit, and [Ylo, Yhi] is the one y extent that every group box with
+//      members has, bit for bit (the host's condition; it is fp_y, and the slab's on a slab
+//      scene), so t0, t1 are the box test's own y terms. By (2)-(4) a group whose box the test
+//      rules out holds no member that the exact test accepts, so the mask's groups include every
+//      group with such a member; a surplus group entry runs the exact four-sphere test for
+//      nothing and changes only the issued tests. The scan pushes the mask's groups straight onto
+//      the group stack: no node entry, no node pass, no box test (bound_tests counts none).
+//      The host sets the flag only for at most 128 hierarchy groups, one height, and a frame
+//      whose camera rays have their lists: those rays cross the scene on long grazing stretches,
+//      where the xz rectangle of the tables is much looser than the line test.
 //  (6) any hit (occlusion queries, occlude_culled_lane). The question "does hit_sphere accept
 //      some sphere with min_t and a fixed max_t = T" is an OR over the spheres, each term a
 //      function of that sphere and the ray alone (max_t never shrinks), so the visiting order and
@@ -1114,6 +1132,7 @@ struct PhaseTicks {
     uint64_t scan = 0, levels = 0, node = 0, group = 0, cand = 0, cand_passes = 0, big = 0,
              push = 0, shade = 0, fetch = 0;
     uint64_t pass_entries = 0, pass_lanes = 0, partial_passes = 0, passes = 0;
+    uint64_t group_entries = 0, node_entries = 0;  // entries the group / node passes took
     uint64_t cam = 0;  // the camera fast trace with its shading
     // camera fast trace occupancy: entries, camera lanes, live lanes, listed-loop trips and
     // lane sum, root-loop trips and lane sum; main shading hit lanes
@@ -1131,7 +1150,9 @@ struct FlatStacks {  // wave-uniform stack heights
     uint32_t cand, group, node, chunk;
 };
 
-template <bool kStats, int kFmt, bool kGRec, uint32_t kNS, int kSlab, class WS>
+// kGroupsOnly: the group-footprint scan (fact (5g)), whose node and chunk stacks stay empty.
+template <bool kStats, int kFmt, bool kGRec, uint32_t kNS, int kSlab, bool kGroupsOnly = false,
+          class WS>
 __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t rank, uint32_t lane,
                                            WS* ws, FlatStacks& h,
                                            const float4* tbound, const float4* tnode, uint32_t ncg,
@@ -1163,9 +1184,9 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
         int kind = -1;
         if (nc >= nact) kind = 0;
         else if (ng >= nact) kind = 1;
-        else if (nn >= nact) kind = 2;
-        else if (nk >= nact) kind = 3;
-        else if (th == 1u) kind = nk ? 3 : nn ? 2 : ng ? 1 : nc ? 0 : -1;
+        else if (!kGroupsOnly && nn >= nact) kind = 2;
+        else if (!kGroupsOnly && nk >= nact) kind = 3;
+        else if (th == 1u) kind = !kGroupsOnly && nk ? 3 : !kGroupsOnly && nn ? 2 : ng ? 1 : nc ? 0 : -1;
         if (kind == 0) {
             region(rrow, reg::kPassCand);
             flat_pass<0, kFmt, kGRec, kNS, kSlab>(nc, nc, nact, rank, lane, ws, tbound, tnode, ncg,
@@ -1177,17 +1198,21 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
         } else if (kind == 1) {
             region(rrow, reg::kPassGroup);
             ++n_groups;
+            if constexpr (kStats && kFmt == 0) pt.group_entries += min(ng, nact);
             flat_pass<1, kFmt, kGRec, kNS, kSlab>(ng, nc, nact, rank, lane, ws, tbound, tnode, ncg,
                                                   tg, my, slab, rrow);
             if constexpr (kStats) pt.group += ticks() - t0;
         } else if (kind == 2) {
+            if constexpr (!kGroupsOnly) {
             region(rrow, reg::kPassNode);
             n_bounds += 8;
+            if constexpr (kStats && kFmt == 0) pt.node_entries += min(nn, nact);
             flat_pass<2, kFmt, kGRec, kNS, kSlab>(nn, ng, nact, rank, lane, ws, tbound, tnode, ncg,
                                                   tg, my, slab, rrow);
             if constexpr (kStats) pt.node += ticks() - t0;
+            }
         } else if (kind == 3) {
-            if constexpr (WS::kHasChunks) {  // (nk stays 0 without the chunk stack)
+            if constexpr (WS::kHasChunks && !kGroupsOnly) {  // (nk stays 0 without the chunk stack)
                 region(rrow, reg::kPassChunk);
                 n_bounds += 8;
                 flat_pass<3, kFmt, kGRec, kNS, kSlab>(nk, nn, nact, rank, lane, ws, tbound,
@@ -1237,12 +1262,46 @@ __device__ __forceinline__ uint32_t foot_mask(const TraceParams& p, const BoxRay
     return (tb < ta ? 0u : m) | p.fp_always;
 }
 
+// The group mask of one ray from the group-level footprint tables (fact (5g)): foot_mask's cells,
+// ta, tb and S over the group boxes, 128-bit masks (bit g = hierarchy group g). gt: the four tables
+// of TraceParams.gf_n cells in LDS.
+__device__ __forceinline__ uint4 group_foot_mask(const TraceParams& p, const BoxRay& br, float t0,
+                                                 float t1, float ddx, float ddz,
+                                                 const float4* gt) {
+    const float S = __builtin_fmaf(p.gf_k2, br.c2.x, br.c1.x + br.c1.x);
+    const float ta = t0 - S, tb = t1 + S;  // t0, t1 finite; S finite or +inf
+    const float xa = (ta - br.cx.x) * ddx, xb = (tb - br.cx.x) * ddx;
+    const float za = (ta - br.cz.x) * ddz, zb = (tb - br.cz.x) * ddz;
+    const uint32_t n = p.gf_n;
+    const float last = (float)(n - 1u);
+    auto cell = [last](float x, const float so[2]) {
+        const float f = __builtin_fmaf(x, so[0], so[1]);
+        return (uint32_t)__builtin_amdgcn_fmed3f(f, 0.0f, last);
+    };
+    const uint32_t ixa = cell(xa, p.gf_x), ixb = cell(xb, p.gf_x);
+    const uint32_t iza = cell(za, p.gf_z), izb = cell(zb, p.gf_z);
+    const uint32_t x0 = min(ixa, ixb), x1 = max(ixa, ixb), z0 = min(iza, izb), z1 = max(iza, izb);
+    const uint4* t = reinterpret_cast<const uint4*>(gt);
+    const uint4 a = t[x1], b = t[n + x0], c = t[2u * n + z1], e = t[3u * n + z0];
+    const bool none = tb < ta;  // the ray never reaches the y extent: only `always`
+    uint4 m;
+    m.x = (none ? 0u : a.x & b.x & c.x & e.x) | p.gf_always[0];
+    m.y = (none ? 0u : a.y & b.y & c.y & e.y) | p.gf_always[1];
+    m.z = (none ? 0u : a.z & b.z & c.z & e.z) | p.gf_always[2];
+    m.w = (none ? 0u : a.w & b.w & c.w & e.w) | p.gf_always[3];
+    return m;
+}
+
 // kChunks: the chunk level as per-lane chunk passes over the near/far node boxes `tnode` (many
 // chunks: the stress scene), else each lane's node mask from the footprint tables in `tnode`'s
 // place (the LDS-table kernel: two chunks at the final scene).
 // kSlab: 1 = the boxes share their y extent (kFlagSlab), box tests by the ray's y interval (3a);
 // 0 = they do not; -1 = read the flag here and branch at each run of box tests.
-template <bool kStats, int kFmt, bool kGRec, bool kChunks, uint32_t kNS, int kSlab, class WS>
+// kGroupFoot (the LDS-table kernel with kFlagGroupFoot, fact (5g)): each lane's group mask from
+// the group-level tables in `tnode`'s place, pushed straight onto the group stack: no node level,
+// no box test (kSlab -1: the flag only says where the ray's y interval comes from).
+template <bool kStats, int kFmt, bool kGRec, bool kChunks, uint32_t kNS, int kSlab,
+          bool kGroupFoot = false, class WS>
 __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const float4* tbound,
                                                  const float4* tnode,
                                                  const GroupTab<kGRec>& tg, WS* ws,
@@ -1309,6 +1368,82 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
     uint32_t tops = 0;
     // (LDS-table kernel) the lane's node mask, once per segment: no box test at the levels
     uint32_t fmask = 0;
+    if constexpr (kGroupFoot) {
+        using F = FlatFmt<kFmt>;
+        using entry_t = typename F::entry_t;
+        region(rrow, reg::kLevelGroups);
+        uint64_t t0 = 0;
+        if constexpr (kStats) t0 = ticks();
+        float ty0 = br.iy.x, ty1 = br.cy.x;
+        if (!slab) {  // the y interval over the group boxes' one extent, by box_ray's operations
+            const float tly = __builtin_fmaf(p.fp_y[0], br.iy.x, br.cy.x);
+            const float thy = __builtin_fmaf(p.fp_y[1], br.iy.x, br.cy.x);
+            ty0 = fmaxf(fminf(tly, thy), 0.0f);
+            ty1 = fmaxf(tly, thy);
+        }
+        const float ddx = copysignf(fmaxf(fabsf(d.x), 0x1p-40f), d.x);  // d' of box_axis
+        const float ddz = copysignf(fmaxf(fabsf(d.z), 0x1p-40f), d.z);
+        uint4 gm = group_foot_mask(p, br, ty0, ty1, ddx, ddz, tnode);
+        if (listed) gm = make_uint4(0u, 0u, 0u, 0u);  // a listed camera ray has its groups
+        const uint32_t cnt = (uint32_t)(__popc(gm.x) + __popc(gm.y) + __popc(gm.z) + __popc(gm.w));
+        uint32_t tot;
+        const uint32_t pre = wave_prefix<8>(cnt, tot, rrow);
+        const uint32_t tag = lane << F::kShift;
+        // All lanes' groups in one step when the stack takes them (left over: the lists' entries);
+        // else, rarely, a node's worth (8 groups: at most 512 entries) at a time with full passes
+        // in between, which keeps the stack bound of the node passes (see kNodeCap): the first
+        // slice joins the lists' entries (a lane has a list or a mask: 8 each at most), every
+        // later one fewer than nact left over.
+        uint32_t slice = 16u;
+        if (h.group + tot <= (uint32_t)kGroupCap) {
+            uint32_t pos = h.group + pre;
+            h.group += tot;
+            // one loop per mask word, each with its own region (the stats build counts trips)
+            for (uint32_t bits = gm.x; bits; bits &= bits - 1) {
+                region(rrow, reg::kPushGroups0);
+                ws->group[pos++] = (entry_t)(tag | (uint32_t)__builtin_ctz(bits));
+            }
+            for (uint32_t bits = gm.y; bits; bits &= bits - 1) {
+                region(rrow, reg::kPushGroups1);
+                ws->group[pos++] = (entry_t)(tag | 32u | (uint32_t)__builtin_ctz(bits));
+            }
+            for (uint32_t bits = gm.z; bits; bits &= bits - 1) {
+                region(rrow, reg::kPushGroups2);
+                ws->group[pos++] = (entry_t)(tag | 64u | (uint32_t)__builtin_ctz(bits));
+            }
+            for (uint32_t bits = gm.w; bits; bits &= bits - 1) {
+                region(rrow, reg::kPushGroups3);
+                ws->group[pos++] = (entry_t)(tag | 96u | (uint32_t)__builtin_ctz(bits));
+            }
+        } else {
+            slice = 0u;
+        }
+        if constexpr (kStats) pt.push += ticks() - t0;
+        for (;;) {
+            uint32_t th = 1u;  // past the last slice: drain everything
+            if (slice < 16u) {
+                region(rrow, reg::kSliceGroups);
+                th = nact;
+                const uint32_t w = slice < 4u ? gm.x : slice < 8u ? gm.y : slice < 12u ? gm.z : gm.w;
+                uint32_t bits = (w >> (8u * (slice & 3u))) & 0xffu;
+                uint32_t stot;
+                uint32_t pos = h.group + wave_prefix<4>((uint32_t)__popc(bits), stot, rrow);
+                h.group += stot;
+                const uint32_t stag = tag | (8u * slice);
+                while (bits) {
+                    region(rrow, reg::kPushSlice);
+                    const uint32_t k = (uint32_t)__builtin_ctz(bits);
+                    bits &= bits - 1;
+                    ws->group[pos++] = (entry_t)(stag | k);
+                }
+                ++slice;
+            }
+            flat_drain<kStats, kFmt, kGRec, kNS, kSlab, true>(th, nact, rank, lane, ws, h, tbound,
+                                                              tnode, (uint32_t)ncg, tg, my,
+                                                              n_groups, n_bounds, pt, slab, rrow);
+            if (th == 1u) break;
+        }
+    } else {
     if constexpr (!kChunks) {
         float ty0 = br.iy.x, ty1 = br.cy.x;
         if (!slab) {  // the y interval over all node boxes, by box_ray's operations (3a)
@@ -1385,6 +1520,7 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
                                                     (uint32_t)ncg, tg, my, n_groups, n_bounds, pt,
                                                     slab, rrow);
         if (base >= ncg) break;
+    }
     }
     __builtin_amdgcn_wave_barrier();
     const unsigned long long k = ws->key[lane];
@@ -1672,12 +1808,20 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         const int nb = (P.ncgroups >> 3) * kNS, ng = P.ncgroups * 5;
         // and the node level's footprint tables (fact (5)) after the group records
         const int nf = (int)(foot_lds_bytes(P.ncgroups) >> 4);
-        {
+        // With kFlagGroupFoot (fact (5g)) the group-level tables, 4 x gf_n float4s, take the place
+        // of the boxes and the node tables (the host: 4 gf_n <= nb + nf), ahead of the records.
+        const bool gfoot = (P.flags & kFlagGroupFoot) != 0u;
+        const int rb = gfoot ? nb + nf : nb;  // where the group records start
+        if (gfoot) {
+            const float4* gt = reinterpret_cast<const float4*>(P.gf_tab);
+            const int nt = min(4 * (int)P.gf_n, nb + nf);
+            for (int i = threadIdx.x; i < nt; i += blockDim.x) lds_geom[i] = gt[i];
+        } else {
             uint32_t* ft = reinterpret_cast<uint32_t*>(lds_geom + nb + ng);
             for (int i = threadIdx.x; i < 4 * nf; i += blockDim.x) ft[i] = P.fp_tab[i];
+            for (int i = threadIdx.x; i < nb; i += blockDim.x)
+                if (i % kNS != 20u) lds_geom[i] = tbound[i - i / kNS];
         }
-        for (int i = threadIdx.x; i < nb; i += blockDim.x)
-            if (i % kNS != 20u) lds_geom[i] = tbound[i - i / kNS];
         for (int i = threadIdx.x; i < ng; i += blockDim.x) {
             float4 v = tgroup[i];
             if (i % 5 == 4) {  // member indices < 2^16 (<= 1024 groups), as uint16 (-1: 0xffff)
@@ -1687,12 +1831,13 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                                     ((uint32_t)__float_as_int(v.w) << 16);
                 v = make_float4(__uint_as_float(lo), __uint_as_float(hi), 0.0f, 0.0f);
             }
-            lds_geom[nb + i] = v;
+            lds_geom[rb + i] = v;
         }
         __syncthreads();
         tbound = lds_geom;
-        tg.geom = lds_geom + nb;
-        tnode = lds_geom + nb + ng;  // (this kernel: the footprint tables)
+        tg.geom = lds_geom + rb;
+        // (this kernel: the footprint tables, node level or group level)
+        tnode = gfoot ? lds_geom : lds_geom + nb + ng;
         ws = reinterpret_cast<WS*>(lds_geom + nb + ng + nf) + (threadIdx.x >> 6);
         static_assert(foot_lds_bytes(128) % 16u == 0u && foot_lds_bytes(256) % 16u == 0u,
                       "whole float4s");
@@ -2443,6 +2588,10 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                         scan_culled_flat<kStats, kFmt, kGRec, kChunks, kNS, -1>(
                             P, tbound, tnode, tg, ws, o, d, pass == 0, q & kQMask, max_t, best,
                             w_halves, w_bounds, pt, rrow);
+                    else if (kCull == 4 && (P.flags & kFlagGroupFoot) != 0u)
+                        scan_culled_flat<kStats, kFmt, kGRec, kChunks, kNS, -1, kCull == 4>(
+                            P, tbound, tnode, tg, ws, o, d, pass == 0, q & kQMask, max_t, best,
+                            w_halves, w_bounds, pt, rrow);
                     else if ((P.flags & kFlagSlab) != 0u)
                         scan_culled_flat<kStats, kFmt, kGRec, kChunks, kNS, 1>(
                             P, tbound, tnode, tg, ws, o, d, pass == 0, q & kQMask, max_t, best,
@@ -2584,6 +2733,10 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             atomicAdd(P.debug + 33, (unsigned long long)pt.fetch_iters);
             atomicAdd(P.debug + 34, (unsigned long long)pt.blk_fetches);
             atomicAdd(P.debug + 35, (unsigned long long)pt.items_cur);
+            if constexpr (kCull == 4) {  // entries of the LDS-table kernel's group / node passes
+                atomicAdd(P.debug + 36, (unsigned long long)pt.group_entries);
+                atomicAdd(P.debug + 37, (unsigned long long)pt.node_entries);
+            }
             atomicAdd(P.debug + 38, (unsigned long long)pt.retire_iters);
             atomicAdd(P.debug + 39, (unsigned long long)pt.quanta);
         }

@@ -141,6 +141,17 @@ struct TraceParams {
     float fp_x[2], fp_z[2], fp_y[2];
     float fp_k2;
     uint32_t fp_always;
+    // The group-level footprint tables (kFlagGroupFoot; cluster.hpp CullTables::gf_*; tracer.hip
+    // fact (5g)): four tables of gf_n 128-bit group masks (bit = hierarchy group index; x: lo <=
+    // cell, hi >= cell; z the same), which take the place of the group boxes and the node tables
+    // in the LDS-table kernel's image (group_foot_cells); gf_x / gf_z the cells' (scale, offset);
+    // gf_k2 twice the group boxes' largest finite K; gf_always the groups every ray keeps. The y
+    // extent is fp_y (one height: every group box has it). Last in the block, as the fields above.
+    const uint4* gf_tab;
+    float gf_x[2], gf_z[2];
+    float gf_k2;
+    uint32_t gf_n;
+    uint32_t gf_always[4];
 };
 
 constexpr uint32_t kQueueStride = 32;  // u32s between the work-queue counters (128 B)
@@ -166,6 +177,13 @@ constexpr uint32_t kFootCells = 84;  // cells per footprint table: 4 x 84 16-bit
 constexpr uint32_t foot_lds_bytes(int32_t ncgroups) {
     return 4u * kFootCells * (ncgroups > 128 ? 4u : 2u);
 }
+// cells per group-level footprint table (four tables of 16-B masks): what fits in the bytes of
+// the group boxes (336 B per node) and the node tables they replace, so that the LDS image keeps
+// its size; 94 at the final scene's 128 groups
+constexpr uint32_t kGroupFootMaxGroups = 128;
+constexpr uint32_t group_foot_cells(int32_t ncgroups) {
+    return (static_cast<uint32_t>(ncgroups) / 8u * 336u + foot_lds_bytes(ncgroups)) / 64u;
+}
 constexpr uint32_t kWaveScratchBytes = 4360;  // CULL_FLAT per-wave LDS stacks, 16-bit entries
 constexpr uint32_t kWaveScratchBytes8 = 3464;  // 16-bit candidates, no chunk stack (LDS tables)
 constexpr uint32_t kWaveScratchBytesWide = 6920;  // the same with 32-bit entries (global tables)
@@ -181,6 +199,9 @@ constexpr uint32_t kFlagPixelScale = 32u;  // per-pixel scales from TraceParams.
 constexpr uint32_t kFlagSlab = 64u;  // the boxes share their y extent, TraceParams.slab (a bit
                                      // of the flags word the scans hold anyway: no load, no
                                      // register of its own)
+constexpr uint32_t kFlagGroupFoot = 128u;  // the LDS-table flat scan takes each ray's groups from
+                                           // TraceParams.gf_* (no node level, no box test); the
+                                           // frame's camera rays have their lists
 constexpr uint32_t kFlagDirect = 4u;  // one work item per pixel and frame, not progressive: the
                                       // lane writes the pixel itself (no sums, no resolve pass)
 

@@ -125,6 +125,31 @@ def cull_footprint(spheres: np.ndarray) -> dict | None:
             "k2": par[6], "always": int(always.value)}
 
 
+def cull_group_footprint(spheres: np.ndarray) -> dict | None:
+    """The group-level footprint tables of `spheres` (host computation, no GPU), which take the
+    node level's place in the LDS-table flat scan on eligible scenes: ``tables`` [4, N, 4] uint32,
+    128-bit group masks, low word first (x: lo <= cell, hi >= cell; then z), ``n`` = N, ``x`` /
+    ``z`` the cells' (scale, offset), ``y`` the y extent of the boxes with members, ``k2`` twice
+    the group boxes' largest finite K, ``always`` [4] uint32 the groups every ray keeps, and
+    ``eligible``: at most 128 groups, one y extent in every group box with members (whatever
+    VCRT_SLAB says) and VCRT_GROUP_FOOT not 0. None without tables (no culling, more than 128
+    groups)."""
+    spheres = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+    lib = N.lib()
+    n = lib.vcrt_cull_group_footprint(spheres.ctypes.data, len(spheres), None, None, None, None)
+    if n == 0:
+        return None
+    tables = np.zeros((4, n, 4), np.uint32)
+    par = np.zeros(8, np.float32)
+    always = np.zeros(4, np.uint32)
+    eligible = ctypes.c_int32(0)
+    lib.vcrt_cull_group_footprint(spheres.ctypes.data, len(spheres), tables.ctypes.data,
+                                  par.ctypes.data, always.ctypes.data, ctypes.byref(eligible))
+    return {"tables": tables, "n": n, "x": par[0:2].copy(), "z": par[2:4].copy(),
+            "y": par[4:6].copy(), "k2": par[6], "always": always,
+            "eligible": bool(eligible.value)}
+
+
 def primary_lists(spheres: np.ndarray, desc) -> dict | None:
     """The flat scan's camera-ray lists (host computation, no GPU; csrc/primary.cpp) for
     `spheres` and a RenderDesc: ``info`` [4 x local tiles] uint32, entry 4 lt + 2 qy + qx for the
