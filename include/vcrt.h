@@ -20,7 +20,8 @@
  * Added (the reference has no equivalents): read-back of the rgba32f framebuffer, statistics,
  * rank/world tile sharding and the tile re-assembly used after a multi-GPU gather; ray queries
  * on rays the caller supplies (vcrt_trace_rays: radiance and first hit) and occlusion queries
- * (vcrt_occlude_rays: is anything in the way within a per-ray reach).
+ * (vcrt_occlude_rays: is anything in the way within a per-ray reach); a thin lens for the
+ * frames' camera (vcrt_render_desc.lens_radius, vcrt_lens_offsets).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -133,6 +134,31 @@ typedef struct vcrt_render_desc {
                                    equals a one-GPU render bit for bit. Work items hold whole
                                    quanta. At most 512 quanta per pixel (progressive frames
                                    included). */
+    float lens_radius; /* thin lens: the radius R of the camera's aperture disk in world units.
+                          0 (vcrt_default_desc) = the reference's pinhole, exactly as without the
+                          field: the same kernels, camera-ray lists and bits. R > 0: sample index i
+                          (absolute: progressive frame f covers f*spp .. (f+1)*spp-1) of every
+                          pixel starts at camera centre + offset_i, a point of the disk of radius R
+                          in the viewport's plane basis (vcrt_lens_offsets), and aims at the viewport
+                          point the pinhole's ray of (x, y, i) passes through:
+                            origin_i = center + offset_i
+                            dir      = (corner(x, y) + jitter_i) - origin_i
+                          each fp32 operation rounded on its own; the pixel is the same
+                          accumulation of ray_color(origin_i, dir, max_depth). The viewport lies
+                          in the plane through lookat (focal length = |lookfrom - lookat|,
+                          shader.comp:21,38), so that plane is in focus: focus by placing lookat on
+                          the view axis at the focus distance (there is no separate field).
+                          Negative, NaN or infinite: VCRT_ERROR_INITIALIZATION_FAILED.
+                          Appended after the first release of this struct: struct_size may be
+                          sizeof(vcrt_render_desc) or the size without this field (the field then
+                          reads 0). On LP64 targets the field takes the four bytes that padded the
+                          struct to its pointer's alignment, so the two sizes are both 112 and a
+                          caller built against the older header must have zeroed the whole struct
+                          (vcrt_default_desc does). With R > 0 the frame runs the *_lens kernels
+                          (vcrt_stats.kernel): AUTO, SMEM and CULL_FLAT; LDS, CULL, CULL_LANE,
+                          VCRT_DEBUG_STATS=1 or a code object without the lens kernels give
+                          VCRT_ERROR_FEATURE_NOT_PRESENT from vcrt_begin. vcrt_trace_rays and
+                          vcrt_occlude_rays take the caller's rays and ignore the lens. */
 } vcrt_render_desc;
 
 typedef struct vcrt_stats {
@@ -348,7 +374,9 @@ vcrt_result vcrt_occlude_rays_device(const float* origins, const float* dirs, co
 
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file
- * cannot be read or is not a gfx950 code object. Requires vcrt_begin. */
+ * cannot be read or is not a gfx950 code object. Requires vcrt_begin. A lens renderer
+ * (lens_radius > 0) gets VCRT_ERROR_FEATURE_NOT_PRESENT for a code object without the *_lens
+ * kernels (an A/B build of an older tree), and so do its draws until another one is loaded. */
 vcrt_result vcrt_shader_load(const char* filename);
 
 /* Built-in scenes. */
@@ -403,7 +431,8 @@ int32_t vcrt_cull_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t*
  * tables: culling does not apply, more than 128 hierarchy groups or a degenerate extent).
  * *eligible = 1 when a frame of this scene takes its groups from them in place of the node level:
  * every group box with members has one y extent, bit for bit (whatever VCRT_SLAB says), and
- * VCRT_GROUP_FOOT is not 0; a renderer further needs its camera-ray lists (VCRT_PRIMARY_LISTS).
+ * VCRT_GROUP_FOOT is not 0; a renderer further needs its camera-ray lists (VCRT_PRIMARY_LISTS;
+ * a lens renderer, lens_radius > 0, has none).
  * Any pointer may be NULL. */
 int32_t vcrt_cull_group_footprint(const vcrt_sphere* spheres, int32_t count, uint32_t* tables,
                                   float* params8, uint32_t* always4, int32_t* eligible);
@@ -412,7 +441,7 @@ int32_t vcrt_cull_group_footprint(const vcrt_sphere* spheres, int32_t count, uin
  * GPU; csrc/primary.cpp): for each 4x4-pixel quarter (qx, qy) of each local tile lt of
  * desc->rank (in the kernels' local-tile order), info[4 lt + 2 qy + qx] = offset << 4 | count
  * of its hierarchy groups in ids (count <= 8), or 15 when it has no list. Returns the number of
- * ids (-1: no culling tables, or an invalid desc), and writes info / ids when cap_tiles (entries
+ * ids (-1: no culling tables, an invalid desc, or lens_radius > 0: lens rays share no origin), and writes info / ids when cap_tiles (entries
  * of info) / cap_ids are large enough (pointers may be NULL). */
 int32_t vcrt_primary_lists(const vcrt_sphere* spheres, int32_t count, const vcrt_render_desc* desc,
                            uint32_t* info, int32_t cap_tiles, uint16_t* ids, int32_t cap_ids);
@@ -422,11 +451,24 @@ int32_t vcrt_primary_lists(const vcrt_sphere* spheres, int32_t count, const vcrt
  * pair records, 12 floats each: (ocx0,ocx1,ocy0,ocy1) (ocz0,ocz1,cc0,cc1) (index0, index1 as
  * int bits, 0, 0), camera-relative as the kernel's exact test computes them (oc = camera centre -
  * centre, cc = |oc|^2 - r^2 in fp32; an odd list pads with oc = 0, cc = 3e38, index -1). Returns
- * the number of pair records (-1: no culling tables, or an invalid desc), and writes info / rec
+ * the number of pair records (-1: no culling tables, an invalid desc, or lens_radius > 0: lens rays share no origin), and writes info / rec
  * when cap_tiles (entries) / cap_floats are large enough (pointers may be NULL). */
 int32_t vcrt_primary_sphere_lists(const vcrt_sphere* spheres, int32_t count,
                                   const vcrt_render_desc* desc, uint32_t* info, int32_t cap_tiles,
                                   float* rec, int32_t cap_floats);
+
+/* The thin lens's per-sample origin offsets for a render description (host only, no GPU):
+ * offsets[3 k .. 3 k + 2] = offset_i for sample index i = first + k, k < count, with R =
+ * desc->lens_radius, fi = (float)i and (camera_u, camera_v) shader.comp:28-29's unit basis
+ *   a   = rand(fi, fi + 0.5f)            b   = rand(fi + 0.5f, fi)        vcrt_canonical_rand
+ *   rho = R * sqrtf(a)                   phi = 6.2831855f * b             0x40C90FDB
+ *   lx  = rho * sin(phi + 1.5707964f)    ly  = rho * sin(phi)             vcrt_canonical_sin
+ *   offset_i = lx * camera_u + ly * camera_v                              (0x3FC90FDB)
+ * every fp32 operation rounded on its own; all +0 when R == 0. i and i + 0.5 are exact for every
+ * index a renderer admits (< 2^19). Returns count, or a negative VkResult for an invalid desc or
+ * a NULL offsets with count > 0. */
+int32_t vcrt_lens_offsets(const vcrt_render_desc* desc, uint32_t first, uint32_t count,
+                          float* offsets /* [count][3] */);
 
 /* Device self-test of the kernel's fast sin path (tracer.hip vcrt_check_sin): for the fp32
  * inputs whose bit patterns are first .. first + count - 1, counts those where the device's

@@ -79,6 +79,7 @@ class vcrt_render_desc(ctypes.Structure):
         ("accumulate_tail", ctypes.c_int32),
         ("accumulate_tail_chunk", ctypes.c_int32),
         ("accumulate_quantum", ctypes.c_int32),
+        ("lens_radius", ctypes.c_float),
     ]
 
 
@@ -204,6 +205,8 @@ SIGNATURES = {
                                                    ctypes.POINTER(vcrt_render_desc),
                                                    ctypes.c_void_p, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_int32]),
+    "vcrt_lens_offsets": (ctypes.c_int32, [ctypes.POINTER(vcrt_render_desc), ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.c_void_p]),
     "vcrt_canonical_sin": (ctypes.c_float, [ctypes.c_float]),
     "vcrt_canonical_rand": (ctypes.c_float, [ctypes.c_float, ctypes.c_float]),
     "vcrt_result_string": (ctypes.c_char_p, [ctypes.c_int32]),

@@ -69,6 +69,11 @@ struct RendererState {
     // through device buffers kept and grown between calls; the counters (the work index at 0,
     // three u64 tallies from 8) are the query's own, so a frame's are left alone.
     hipFunction_t k_trace_rays = nullptr;
+    // the thin-lens frame kernels (desc.lens_radius > 0; null: the code object predates them):
+    // the SMEM scan, then the three flat scans and their cost-order builds
+    hipFunction_t k_smem_lens = nullptr, k_flat_lens = nullptr, k_flat_lens_cost = nullptr,
+                  k_flat_global_lens = nullptr, k_flat_global_lens_cost = nullptr,
+                  k_flat_boxes_lens = nullptr, k_flat_boxes_lens_cost = nullptr;
     float* d_rq_rays = nullptr;  // [cap][6]: the origins, then the directions
     float4* d_rq_radiance = nullptr;
     uint4* d_rq_hits = nullptr;
@@ -162,6 +167,10 @@ struct RendererState {
     // each reused only once the copy recorded by its event is done (progressive frames set up
     // their jitter without waiting for the stream)
     float2* h_jitter[2] = {nullptr, nullptr};
+    // the lens origins of the same sample indices (desc.lens_radius > 0, else null), built on
+    // the host (vcrt_math.h lens_offset) in the same two turns and under the same events
+    float4* h_lens[2] = {nullptr, nullptr};
+    float4* d_lens = nullptr;  // TraceParams.lens
     hipEvent_t ev_jitter[2] = {nullptr, nullptr};
     int jitter_slot = 0;
     float* d_srgb_thresholds = nullptr;
@@ -550,6 +559,20 @@ VkResult bind_kernels() {
         (void)hipGetLastError();
         g.k_trace_rays = nullptr;
     }
+    // optional: the thin-lens frame kernels (a lens renderer answers the same without them)
+    const std::pair<hipFunction_t*, const char*> lens_kernels[] = {
+        {&g.k_smem_lens, "vcrt_trace_smem_lens"},
+        {&g.k_flat_lens, "vcrt_trace_cull_flat_lens"},
+        {&g.k_flat_lens_cost, "vcrt_trace_cull_flat_lens_cost"},
+        {&g.k_flat_global_lens, "vcrt_trace_cull_flat_global_lens"},
+        {&g.k_flat_global_lens_cost, "vcrt_trace_cull_flat_global_lens_cost"},
+        {&g.k_flat_boxes_lens, "vcrt_trace_cull_flat_boxes_lens"},
+        {&g.k_flat_boxes_lens_cost, "vcrt_trace_cull_flat_boxes_lens_cost"}};
+    for (const auto& [fp, name] : lens_kernels)
+        if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
+            (void)hipGetLastError();
+            *fp = nullptr;
+        }
     // optional: the occlusion-query kernel (vcrt_occlude_rays answers the same)
     if (hipModuleGetFunction(&g.k_occlude_rays, m, "vcrt_occlude_rays") != hipSuccess) {
         (void)hipGetLastError();
@@ -581,8 +604,35 @@ VkResult load_code_object(const char* path) {
     return bind_kernels();
 }
 
+// The caller's description as this library's struct. struct_size is sizeof(vcrt_render_desc), or
+// the size of the struct before lens_radius was appended (a binary built against that header):
+// the field then reads 0. (Where the field fits the struct's tail padding -- LP64 -- the two
+// sizes are equal and the field is read.)
+constexpr size_t kDescSizeNoLens = (offsetof(vcrt_render_desc, lens_radius) +
+                                    alignof(vcrt_render_desc) - 1) /
+                                   alignof(vcrt_render_desc) * alignof(vcrt_render_desc);
+bool read_desc(const vcrt_render_desc* in, vcrt_render_desc& out) {
+    if (!in) return false;
+    if (in->struct_size == sizeof(vcrt_render_desc)) {
+        out = *in;
+        return true;
+    }
+    if (in->struct_size != kDescSizeNoLens) return false;
+    out = vcrt_render_desc{};
+    std::memcpy(&out, in, offsetof(vcrt_render_desc, lens_radius));
+    out.struct_size = sizeof(vcrt_render_desc);
+    return true;
+}
+
+bool lens_on() { return g.desc.lens_radius > 0.0f; }
+bool lens_kernels_bound() {
+    return g.k_smem_lens && g.k_flat_lens && g.k_flat_lens_cost && g.k_flat_global_lens &&
+           g.k_flat_global_lens_cost && g.k_flat_boxes_lens && g.k_flat_boxes_lens_cost;
+}
+
 bool desc_valid(const vcrt_render_desc& d) {
     if (d.struct_size != sizeof(vcrt_render_desc)) return false;
+    if (!(d.lens_radius >= 0.0f) || std::isinf(d.lens_radius)) return false;  // (NaN: false)
     if (d.width <= 0 || d.height <= 0 || d.samples_per_pixel <= 0 || d.max_depth < 0)
         return false;
     if (static_cast<int64_t>(d.width) * d.height > (int64_t{1} << 31)) return false;
@@ -661,6 +711,16 @@ VkResult setup_jitter(uint64_t base, bool corners = false) {
     make_jitter(base, spp, g.h_jitter[slot]);
     VCRT_TRY(hipMemcpyAsync(g.d_jitter_in, g.h_jitter[slot], sizeof(float2) * spp,
                             hipMemcpyHostToDevice, g.stream));
+    if (g.d_lens) {  // the lens origins of the same sample indices: centre + offset_i
+        for (int k = 0; k < spp; k++) {
+            const vcrt::f3 o = vcrt::add(
+                g.cam.center, vcrt::lens_offset(static_cast<uint32_t>(base + k),
+                                                g.desc.lens_radius, g.cam.u, g.cam.v));
+            g.h_lens[slot][k] = make_float4(o.x, o.y, o.z, 0.0f);
+        }
+        VCRT_TRY(hipMemcpyAsync(g.d_lens, g.h_lens[slot], sizeof(float4) * spp,
+                                hipMemcpyHostToDevice, g.stream));
+    }
     VCRT_TRY(hipEventRecord(g.ev_jitter[slot], g.stream));
     vcrt::SetupJitterParams sp{};
     sp.jitter_in = g.d_jitter_in;
@@ -788,6 +848,9 @@ VkResult wait_gather() {
 // entry point, block size and dynamic LDS.
 struct KernelChoice {
     hipFunction_t f, stats;
+    // the pinhole kernel of the same kind: f itself, or for a lens renderer the kernel whose
+    // *_lens build f is (the rules of a draw ask what kind of kernel runs)
+    hipFunction_t base;
     // the build a cost-ordered frame launches (it counts pixel segments into
     // TraceParams.pixel_cost and follows TraceParams.block_order); null: no cost order
     hipFunction_t cost;
@@ -900,7 +963,31 @@ KernelChoice select_kernel() {
                        : f == g.k_trace_cull_flat_global ? g.k_trace_cull_flat_global_cost
                        : f == g.k_trace_cull_flat_boxes  ? g.k_trace_cull_flat_boxes_cost
                                                          : nullptr;
-    return KernelChoice{f, fs, fc, fname, block, lds, variant};
+    const hipFunction_t base = f;
+    if (lens_on()) {
+        // the thin lens: the *_lens build of the same kernel (vcrt_begin admits AUTO, SMEM and
+        // CULL_FLAT only, and no stats builds); null when the code object has none
+        fs = nullptr;
+        if (f == g.k_trace_smem) {
+            f = fc = g.k_smem_lens;
+            fname = "vcrt_trace_smem_lens";
+        } else if (f == g.k_trace_cull_flat) {
+            f = g.k_flat_lens;
+            fc = g.k_flat_lens_cost;
+            fname = "vcrt_trace_cull_flat_lens";
+        } else if (f == g.k_trace_cull_flat_boxes) {
+            f = g.k_flat_boxes_lens;
+            fc = g.k_flat_boxes_lens_cost;
+            fname = "vcrt_trace_cull_flat_boxes_lens";
+        } else if (f == g.k_trace_cull_flat_global) {
+            f = g.k_flat_global_lens;
+            fc = g.k_flat_global_lens_cost;
+            fname = "vcrt_trace_cull_flat_global_lens";
+        } else {
+            f = fc = nullptr;
+        }
+    }
+    return KernelChoice{f, fs, base, fc, fname, block, lds, variant};
 }
 
 }  // namespace
@@ -927,18 +1014,22 @@ vcrt_result vcrt_default_desc(vcrt_render_desc* d) {
 }
 
 int32_t vcrt_work_chunk(const vcrt_render_desc* desc) {
-    if (!desc || !desc_valid(*desc)) return VCRT_ERROR_INITIALIZATION_FAILED;
-    return work_chunk(*desc);
+    vcrt_render_desc d;
+    if (!read_desc(desc, d) || !desc_valid(d)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    return work_chunk(d);
 }
 
 int32_t vcrt_work_quantum(const vcrt_render_desc* desc) {
-    if (!desc || !desc_valid(*desc)) return VCRT_ERROR_INITIALIZATION_FAILED;
-    return work_quantum(*desc);
+    vcrt_render_desc d;
+    if (!read_desc(desc, d) || !desc_valid(d)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    return work_quantum(d);
 }
 
 int32_t vcrt_work_tail(const vcrt_render_desc* desc, int32_t* tail_chunk) {
-    if (!desc || !desc_valid(*desc) || !tail_chunk) return VCRT_ERROR_INITIALIZATION_FAILED;
-    return work_tail(*desc, work_chunk(*desc), tail_chunk);
+    vcrt_render_desc d;
+    if (!read_desc(desc, d) || !desc_valid(d) || !tail_chunk)
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    return work_tail(d, work_chunk(d), tail_chunk);
 }
 
 int32_t vcrt_pixel_scale_log2(float max_abs_quantum_sum) {
@@ -949,10 +1040,18 @@ int32_t vcrt_pixel_scale_log2(float max_abs_quantum_sum) {
 }
 
 vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
-    if (!desc || !desc_valid(*desc)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    vcrt_render_desc dv;
+    if (!read_desc(desc, dv) || !desc_valid(dv)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (dv.lens_radius > 0.0f) {
+        // the thin lens has builds of the SMEM and flat scans only, and no stats builds
+        const char* ds = std::getenv("VCRT_DEBUG_STATS");
+        if (dv.kernel_variant == VCRT_KERNEL_LDS || dv.kernel_variant == VCRT_KERNEL_CULL ||
+            dv.kernel_variant == VCRT_KERNEL_CULL_LANE || (ds && std::atoi(ds) == 1))
+            return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    }
     if (g.begun) vcrt_end();
     g = RendererState{};
-    g.desc = *desc;
+    g.desc = dv;
     g.begun = true;  // from here on vcrt_end() cleans up whatever was created
 
     int count = 0;
@@ -987,6 +1086,7 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
     if ((r = to_vk(hipEventCreate(&g.ev_resolve))) != VK_SUCCESS) return fail(r);
     if ((r = load_code_object(g.desc.code_object_path)) != VK_SUCCESS) return fail(r);
     g.desc.code_object_path = nullptr;  // not owned
+    if (lens_on() && !lens_kernels_bound()) return fail(VCRT_ERROR_FEATURE_NOT_PRESENT);
 
     // Camera (shader.comp:18-39): uniform per dispatch, computed once here.
     const vcrt_camera& c = g.desc.camera;
@@ -1006,6 +1106,12 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
             return fail(r);
     }
     if ((r = to_vk(hipMalloc(&g.d_jitter, sizeof(float4) * spp))) != VK_SUCCESS) return fail(r);
+    if (lens_on()) {  // the lens origins, a table like the jitter's
+        for (int k = 0; k < 2; k++)
+            if ((r = to_vk(hipHostMalloc(&g.h_lens[k], sizeof(float4) * spp))) != VK_SUCCESS)
+                return fail(r);
+        if ((r = to_vk(hipMalloc(&g.d_lens, sizeof(float4) * spp))) != VK_SUCCESS) return fail(r);
+    }
     {
         float th[255];
         srgb_thresholds(th);
@@ -1256,7 +1362,9 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
             g.cgf_n = static_cast<uint32_t>(ct.gf_cells);
             g.cgf_ok = ct.gf_ok;
         }
-        if (g.primary_lists && g.local_tiles > 0) {
+        // (not for a lens: its camera rays do not share an origin, so they have no lists, no
+        // camera-relative records and, for want of the lists, no group-level footprint)
+        if (g.primary_lists && g.local_tiles > 0 && !lens_on()) {
             // camera rays of a tile start from its quarter's lists (primary.cpp): the groups
             // for the main scan, the spheres for the camera fast trace; info interleaved
             vcrt::PrimaryLists pl;
@@ -1448,6 +1556,7 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     vcrt::TraceParams p{};
     scene_params(p);
     p.jitter = g.d_jitter;
+    p.lens = g.d_lens;
     p.corner = g.d_corner;
     p.out = g.d_fb;
     p.accum = g.d_accum;
@@ -1496,11 +1605,12 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     for (int i = 0; i < 12; i++) p.cam[i] = cam[i];
     const KernelChoice kc = select_kernel();
     hipFunction_t f = g.debug_stats == 1 ? kc.stats : kc.f;
+    if (f == nullptr) return VK_ERROR_FEATURE_NOT_PRESENT;  // (a lens, no lens kernels loaded)
     // Deferred fetches (tracer.hip, the flat scans): the LDS-table flat scan waits until 4 lanes
     // need an item (at most one iteration): C3 -0.6 % kernel time (its 16 items per pixel make
     // the fetch frequent), C4 and the 8-way shards within 0.1 %, same bits; the global-table and
     // boxes-in-LDS scans fetch at once (C5 +0.6 % with it). profiles/r06_ab_log.md.
-    const bool lds_flat = kc.f == g.k_trace_cull_flat;
+    const bool lds_flat = kc.base == g.k_trace_cull_flat;
     p.fetch_min = g.fetch_min > 0u ? g.fetch_min : (lds_flat ? 4u : 1u);
     p.fetch_wait = g.fetch_min > 0u ? g.fetch_wait : (lds_flat ? 1u : 0u);
     const uint32_t block = kc.block;
@@ -1509,10 +1619,12 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     // (TraceParams.stage_*): C2 (4 spheres, 64 spp) is latency-bound on those reads
     p.stage_spheres = 0u;
     p.stage_spp = 0u;
-    if (kc.f == g.k_trace_smem && g.nspheres > 0 && g.stage_tables) {
-        // in 64 bits: 16 * spp wraps 32 bits for spp >= 2^28
+    if (kc.base == g.k_trace_smem && g.nspheres > 0 && g.stage_tables) {
+        // in 64 bits: 16 * spp wraps 32 bits for spp >= 2^28; a lens renderer
+        // stages its origins after the jitter (16 B more per sample)
         const uint64_t bytes = 48ull * static_cast<uint64_t>(g.nspheres) +
-                               16ull * static_cast<uint64_t>(g.desc.samples_per_pixel);
+                               (lens_on() ? 32ull : 16ull) *
+                                   static_cast<uint64_t>(g.desc.samples_per_pixel);
         if (bytes <= kStageMaxBytes) {
             p.stage_spheres = static_cast<uint32_t>(g.nspheres);
             p.stage_spp = static_cast<uint32_t>(g.desc.samples_per_pixel);
@@ -1707,9 +1819,9 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     g.stats.block_threads = static_cast<int32_t>(block);
     g.stats.kernel_variant = variant;
     g.stats.lds_bytes = lds;  // tables and stacks; the ring adds ring_entries x 32 B per wave
-    g.stats.tables_in_lds = kc.f == g.k_trace_cull_flat_boxes ? 2 :
-                            (kc.f == g.k_trace_cull_flat || kc.f == g.k_trace_cull_lane_lds ||
-                             kc.f == g.k_trace_cull_lane_lds_wide) ? 1 : 0;
+    g.stats.tables_in_lds = kc.base == g.k_trace_cull_flat_boxes ? 2 :
+                            (kc.base == g.k_trace_cull_flat || kc.base == g.k_trace_cull_lane_lds ||
+                             kc.base == g.k_trace_cull_lane_lds_wide) ? 1 : 0;
     *outlier_max = static_cast<uint32_t>(counters[0]);
     return VK_SUCCESS;
 }
@@ -1820,8 +1932,10 @@ vcrt_result vcrt_end(void) {
     if (g.d_jitter_in) (void)hipFree(g.d_jitter_in);
     for (int k = 0; k < 2; k++) {
         if (g.h_jitter[k]) (void)hipHostFree(g.h_jitter[k]);
+        if (g.h_lens[k]) (void)hipHostFree(g.h_lens[k]);
         if (g.ev_jitter[k]) (void)hipEventDestroy(g.ev_jitter[k]);
     }
+    if (g.d_lens) (void)hipFree(g.d_lens);
     if (g.d_corner) (void)hipFree(g.d_corner);
     if (g.d_fb_own) (void)hipFree(g.d_fb_own);
     if (g.d_counters) (void)hipFree(g.d_counters);
@@ -2256,6 +2370,8 @@ vcrt_result vcrt_shader_load(const char* filename) {
     (void)hipStreamSynchronize(g.stream);
     const VkResult r = load_code_object(filename);
     if (r == VK_SUCCESS && g.d_geom) g.stage.pName = select_kernel().name;
+    // a lens renderer cannot draw with a code object that has no lens kernels
+    if (r == VK_SUCCESS && lens_on() && !lens_kernels_bound()) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     return r;
 }
 
@@ -2339,16 +2455,24 @@ int32_t vcrt_cull_slab(const vcrt_sphere* spheres, int32_t count, float lohi[2])
 
 namespace {
 // Culling tables and the kernels' camera array for a desc (host only).
-bool host_camera_tables(const vcrt_sphere* spheres, int32_t count, const vcrt_render_desc* desc,
+vcrt::Camera desc_camera(const vcrt_render_desc& d) {
+    const vcrt_camera& c = d.camera;
+    return vcrt::make_camera(d.width, d.height,
+                             vcrt::mk(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]),
+                             vcrt::mk(c.lookat[0], c.lookat[1], c.lookat[2]),
+                             vcrt::mk(c.vup[0], c.vup[1], c.vup[2]), c.vfov,
+                             [](double x) { return std::tan(x); });
+}
+
+// (a lens desc has no camera-ray lists: its rays do not share an origin)
+bool host_camera_tables(const vcrt_sphere* spheres, int32_t count, const vcrt_render_desc* desc_in,
                         vcrt::CullTables& ct, float cam[12]) {
-    if (!desc || !desc_valid(*desc) || count < 0 || (count > 0 && !spheres)) return false;
+    vcrt_render_desc dv;
+    if (!read_desc(desc_in, dv) || !desc_valid(dv) || count < 0 || (count > 0 && !spheres))
+        return false;
+    if (dv.lens_radius > 0.0f) return false;
     if (!vcrt::build_cull_tables(spheres, count, ct)) return false;
-    const vcrt_camera& c = desc->camera;
-    const vcrt::Camera cm = vcrt::make_camera(desc->width, desc->height,
-                                              vcrt::mk(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]),
-                                              vcrt::mk(c.lookat[0], c.lookat[1], c.lookat[2]),
-                                              vcrt::mk(c.vup[0], c.vup[1], c.vup[2]), c.vfov,
-                                              [](double x) { return std::tan(x); });
+    const vcrt::Camera cm = desc_camera(dv);
     const vcrt::f3 v[4] = {cm.pixel00, cm.delta_u, cm.delta_v, cm.center};
     for (int i = 0; i < 4; i++) {
         cam[3 * i + 0] = v[i].x;
@@ -2388,6 +2512,26 @@ int32_t vcrt_primary_sphere_lists(const vcrt_sphere* spheres, int32_t count,
     if (rec && cap_floats >= static_cast<int32_t>(sl.rec.size()))
         std::memcpy(rec, sl.rec.data(), sizeof(float) * sl.rec.size());
     return static_cast<int32_t>(sl.rec.size() / 12);
+}
+
+int32_t vcrt_lens_offsets(const vcrt_render_desc* desc, uint32_t first, uint32_t count,
+                          float* offsets) {
+    vcrt_render_desc d;
+    if (!read_desc(desc, d) || !desc_valid(d) || (count > 0 && !offsets) ||
+        count > static_cast<uint32_t>(INT32_MAX))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    const vcrt::Camera cm = desc_camera(d);
+    for (uint32_t k = 0; k < count; k++) {
+        // R == 0: the pinhole, +0 (the products of a zero radius would carry the sines' signs)
+        const vcrt::f3 o = d.lens_radius > 0.0f
+                               ? vcrt::lens_offset(first + k, d.lens_radius, cm.u, cm.v)
+                               : vcrt::mk(0.0f, 0.0f, 0.0f);
+        float* out = offsets + 3 * static_cast<size_t>(k);
+        out[0] = o.x;
+        out[1] = o.y;
+        out[2] = o.z;
+    }
+    return static_cast<int32_t>(count);
 }
 
 float vcrt_canonical_sin(float x) { return vcrt::sin_canonical(x); }

@@ -1720,6 +1720,15 @@ __device__ __forceinline__ float4 jitter_at(const TraceParams& p, const float4* 
     return p.jitter[i];
 }
 
+// The lens origin of sample i (TraceParams.lens; the *_lens kernels), staged after the jitter.
+template <bool kStageable>
+__device__ __forceinline__ float4 lens_at(const TraceParams& p, const float4* lds, int i) {
+    if constexpr (kStageable) {
+        if (p.stage_spp != 0u) return lds[3u * p.stage_spheres + p.stage_spp + (uint32_t)i];
+    }
+    return p.lens[i];
+}
+
 template <bool kStageable>
 __device__ __forceinline__ void shading_rows(const TraceParams& p, const float4* lds, int best,
                                              float4& cr, float4& sh, float4& mat) {
@@ -1739,7 +1748,10 @@ __device__ __forceinline__ void shading_rows(const TraceParams& p, const float4*
 
 // kCull: 0 = linear scan (kLds: table in LDS), 1 = culled scan, 2 = per-lane culled scan
 // with the group tables copied to LDS, 3 = per-lane culled scan on global tables.
-template <bool kLds, bool kStats, int kCull = 0, bool kCostOrder = false>
+// kLens: the thin lens (vcrt.h lens_radius > 0): a camera ray starts at its sample's lens origin
+// (TraceParams.lens) instead of the camera centre; the host then passes no camera-ray lists, so
+// the scans treat a camera ray as any other ray.
+template <bool kLds, bool kStats, int kCull = 0, bool kCostOrder = false, bool kLens = false>
 __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds_dyn) {
     // P: the kernel arguments, read through a pointer to the kernarg segment (the kernels' only
     // argument) that the persistent loop makes opaque at the top of every iteration (below), so
@@ -1771,6 +1783,10 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             }
             for (uint32_t i = threadIdx.x; i < P.stage_spp; i += blockDim.x)
                 lds_dyn[3u * ns + i] = P.jitter[i];
+            if constexpr (kLens) {
+                for (uint32_t i = threadIdx.x; i < P.stage_spp; i += blockDim.x)
+                    lds_dyn[3u * ns + P.stage_spp + i] = P.lens[i];
+            }
             __syncthreads();
         }
     }
@@ -1898,7 +1914,13 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             c = viewport_corner(p00, du, dv, pxy & 0xffffu, pxy >> 16);
         }
         const float4 j = jitter_at<kStageable>(P, lds_dyn, s);
-        return sub(add(c, mk(j.x, j.y, j.z)), cam);
+        if constexpr (kLens) {  // (corner + jitter) - origin_s; the ray's origin set here
+            const float4 l = lens_at<kStageable>(P, lds_dyn, s);
+            o = mk(l.x, l.y, l.z);
+            return sub(add(c, mk(j.x, j.y, j.z)), o);
+        } else {
+            return sub(add(c, mk(j.x, j.y, j.z)), cam);
+        }
     };
     uint32_t segs = 0;  // this lane's segments (< 2^32: ~2.4e5 per lane at the C5 workload)
     uint64_t st_iters = 0, st_active = 0, st_hitgroups = 0, st_fetch = 0;
@@ -2052,7 +2074,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                 } else {
                     region(rrow, rb + reg::kShNewRay);
                     d = camera_dir(sample);
-                    o = cam;
+                    if constexpr (!kLens) o = cam;
                     atten = mk(1.f, 1.f, 1.f);
                     pass = 0;
                     fresh_cam = true;
@@ -2155,7 +2177,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             region(rrow, reg::kNewRay);
             newray = false;
             d = camera_dir(sample);
-            o = cam;
+            if constexpr (!kLens) o = cam;
             atten = mk(1.f, 1.f, 1.f);
             pass = 0;
             fresh = true;
@@ -2424,7 +2446,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
 #endif
             // first camera ray of the chunk, shader.comp:48-52
             d = camera_dir(sample);
-            o = cam;
+            if constexpr (!kLens) o = cam;
             atten = mk(1.f, 1.f, 1.f);
             pass = 0;
             fresh = true;
@@ -2448,13 +2470,17 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             uint64_t t_cam = 0;
             if constexpr (kStats) t_cam = ticks();
             uint32_t inf = 15u;
-            if (fresh && P.prim_info != nullptr)  // the sphere list of the item's 4x4 quarter
-                inf = P.prim_info[2u * (((q & kQMask) >> 6) * 4u + (((q >> 5) & 1u) << 1) +
-                                        ((q >> 2) & 1u)) +
-                                  1u];
+            // (kLens: the rays do not share an origin, so no lists and no fast trace)
+            if constexpr (!kLens) {
+                if (fresh && P.prim_info != nullptr)  // the sphere list of the item's 4x4 quarter
+                    inf = P.prim_info[2u * (((q & kQMask) >> 6) * 4u + (((q >> 5) & 1u) << 1) +
+                                            ((q >> 2) & 1u)) +
+                                      1u];
+            }
             const float aa = dot(d, d);
-            const bool cam_now = fresh && (inf & 15u) != 15u && (P.flags & kFlagSceneBounded) != 0 &&
-                                 aa >= 0x1p-20f && aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f &&
+            const bool cam_now = !kLens && fresh && (inf & 15u) != 15u &&
+                                 (P.flags & kFlagSceneBounded) != 0 && aa >= 0x1p-20f &&
+                                 aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f &&
                                  fabsf(o.y) <= 0x1p30f && fabsf(o.z) <= 0x1p30f;
             float mt = __uint_as_float(vconst<0x47c35000u>());  // kInfinity
             int bst = (int)vconst<0xffffffffu>();                // -1
@@ -3491,5 +3517,53 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_occlude_rays(OcclusionPar
         atomicAdd(p.tallies + 0, wh / 2u);
         atomicAdd(p.tallies + 1, wb);
     }
+}
+#endif
+
+// ---- thin-lens frames (vcrt.h lens_radius > 0) ----------------------------------------------
+// Part 5, a unit of its own with the default scheduler: the frame kernels a lens renderer
+// launches, trace_impl with kLens. The linear SMEM scan has its cost-order hooks built in; the
+// flat scans come as the product build and the cost-order build, with the launch bounds and
+// wave targets of their pinhole kernels. There are no lens stats builds.
+#if !defined(VCRT_PART) || VCRT_PART == 5
+extern "C" __global__ __launch_bounds__(256) void vcrt_trace_smem_lens(TraceParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_dyn[];
+    trace_impl<false, false, 0, false, true>(p, lds_dyn);
+}
+
+extern "C" __global__ __launch_bounds__(VCRT_FLAT_BLOCK)
+__attribute__((amdgpu_waves_per_eu(VCRT_FLAT_WAVES))) void vcrt_trace_cull_flat_lens(TraceParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tab[];
+    trace_impl<false, false, 4, false, true>(p, lds_tab);
+}
+
+extern "C" __global__ __launch_bounds__(VCRT_FLAT_BLOCK)
+__attribute__((amdgpu_waves_per_eu(VCRT_FLAT_WAVES))) void vcrt_trace_cull_flat_lens_cost(TraceParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tab[];
+    trace_impl<false, false, 4, true, true>(p, lds_tab);
+}
+
+// The global-table scan at five waves per SIMD spills two VGPRs to scratch (as its pinhole build
+// does); the lens builds are compiled for four and keep everything in registers.
+extern "C" __global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(VCRT_FLAT_WAVES - 1))) void vcrt_trace_cull_flat_global_lens(TraceParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tab[];
+    trace_impl<false, false, 5, false, true>(p, lds_tab);
+}
+
+extern "C" __global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(VCRT_FLAT_WAVES - 1))) void vcrt_trace_cull_flat_global_lens_cost(TraceParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tab[];
+    trace_impl<false, false, 5, true, true>(p, lds_tab);
+}
+
+extern "C" __global__ __launch_bounds__(1024) void vcrt_trace_cull_flat_boxes_lens(TraceParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tab[];
+    trace_impl<false, false, 6, false, true>(p, lds_tab);
+}
+
+extern "C" __global__ __launch_bounds__(1024) void vcrt_trace_cull_flat_boxes_lens_cost(TraceParams p) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_tab[];
+    trace_impl<false, false, 6, true, true>(p, lds_tab);
 }
 #endif

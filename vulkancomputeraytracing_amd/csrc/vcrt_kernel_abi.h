@@ -152,6 +152,11 @@ struct TraceParams {
     float gf_k2;
     uint32_t gf_n;
     uint32_t gf_always[4];
+    // The thin lens (vcrt.h lens_radius > 0; the *_lens kernels only): [spp] the ray origin of
+    // each sample index of the frame, camera centre + lens offset (vcrt_math.h lens_offset, built
+    // on the host with the same fp32 operations), w = 0; indexed as jitter is. Null for the
+    // pinhole, whose kernels do not read it. Last in the block, as the fields above.
+    const float4* lens;
 };
 
 constexpr uint32_t kQueueStride = 32;  // u32s between the work-queue counters (128 B)

@@ -468,6 +468,7 @@ VCRT_HD float resolve_channel(double s, double inv_scale, double spp_total) {
 struct Camera {
     f3 pixel00, delta_u, delta_v, center;
     float focal_length, viewport_height, viewport_width;
+    f3 u, v;  // shader.comp:28-29's unit basis of the viewport plane (the thin lens's disk)
 };
 
 inline Camera make_camera(int width, int height, f3 lookfrom, f3 lookat, f3 vup, float vfov,
@@ -489,7 +490,30 @@ inline Camera make_camera(int width, int height, f3 lookfrom, f3 lookat, f3 vup,
     f3 ul = sub(sub(sub(c.center, scale(c.focal_length, w)), divs(viewport_u, 2.0f)),
                 divs(viewport_v, 2.0f));
     c.pixel00 = add(ul, scale(0.5f, add(c.delta_u, c.delta_v)));
+    c.u = u;
+    c.v = v;
     return c;
 }
+
+// ---------------------------------------------------------------------------------------
+// Thin lens (vcrt.h lens_radius; the reference has a pinhole only). The viewport lies in the
+// plane through lookat (focal_length = |lookfrom - lookat|), so that plane is in focus and a lens
+// only moves each sample's ray origin: sample index i starts at center + lens_offset(i, R, u, v),
+// a point of the disk of radius R spanned by the camera's unit basis, and aims at the same
+// viewport point as the pinhole's ray. Like the jitter the offset depends on the sample index
+// alone; its two rand() arguments are half-integers (exact for i < 2^19), off the jitter's
+// diagonal rand(i, i). One fixed sequence of fp32 operations (host only: the table
+// TraceParams.lens is built here).
+constexpr float kLensTwoPi = 6.2831855f;   // 0x40C90FDB
+constexpr float kLensHalfPi = 1.5707964f;  // 0x3FC90FDB: cos(phi) as sin(phi + pi/2)
+#if !defined(__HIP_DEVICE_COMPILE__)
+inline f3 lens_offset(uint32_t i, float radius, f3 u, f3 v) {
+    const float fi = static_cast<float>(i);
+    const float a = rand2(fi, fi + 0.5f), b = rand2(fi + 0.5f, fi);
+    const float rho = radius * __builtin_sqrtf(a), phi = kLensTwoPi * b;
+    const float lx = rho * sin_canonical(phi + kLensHalfPi), ly = rho * sin_canonical(phi);
+    return add(scale(lx, u), scale(ly, v));
+}
+#endif
 
 }  // namespace vcrt

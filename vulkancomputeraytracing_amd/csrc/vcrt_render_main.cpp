@@ -17,7 +17,7 @@ int usage() {
     std::fprintf(stderr,
                  "usage: vcrt_render [--width W] [--height H] [--spp N] [--depth D] "
                  "[--scene final|three|red|stress4096] [--frames F] [--progressive 0|1] [--device I] "
-                 "[--out file.ppm|file.pfm]\n");
+                 "[--lens-radius R] [--out file.ppm|file.pfm]\n");
     return 2;
 }
 
@@ -41,6 +41,7 @@ int main(int argc, char** argv) {
         else if (a == "--frames") frames = std::atoi(v);
         else if (a == "--device") desc.device = std::atoi(v);
         else if (a == "--progressive") desc.progressive = std::atoi(v);
+        else if (a == "--lens-radius") desc.lens_radius = std::strtof(v, nullptr);  // thin lens
         else if (a == "--out") out = v;
         else if (a == "--scene") {
             const std::string s = v;

@@ -39,6 +39,8 @@ class RenderDesc:
     accumulate_tail_chunk: int = 0  # samples per tail item; 0 = the rule
     accumulate_quantum: int = 0     # accumulation quantum G (the image depends on it alone):
                                     # 0 = the rule (work_quantum); >= spp: sequential order
+    lens_radius: float = 0.0        # thin lens: aperture radius in world units (0 = the pinhole);
+                                    # the plane through lookat is in focus (vcrt.h)
     _path_keepalive: bytes | None = field(default=None, repr=False)
 
     def to_c(self) -> N.vcrt_render_desc:
@@ -59,6 +61,7 @@ class RenderDesc:
         d.accumulate_tail = self.accumulate_tail
         d.accumulate_tail_chunk = self.accumulate_tail_chunk
         d.accumulate_quantum = self.accumulate_quantum
+        d.lens_radius = float(self.lens_radius)
         if self.code_object_path:
             self._path_keepalive = self.code_object_path.encode()
             d.code_object_path = self._path_keepalive
@@ -86,6 +89,16 @@ def work_tail(desc: RenderDesc) -> tuple[int, int]:
     t = N.check_count("vcrt_work_tail", N.lib().vcrt_work_tail(ctypes.byref(desc.to_c()),
                                                                 ctypes.byref(kt)))
     return (t, kt.value) if t > 0 else (0, 0)
+
+
+def lens_offsets(desc: RenderDesc, first: int, count: int) -> np.ndarray:
+    """float32 [count, 3]: the thin lens's origin offsets of sample indices first .. first+count-1
+    for `desc` (vcrt_lens_offsets: host only, no GPU); all +0 for the pinhole (lens_radius 0)."""
+    out = np.zeros((int(count), 3), np.float32)
+    N.check_count("vcrt_lens_offsets",
+                  N.lib().vcrt_lens_offsets(ctypes.byref(desc.to_c()), int(first), int(count),
+                                            out.ctypes.data_as(ctypes.c_void_p)))
+    return out
 
 
 def pixel_scale_log2(max_abs_quantum_sum: float) -> int:
