@@ -192,11 +192,13 @@ typedef struct vcrt_stats {
                            trace entries, its lanes, live lanes, listed-group loop trips and
                            lane sum, root loop trips and lane sum; main-scan hit lanes;
                            [32..39] flat scans: wave ticks in the retire, wave-iterations
-                           running the fetch loop, block fetches, items started, next items
-                           handed out, item switches in the shading, wave-iterations running
-                           the retire, quanta retired (lanes); [40..111] region counters:
-                           wave-level entries into the tracer's counted regions (tracer.hip
-                           reg::*, in order), summed over the waves */
+                           running the fetch loop, block fetches, items started, [36] [37] the
+                           entries the LDS-table kernel's group passes and node passes took
+                           (vcrt_trace_cull_flat_stats; 0 from the other kernels),
+                           wave-iterations running the retire, quanta retired (lanes);
+                           [40..127] region counters: wave-level entries into the tracer's
+                           counted regions (tracer.hip reg::*, by enum value), summed over
+                           the waves */
     int32_t accumulate_tail;       /* tail samples per pixel in effect (0: none) */
     int32_t accumulate_tail_chunk; /* samples per tail item in effect */
     int32_t ring_entries;          /* LDS accumulation ring entries per wave (0: none; the chunk

@@ -30,6 +30,7 @@ if len(d) > 39 and d[33]:
     print("loop top: retire %.1f%% of wave time (%.1f ticks per wave-iter), run in %.2f of "
           "wave-iters, %.2f quanta per wave-iter" % (100 * d[32] / tot, d[32] / wi, d[38] / wi,
                                                      d[39] / wi))
-    print("fetch loop in %.2f of wave-iters; blocks %.4f, items started %.3f, next items %.3f, "
-          "switches %.3f per wave-iter" % (d[33] / wi, d[34] / wi, d[35] / wi, d[36] / wi,
-                                           d[37] / wi))
+    # d[36], d[37]: the LDS-table kernel's group / node passes (0 from the other kernels)
+    print("fetch loop in %.2f of wave-iters; blocks %.4f, items started %.3f, group-pass entries "
+          "%.3f, node-pass entries %.3f per wave-iter" % (d[33] / wi, d[34] / wi, d[35] / wi,
+                                                          d[36] / wi, d[37] / wi))

@@ -1146,6 +1146,25 @@ struct PhaseTicks {
 
 __device__ __forceinline__ uint64_t ticks() { return __builtin_amdgcn_s_memtime(); }
 
+// Stats builds: the per-wave counters (PhaseTicks, trace_impl's st_*) are per lane under SIMT, as
+// tally says of the product's -- a lane that is idle when the wave counts keeps its old value,
+// and a lane that is done idles through everything after the loop's `if (done) continue` -- so a
+// wave-uniform amount x is credited to the wave's first active lane and trace_impl sums each
+// counter over the lanes (wave_sum) before lane 0 adds it to TraceParams.debug. (Reading lane
+// 0's own count lost every entry made while lane 0 had no item: the camera trace's and the
+// scan's counters of a wave's last items.)
+__device__ __forceinline__ void credit(uint64_t& c, uint64_t x) {
+    const uint32_t first = (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec());
+    c += (threadIdx.x & 63u) == first ? x : 0u;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(uint64_t c) {  // every lane active
+    unsigned long long v = c;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 struct FlatStacks {  // wave-uniform stack heights
     uint32_t cand, group, node, chunk;
 };
@@ -1170,10 +1189,10 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
                              : nk >= nact ? nk
                              : th == 1u ? (nk ? nk : nn ? nn : ng ? ng : nc) : 0u;
             if (n) {
-                pt.pass_entries += min(n, nact);
-                pt.pass_lanes += nact;
-                pt.partial_passes += n < nact;
-                ++pt.passes;
+                credit(pt.pass_entries, min(n, nact));
+                credit(pt.pass_lanes, nact);
+                credit(pt.partial_passes, n < nact);
+                credit(pt.passes, 1u);
             }
         }
         // full passes first, deepest stack first; then (final drain only) the partial passes
@@ -1192,24 +1211,24 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
             flat_pass<0, kFmt, kGRec, kNS, kSlab>(nc, nc, nact, rank, lane, ws, tbound, tnode, ncg,
                                                   tg, my, slab, rrow);
             if constexpr (kStats) {
-                pt.cand += ticks() - t0;
-                ++pt.cand_passes;
+                credit(pt.cand, ticks() - t0);
+                credit(pt.cand_passes, 1u);
             }
         } else if (kind == 1) {
             region(rrow, reg::kPassGroup);
             ++n_groups;
-            if constexpr (kStats && kFmt == 0) pt.group_entries += min(ng, nact);
+            if constexpr (kStats && kFmt == 0) credit(pt.group_entries, min(ng, nact));
             flat_pass<1, kFmt, kGRec, kNS, kSlab>(ng, nc, nact, rank, lane, ws, tbound, tnode, ncg,
                                                   tg, my, slab, rrow);
-            if constexpr (kStats) pt.group += ticks() - t0;
+            if constexpr (kStats) credit(pt.group, ticks() - t0);
         } else if (kind == 2) {
             if constexpr (!kGroupsOnly) {
             region(rrow, reg::kPassNode);
             n_bounds += 8;
-            if constexpr (kStats && kFmt == 0) pt.node_entries += min(nn, nact);
+            if constexpr (kStats && kFmt == 0) credit(pt.node_entries, min(nn, nact));
             flat_pass<2, kFmt, kGRec, kNS, kSlab>(nn, ng, nact, rank, lane, ws, tbound, tnode, ncg,
                                                   tg, my, slab, rrow);
-            if constexpr (kStats) pt.node += ticks() - t0;
+            if constexpr (kStats) credit(pt.node, ticks() - t0);
             }
         } else if (kind == 3) {
             if constexpr (WS::kHasChunks && !kGroupsOnly) {  // (nk stays 0 without the chunk stack)
@@ -1217,7 +1236,7 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
                 n_bounds += 8;
                 flat_pass<3, kFmt, kGRec, kNS, kSlab>(nk, nn, nact, rank, lane, ws, tbound,
                                                        tnode, ncg, tg, my, slab, rrow);
-                if constexpr (kStats) pt.levels += ticks() - t0;
+                if constexpr (kStats) credit(pt.levels, ticks() - t0);
             }
         } else {
             break;
@@ -1337,7 +1356,7 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
             exact_group_uniform((cfloat4*)p.cgroup + 5 * gb, r, dx, dy, dz, a2, my.a, my.ya, max_t,
                                 best, rrow, reg::kMainBig);
     }
-    if constexpr (kStats) pt.big += ticks() - t_in;
+    if constexpr (kStats) credit(pt.big, ticks() - t_in);
     uint32_t n_bounds = 0, n_groups = (uint32_t)p.nbig;
     const uint32_t lane = threadIdx.x & 63u;
     // finished lanes are masked off for the whole scan: entries go to the live lanes by rank
@@ -1418,7 +1437,7 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
         } else {
             slice = 0u;
         }
-        if constexpr (kStats) pt.push += ticks() - t0;
+        if constexpr (kStats) credit(pt.push, ticks() - t0);
         for (;;) {
             uint32_t th = 1u;  // past the last slice: drain everything
             if (slice < 16u) {
@@ -1492,13 +1511,13 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
                 ws->chunk[h.chunk + lanes_below(want)] = (typename FlatFmt<kFmt>::entry_t)(
                     (lane << FlatFmt<kFmt>::kShift) | ((uint32_t)base >> 6));
             h.chunk += (uint32_t)__popcll(want);
-            if constexpr (kStats) pt.push += ticks() - t0;
+            if constexpr (kStats) credit(pt.push, ticks() - t0);
             } else {
             // level 1 (LDS tables: two chunks at the final scene): the mask's nodes of this chunk
             // -> node entries (no box test issued: nothing counted)
             if constexpr (kStats) {
                 const uint64_t t1 = ticks();
-                pt.levels += t1 - t0;
+                credit(pt.levels, t1 - t0);
                 t0 = t1;
             }
             uint32_t tot;
@@ -1513,7 +1532,7 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
                     ws->node[pos++] = (typename FlatFmt<kFmt>::entry_t)(tag | j);
                 } while (nodes);
             }
-            if constexpr (kStats) pt.push += ticks() - t0;
+            if constexpr (kStats) credit(pt.push, ticks() - t0);
             }
         }
         flat_drain<kStats, kFmt, kGRec, kNS, kSlab>(th, nact, rank, lane, ws, h, tbound, tnode,
@@ -1624,10 +1643,9 @@ __device__ __forceinline__ void scan_culled_lane(const TraceParams& p, const flo
                     consider(candidate_t(hb, ds, a), idx, max_t, best);
                 }
             }
-            if constexpr (kStats) {  // wave passes of the candidate loop = max over lanes
-                for (int off = 32; off > 0; off >>= 1)
-                    cand = max(cand, (uint32_t)__shfl_xor((int)cand, off));
-                rounds += cand;
+            if constexpr (kStats) {  // wave passes of the candidate loop = max over the active
+                                     // lanes (<= 4 members; by ballots: idle lanes are inactive)
+                rounds += wave_max_small<3>(cand);
             }
         }
     }
@@ -2099,8 +2117,8 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         if constexpr (kStats) {
             t_top = ticks();
             const uint64_t fm = __ballot(fin);
-            pt.retire_iters += fm != 0u;
-            pt.quanta += (uint64_t)__popcll(fm);
+            credit(pt.retire_iters, fm != 0u);
+            credit(pt.quanta, (uint64_t)__popcll(fm));
         }
         if (fin) {  // ---- retire the finished quantum: its sum to the pixel ----
             region(rrow, reg::kRetire);
@@ -2187,7 +2205,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         uint64_t t_fetch = 0;
         if constexpr (kStats) {
             t_fetch = ticks();
-            pt.retire += t_fetch - t_top;
+            credit(pt.retire, t_fetch - t_top);
         }
         // The loop only hands out slots; the lane state is set up once after it (setting it up
         // inside made the compiler copy ~20 live registers around the loop on every pass).
@@ -2209,11 +2227,11 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                 }
             }
         }
-        if constexpr (kStats) pt.fetch_iters += need_mask != 0u;
+        if constexpr (kStats) credit(pt.fetch_iters, need_mask != 0u);
         while (need_mask) {
             region(rrow, reg::kFetchTrip);
             if (blk_next >= 64u) {
-                if constexpr (kStats && kCull == 0) ++st_fetch;
+                if constexpr (kStats && kCull == 0) credit(st_fetch, 1u);
                 // kQueues queues, each on workgroups of one XCD (workgroups are dispatched to
                 // the XCDs round robin): queue x hands out blocks kQueues k + x on its own
                 // counter; a wave whose queue is drained moves on to the next open one, and is
@@ -2273,7 +2291,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                     if (need) done = true;
                     break;
                 }
-                if constexpr (kStats) ++pt.blk_fetches;
+                if constexpr (kStats) credit(pt.blk_fetches, 1u);
                 region(rrow, reg::kBlock);
                 // block b = (local tile lt, chunk) of the head, then of the tail: wave-uniform
                 // tile origin and sample range; reversed within each part
@@ -2413,7 +2431,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             }
         }
 #endif
-        if constexpr (kStats) pt.items_cur += (uint64_t)__popcll(__ballot(got));
+        if constexpr (kStats) credit(pt.items_cur, (uint64_t)__popcll(__ballot(got)));
         if (got) {
             region(rrow, reg::kItem);
             q = (g_lt * 64u + g_slot) | (g_ent << kRingQBits);
@@ -2451,12 +2469,12 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             pass = 0;
             fresh = true;
         }
-        if constexpr (kStats) pt.fetch += ticks() - t_fetch;
+        if constexpr (kStats) credit(pt.fetch, ticks() - t_fetch);
         const uint64_t live = __ballot(!done);
         if (live == 0) break;
         if constexpr (kStats) {
-            ++st_iters;
-            st_active += (uint64_t)__popcll(live);
+            credit(st_iters, 1u);
+            credit(st_active, (uint64_t)__popcll(live));
         }
         if (done) continue;
 
@@ -2487,9 +2505,9 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             if (__ballot(cam_now)) {
                 region(rrow, reg::kCam);
                 if constexpr (kStats) {
-                    ++pt.cam_entries;
-                    pt.cam_lanes += (uint64_t)__popcll(__ballot(cam_now));
-                    pt.cam_live += (uint64_t)__popcll(__ballot(1));
+                    credit(pt.cam_entries, 1u);
+                    credit(pt.cam_lanes, (uint64_t)__popcll(__ballot(cam_now)));
+                    credit(pt.cam_live, (uint64_t)__popcll(__ballot(1)));
                 }
                 uint32_t iters = 0, roots = 0;
                 if (cam_now) {
@@ -2542,17 +2560,14 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                     }
                 }
                 if constexpr (kStats) {
-                    uint32_t tl = iters, tr = roots, ml = iters, mr = roots;
-                    for (int off = 32; off > 0; off >>= 1) {
-                        tl += (uint32_t)__shfl_xor((int)tl, off);
-                        tr += (uint32_t)__shfl_xor((int)tr, off);
-                        mr = max(mr, (uint32_t)__shfl_xor((int)mr, off));
-                        ml = max(ml, (uint32_t)__shfl_xor((int)ml, off));
-                    }
-                    pt.list_sum += tl;
-                    pt.root_sum += tr;
-                    pt.list_trips += ml;
-                    pt.root_trips += mr;
+                    // done lanes are inactive here, so no xor butterfly (a partial result that
+                    // passes through an inactive lane is lost): each lane adds its own trips to
+                    // its own counter, which wave_sum totals after the loop, and the maxima
+                    // come from ballots (a listed quarter has <= 14 spheres: <= 7 pairs)
+                    pt.list_sum += iters;
+                    pt.root_sum += roots;
+                    credit(pt.list_trips, wave_max_small<3>(iters));
+                    credit(pt.root_trips, wave_max_small<4>(roots));
                 }
                 // issued work: the big list and the loop's passes (a pair test is half a group
                 // test), per wave
@@ -2575,8 +2590,8 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             }
             if constexpr (kStats) {
                 const uint64_t t1 = ticks();
-                pt.cam += t1 - t_cam;
-                st_fetch += t1 - t_cs;  // flat stats: debug[3] = the camera phase's shading
+                credit(pt.cam, t1 - t_cam);
+                credit(st_fetch, t1 - t_cs);  // flat stats: debug[3] = the camera phase's shading
             }
             if (need) continue;  // that segment finished the lane's chunk
         }
@@ -2630,11 +2645,11 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                 else
                     scan_culled_lane<kStats>(P, tbound, tgroup, o, d, max_t, best, w_halves,
                                              w_bounds, lane_cnt, hit_groups);
-                if constexpr (kStats) pt.scan += ticks() - t0;
+                if constexpr (kStats) credit(pt.scan, ticks() - t0);
                 if constexpr (kStats) {  // CULL stats: debug[3] = sum of per-wave max lane need
-                    for (int off = 32; off > 0; off >>= 1)
-                        lane_cnt = max(lane_cnt, (uint32_t)__shfl_xor((int)lane_cnt, off));
-                    if constexpr (!kFlat) st_fetch += lane_cnt;
+                    // (the maximum by ballots: done lanes are inactive here, which an xor
+                    // butterfly does not survive)
+                    if constexpr (!kFlat) credit(st_fetch, wave_max_small<32>(lane_cnt));
                 }
             } else {
                 region(rrow, reg::kScanLinear);
@@ -2648,13 +2663,13 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             scan_spheres<kLds>(P, lds_geom, n, o, d, max_t, best, hit_groups);
             tally(w_halves, 2u * (uint32_t)((n + 3) >> 2));
         }
-        if constexpr (kStats) st_hitgroups += hit_groups;
+        if constexpr (kStats) credit(st_hitgroups, hit_groups);
 
         // ---- shade (textures.glsl) or sky (functions.glsl:85-89) ----
         uint64_t t_shade = 0;
         if constexpr (kStats) {
             t_shade = ticks();
-            pt.shade_hits += (uint64_t)__popcll(__ballot(best >= 0));
+            credit(pt.shade_hits, (uint64_t)__popcll(__ballot(best >= 0)));
         }
         if constexpr (kFlat) {
             // a hit is shaded with the next iteration's camera rays; so is the sky of a lane
@@ -2671,7 +2686,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         } else {
             fresh = shade_and_advance(max_t, best, false, reg::kShadeBase0);
         }
-        if constexpr (kStats) pt.shade += ticks() - t_shade;
+        if constexpr (kStats) credit(pt.shade, ticks() - t_shade);
 
     }
 
@@ -2721,6 +2736,23 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         }
     }
     if constexpr (kStats) {
+        // the wave's counts: every counter summed over the lanes (credit); every lane is here
+        st_iters = wave_sum(st_iters);
+        st_active = wave_sum(st_active);
+        st_hitgroups = wave_sum(st_hitgroups);
+        st_fetch = wave_sum(st_fetch);
+        for (uint64_t PhaseTicks::*f :
+             {&PhaseTicks::scan, &PhaseTicks::levels, &PhaseTicks::node, &PhaseTicks::group,
+              &PhaseTicks::cand, &PhaseTicks::cand_passes, &PhaseTicks::big, &PhaseTicks::push,
+              &PhaseTicks::shade, &PhaseTicks::fetch, &PhaseTicks::pass_entries,
+              &PhaseTicks::pass_lanes, &PhaseTicks::partial_passes, &PhaseTicks::passes,
+              &PhaseTicks::group_entries, &PhaseTicks::node_entries, &PhaseTicks::cam,
+              &PhaseTicks::cam_entries, &PhaseTicks::cam_lanes, &PhaseTicks::cam_live,
+              &PhaseTicks::list_trips, &PhaseTicks::list_sum, &PhaseTicks::root_trips,
+              &PhaseTicks::root_sum, &PhaseTicks::shade_hits, &PhaseTicks::retire,
+              &PhaseTicks::fetch_iters, &PhaseTicks::blk_fetches, &PhaseTicks::items_cur,
+              &PhaseTicks::retire_iters, &PhaseTicks::quanta})
+            pt.*f = wave_sum(pt.*f);
         if (lane == 0 && P.debug) {
             atomicAdd(P.debug + 0, (unsigned long long)st_iters);
             atomicAdd(P.debug + 1, (unsigned long long)st_active);
