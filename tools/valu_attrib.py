@@ -99,6 +99,10 @@ def marker_lines():
     m["scan"] = find("// ---- one segment: scan the whole sphere list", m["cam_shade"])
     m["shade"] = find("// ---- shade (textures.glsl)", m["scan"])
     m["end"] = find("VCRT_WAVE_END_TIMES", m["shade"])
+    # the group-footprint level's capped push: the light lanes' loops, then the heavy-lane loop
+    m["push_light"] = find("if (!heavy) {")
+    m["push_heavy"] = find("region(rrow, reg::kPushHeavy);") - 1
+    m["push_end"] = find("slice = 0u;", m["push_heavy"])
     # the real branches of the rare fallbacks (asm volatile(""): not if-converted)
     m["rare"] = {find("const float full = __builtin_sqrtf(x);"),
                  find("const float full = __builtin_sqrtf(disc);"),
@@ -147,6 +151,11 @@ def phase(chain, mk):
             return "scan: group level (group footprint table lookups)"
         if "foot_mask" in text or "foot_cell" in text:
             return "scan: node level (footprint table lookups)"
+        own = [ln for f, fl, ln in chain if "scan_culled_flat" in f and fl == "tracer.hip"]
+        if own and mk["push_heavy"] <= own[0] < mk["push_end"]:
+            return "scan: group level (heavy lanes dealt across the wave)"
+        if own and mk["push_light"] <= own[0] < mk["push_heavy"]:
+            return "scan: group level (light lanes' push loops)"
         if "push_bound_pair_nf" in text or "near_far_addr" in text:
             return "scan: node level (chunk's 8 node boxes)"
         return "scan: set-up, lists, pushes, key"

@@ -92,6 +92,7 @@ enum : uint32_t {
     kPrefixSlow = 72, kLevelTop, kPushNode, kPushGroup, kPushLevel, kListedTrip,
     // the group-footprint level (fact (5g)): entries, push trips, slices of the rare sliced push
     kLevelGroups, kPushGroups0, kPushGroups1, kPushGroups2, kPushGroups3, kSliceGroups, kPushSlice,
+    kPushHeavy,  // the level's heavy-lane loop: one per lane whose groups the wave deals out
     kCount = 88
 };
 }  // namespace reg
@@ -907,6 +908,15 @@ constexpr int kChunkCap = 128;
 constexpr int kNodeCap = 576;
 constexpr int kGroupCap = 576;
 constexpr int kCandCap = 320;
+// The group-footprint level's push cap (fact (5g)): a lane with more groups than this is a heavy
+// lane, whose groups the wave deals across its lanes. Light counts up to 7 fit the 3-bit wave
+// prefix (a build with -DVCRT_PUSH_CAP=8..15, for A/B runs only, takes the 4-bit one).
+#ifndef VCRT_PUSH_CAP
+#define VCRT_PUSH_CAP 7
+#endif
+constexpr uint32_t kPushCap = VCRT_PUSH_CAP;
+constexpr int kPushBits = kPushCap <= 7u ? 3 : 4;
+static_assert(kPushCap >= 1u && kPushCap <= 15u, "light counts go through wave_prefix<kPushBits>");
 
 // Stack entries, by format kFmt:
 //   0 (narrow8, the LDS-table kernel, <= 256 groups): 16-bit owner << 8 | index, and 16-bit
@@ -1319,6 +1329,17 @@ __device__ __forceinline__ uint4 group_foot_mask(const TraceParams& p, const Box
 // kGroupFoot (the LDS-table kernel with kFlagGroupFoot, fact (5g)): each lane's group mask from
 // the group-level tables in `tnode`'s place, pushed straight onto the group stack: no node level,
 // no box test (kSlab -1: the flag only says where the ray's y interval comes from).
+// The push is capped: a lane with at most kPushCap groups pushes its own (per-word ctz loops);
+// the groups of a lane with more (a heavy lane) are dealt across the wave, lane i writing the
+// group of bit i of each 64-bit half of the mask. The dead-lane rule: the scan runs with finished
+// lanes masked off (exec = live, in 57 % of the final scene's wave-iterations) and a masked-off
+// lane writes nothing, so only the bits of `mask & live` go that way; each bit of `mask & ~live`
+// is written by the wave's first live lane in a scalar loop. (The other route, dealing those bit
+// positions to the live lanes by rank, needs each lane's r-th set bit of a 64-bit mask, about 30
+// VALU per half, and a loop of its own once the dead bits outnumber the live lanes -- one live
+// lane may stand for 63 dead ones; the scalar loop is bounded by the bits alone.) The entries
+// are the same multiset in another order, their total is known before the first write, and the
+// choice between the one-step and the sliced push is the one made before the cap.
 template <bool kStats, int kFmt, bool kGRec, bool kChunks, uint32_t kNS, int kSlab,
           bool kGroupFoot = false, class WS>
 __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const float4* tbound,
@@ -1405,8 +1426,17 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
         uint4 gm = group_foot_mask(p, br, ty0, ty1, ddx, ddz, tnode);
         if (listed) gm = make_uint4(0u, 0u, 0u, 0u);  // a listed camera ray has its groups
         const uint32_t cnt = (uint32_t)(__popc(gm.x) + __popc(gm.y) + __popc(gm.z) + __popc(gm.w));
-        uint32_t tot;
-        const uint32_t pre = wave_prefix<8>(cnt, tot, rrow);
+        // Light lanes (at most kPushCap groups) push their own groups, the light entries first;
+        // the wave deals each heavy lane's groups across its lanes after them (below). The
+        // wave's total, the heavy lanes' counts by scalar adds, is known before anything is
+        // written: it chooses between the one-step and the sliced push as it always did.
+        const bool heavy = cnt > kPushCap;
+        const uint64_t hv = __ballot(heavy);
+        uint32_t ltot;
+        const uint32_t pre = wave_prefix<kPushBits>(heavy ? 0u : cnt, ltot, rrow);
+        uint32_t tot = ltot;
+        for (uint64_t m = hv; m; m &= m - 1)
+            tot += (uint32_t)__builtin_amdgcn_readlane((int)cnt, __builtin_ctzll(m));
         const uint32_t tag = lane << F::kShift;
         // All lanes' groups in one step when the stack takes them (left over: the lists' entries);
         // else, rarely, a node's worth (8 groups: at most 512 entries) at a time with full passes
@@ -1415,24 +1445,55 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
         // later one fewer than nact left over.
         uint32_t slice = 16u;
         if (h.group + tot <= (uint32_t)kGroupCap) {
-            uint32_t pos = h.group + pre;
+            entry_t* out = ws->group + (h.group + pre);
+            uint32_t base = h.group + ltot;  // the heavy lanes' entries, above the light ones
             h.group += tot;
-            // one loop per mask word, each with its own region (the stats build counts trips)
-            for (uint32_t bits = gm.x; bits; bits &= bits - 1) {
-                region(rrow, reg::kPushGroups0);
-                ws->group[pos++] = (entry_t)(tag | (uint32_t)__builtin_ctz(bits));
+            // light lanes: one loop per mask word, each with its own region (the stats build
+            // counts trips); a wave leaves a loop with its busiest light lane
+            if (!heavy) {
+                for (uint32_t bits = gm.x; bits; bits &= bits - 1) {
+                    region(rrow, reg::kPushGroups0);
+                    *out++ = (entry_t)(tag | (uint32_t)__builtin_ctz(bits));
+                }
+                for (uint32_t bits = gm.y; bits; bits &= bits - 1) {
+                    region(rrow, reg::kPushGroups1);
+                    *out++ = (entry_t)(tag | 32u | (uint32_t)__builtin_ctz(bits));
+                }
+                for (uint32_t bits = gm.z; bits; bits &= bits - 1) {
+                    region(rrow, reg::kPushGroups2);
+                    *out++ = (entry_t)(tag | 64u | (uint32_t)__builtin_ctz(bits));
+                }
+                for (uint32_t bits = gm.w; bits; bits &= bits - 1) {
+                    region(rrow, reg::kPushGroups3);
+                    *out++ = (entry_t)(tag | 96u | (uint32_t)__builtin_ctz(bits));
+                }
             }
-            for (uint32_t bits = gm.y; bits; bits &= bits - 1) {
-                region(rrow, reg::kPushGroups1);
-                ws->group[pos++] = (entry_t)(tag | 32u | (uint32_t)__builtin_ctz(bits));
-            }
-            for (uint32_t bits = gm.z; bits; bits &= bits - 1) {
-                region(rrow, reg::kPushGroups2);
-                ws->group[pos++] = (entry_t)(tag | 64u | (uint32_t)__builtin_ctz(bits));
-            }
-            for (uint32_t bits = gm.w; bits; bits &= bits - 1) {
-                region(rrow, reg::kPushGroups3);
-                ws->group[pos++] = (entry_t)(tag | 96u | (uint32_t)__builtin_ctz(bits));
+            // heavy lanes, one at a time (wave-uniform): the lane's mask words as scalars, each
+            // 64-bit half as a lane mask: lane i writes group 64 half + i, below it the set bits
+            // under i (v_mbcnt), a few dozen instructions whatever the lane's count. A masked-off
+            // lane cannot write: the bits on dead positions (mask & ~live) go one by one through
+            // the wave's first live lane.
+            for (uint64_t m = hv; m; m &= m - 1) {
+                region(rrow, reg::kPushHeavy);
+                const uint32_t hl = (uint32_t)__builtin_ctzll(m);
+                const uint32_t w[4] = {(uint32_t)__builtin_amdgcn_readlane((int)gm.x, hl),
+                                       (uint32_t)__builtin_amdgcn_readlane((int)gm.y, hl),
+                                       (uint32_t)__builtin_amdgcn_readlane((int)gm.z, hl),
+                                       (uint32_t)__builtin_amdgcn_readlane((int)gm.w, hl)};
+#pragma unroll
+                for (uint32_t half = 0; half < 2u; ++half) {
+                    const uint64_t hm = ((uint64_t)w[2u * half + 1u] << 32) | w[2u * half];
+                    const uint32_t htag = (hl << F::kShift) | (64u * half);
+                    const uint64_t on = hm & live;
+                    if (__builtin_amdgcn_inverse_ballot_w64(on))
+                        ws->group[base + lanes_below(on)] = (entry_t)(htag | lane);
+                    base += (uint32_t)__popcll(on);
+                    for (uint64_t dead = hm & ~live; dead; dead &= dead - 1) {
+                        if (rank == 0u)
+                            ws->group[base] = (entry_t)(htag | (uint32_t)__builtin_ctzll(dead));
+                        ++base;
+                    }
+                }
             }
         } else {
             slice = 0u;
