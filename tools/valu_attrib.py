@@ -86,7 +86,7 @@ def marker_lines():
     m = {}
     m["impl"] = find("__device__ __forceinline__ void trace_impl(")
     m["lam"] = find("auto shade_and_advance", m["impl"])
-    m["lam_sky"] = find("const float len = sqrt_fast(dot(d, d));", m["lam"])
+    m["lam_sky"] = find("const float len = sqrt_fast(dot(d, d)", m["lam"])
     m["lam_end"] = find("if (ended) {", m["lam_sky"])
     m["loop"] = find("    for (;;) {", m["impl"])
     m["retire"] = find("// ---- retire the finished", m["loop"])
@@ -108,6 +108,41 @@ def marker_lines():
                  find("const float full = __builtin_sqrtf(disc);"),
                  find("normal = divs(pcv, cr.w);")}
     return m
+
+
+def untaken_ranges(texts):
+    """--untaken TEXT: the tracer.hip line ranges [(first, last, TEXT)] of the blocks that open
+    on the line holding TEXT (an `if (...) {` behind a wave-uniform condition that the frame at
+    hand never meets, e.g. "if ((P.flags & kFlagDirect) != 0u) {" or the steal's
+    "if (idle != 0u) {"). Instructions of such a block are issued by no wave of that frame, so
+    the tools list them on their own instead of charging them with their region's entries."""
+    src = open(TRACER).read().split("\n")
+    out = []
+    for text in texts:
+        hits = [i for i, ln in enumerate(src) if text in ln]
+        if len(hits) != 1:
+            sys.exit(f"--untaken {text!r}: {len(hits)} lines of tracer.hip hold it (need one)")
+        depth, i, closed = 0, hits[0], False
+        while not closed:  # to the brace that closes the block's first one (an else is not in it)
+            for ch in src[i][src[i].index(text) if i == hits[0] else 0:]:
+                depth += (ch == "{") - (ch == "}")
+                if ch == "}" and depth == 0:
+                    closed = True
+                    break
+            i += not closed
+        out.append((hits[0] + 1, i + 1, text))
+    return out
+
+
+def untaken_of(chain, ranges):
+    """The --untaken block that holds the instruction (any tracer.hip frame of its chain), or
+    None."""
+    for _, fl, ln in chain:
+        if fl == "tracer.hip":
+            for lo, hi, text in ranges:
+                if lo <= ln <= hi:
+                    return text
+    return None
 
 
 def phase(chain, mk):
@@ -200,6 +235,9 @@ def main():
     p.add_argument("--phases", default=None)
     p.add_argument("--sq-valu", type=float, default=None)
     p.add_argument("--json", default=None)
+    p.add_argument("--untaken", action="append", default=[], metavar="TEXT",
+                   help="a line of tracer.hip that opens a block the frame never enters "
+                        "(untaken_ranges): its instructions are listed as a phase of their own")
     a = p.parse_args()
     if a.hsaco is None:  # the line tables must come from the source the markers are read from
         a.hsaco = subprocess.run(["bash", os.path.join(ROOT, "tools", "mkab.sh"), "lt"],
@@ -216,8 +254,10 @@ def main():
     chains = symbolize(a.hsaco, [ad for ad, _, _ in insts])
     static = collections.Counter()
     ph_of = {}
+    ranges = untaken_ranges(a.untaken)
     for ad, mn, _ in insts:
-        ph = phase(chains[ad], mk)
+        un = untaken_of(chains[ad], ranges)
+        ph = phase(chains[ad], mk) if un is None else f"not taken in this frame: {un}"
         ph_of[ad] = ph
         if is_valu(mn):
             static[ph] += 1

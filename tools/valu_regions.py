@@ -87,10 +87,14 @@ def is_salu(mn):
     return mn.startswith("s_") and not mn.startswith(_NOT_SALU)
 
 
-def assign_regions(hsaco, product, kernel):
+UNTAKEN = -2  # region of the instructions in --untaken blocks: no wave of the frame issues them
+
+
+def assign_regions(hsaco, product, kernel, untaken=()):
     """Every instruction of `kernel` in the product code object with the region that holds it:
     ([(address, mnemonic, operands, region)], label(region) -> name). hsaco: the
-    -gline-tables-only build (None: built by tools/mkab.sh lt)."""
+    -gline-tables-only build (None: built by tools/mkab.sh lt). untaken: valu_attrib's
+    untaken_ranges; their instructions get the region UNTAKEN."""
     class A:
         pass
     a = A()
@@ -148,6 +152,8 @@ def assign_regions(hsaco, product, kernel):
         return before[-1] if before else same[0]
 
     def region_of(chain):
+        if V.untaken_of(chain, untaken) is not None:
+            return UNTAKEN
         fns = " | ".join(f for f, _, _ in chain)
         if any(k in fns for k in ("sin_canonical", "ksin", "kcos", "reduce_large")) or \
                 any(fl == "vcrt_math.h" and "sin3" in f and ln >= SIN3_FALLBACK
@@ -183,6 +189,8 @@ def assign_regions(hsaco, product, kernel):
 
 
     def label(r):
+        if r == UNTAKEN:
+            return "not taken in this frame (--untaken)"
         if r < 0:
             return "prologue/epilogue"
         if r in names:
@@ -214,8 +222,14 @@ def main():
                         "are left out instead of being charged with the shared regions' counts")
     p.add_argument("--detail", action="append", default=[],
                    help="region name: also list its static VALU per innermost source line")
+    p.add_argument("--untaken", action="append", default=[], metavar="TEXT",
+                   help="a line of tracer.hip that opens a block behind a wave-uniform branch "
+                        "the frame never takes (valu_attrib.untaken_ranges), e.g. 'if ((P.flags & "
+                        "kFlagDirect) != 0u) {' or 'if (idle != 0u) {': its instructions count "
+                        "zero times instead of their region's entries")
     a = p.parse_args()
-    insts_r, label, chains = assign_regions(a.hsaco, a.product, a.kernel)
+    insts_r, label, chains = assign_regions(a.hsaco, a.product, a.kernel,
+                                            V.untaken_ranges(a.untaken))
     static = collections.Counter()
     where = collections.defaultdict(collections.Counter)
     def scan_kind(chain):
@@ -243,7 +257,7 @@ def main():
     total = 0.0
     rows = []
     for r, n in static.items():
-        cnt = waves if r < 0 else d[REGION_DEBUG_BASE + r]
+        cnt = 0 if r == UNTAKEN else waves if r < 0 else d[REGION_DEBUG_BASE + r]
         dyn = n * cnt
         total += dyn
         rows.append((dyn, r, n, cnt))

@@ -1603,6 +1603,15 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.nch_magic[1] = g.nch_magic[1];
     const std::array<float, 12> cam = camera_array();
     for (int i = 0; i < 12; i++) p.cam[i] = cam[i];
+    // The camera phase of the flat scans traces a fresh camera ray from its quarter's list when
+    // the ray is in the guarded range. Its origin is the camera centre, a frame constant, so that
+    // half of the guard (every |component| <= 2^30, in a bounded scene; also rejects NaN) is
+    // decided here: a frame that fails it gets no lists, and its camera rays take the main scan,
+    // which tests their origin itself. (The group footprint keeps to the lists the scene has:
+    // such a frame's camera rays never reach a culled scan.)
+    if (!(g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
+          std::fabs(cam[11]) <= 0x1p30f))
+        p.prim_info = nullptr;
     const KernelChoice kc = select_kernel();
     hipFunction_t f = g.debug_stats == 1 ? kc.stats : kc.f;
     if (f == nullptr) return VK_ERROR_FEATURE_NOT_PRESENT;  // (a lens, no lens kernels loaded)

@@ -2557,10 +2557,17 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                                       1u];
             }
             const float aa = dot(d, d);
+#ifdef VCRT_OLD_GUARDS
             const bool cam_now = !kLens && fresh && (inf & 15u) != 15u &&
                                  (P.flags & kFlagSceneBounded) != 0 && aa >= 0x1p-20f &&
                                  aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f &&
                                  fabsf(o.y) <= 0x1p30f && fabsf(o.z) <= 0x1p30f;
+#else
+            // (a fresh ray of a pinhole frame starts at the camera centre: the origin's range
+            // test and the scene's bound are the host's, which hands out the lists, prim_info,
+            // only to a frame that passes both: no flag to load, no compare on o here)
+            const bool cam_now = !kLens && fresh && (inf & 15u) != 15u && guard_a(aa);
+#endif
             float mt = __uint_as_float(vconst<0x47c35000u>());  // kInfinity
             int bst = (int)vconst<0xffffffffu>();                // -1
             if (__ballot(cam_now)) {
@@ -2668,9 +2675,13 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         if constexpr (kCull != 0) {
             // culling needs every ray of the wave in the guarded finite range (see above)
             const float aa = dot(d, d);
+#ifdef VCRT_OLD_GUARDS
             const bool guarded = (P.flags & kFlagSceneBounded) != 0 && aa >= 0x1p-20f &&
                                  aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f &&
                                  fabsf(o.y) <= 0x1p30f && fabsf(o.z) <= 0x1p30f;
+#else
+            const bool guarded = (P.flags & kFlagSceneBounded) != 0 && guard_a(aa) && guard_o(o);
+#endif
             if (__ballot(!guarded) == 0) {
                 region(rrow, reg::kScan);
                 uint32_t lane_cnt = 0;

@@ -58,7 +58,10 @@ struct TraceParams {
                                 //   (4 lt + 2 qy + qx) of each local tile, or null: [0] the
                                 //   hierarchy groups (main scan) as offset << 4 | count (<= 8),
                                 //   [1] the spheres (camera fast trace) as first pair << 4 |
-                                //   count (<= 14); 15 = no list
+                                //   count (<= 14); 15 = no list. Null also when the scene is
+                                //   not bounded or a |component| of the camera centre exceeds
+                                //   2^30: with the lists the host vouches for that half of the
+                                //   camera rays' range guard (capi.cpp trace_frame)
     const uint16_t* prim_ids;   // hierarchy group indices of the group lists
     const float4* cam_rec;      // with the lists: [nbig * 4] the big groups' camera-relative
                                 //   records, pair-SoA (ocx0,ocx1,ocy0,ocy1) (ocz0,ocz1,cc0,cc1)

@@ -112,6 +112,22 @@ VCRT_HD void owner_of(uint32_t tx, uint32_t ty, uint32_t world, uint32_t tiles_x
 }
 
 // ---------------------------------------------------------------------------------------
+// The culled scans' range guards (tracer.hip): a ray is "guarded" when a = dot(d, d) lies in
+// [2^-20, 2^60] and every |origin component| <= 2^30. guard_a is the first as one subtraction
+// and one unsigned compare on a's bits (fp32 ordering is its bits' ordering for a >= 0; zero,
+// negative values, infinities and NaNs all wrap or lie above the window, so they read "not
+// guarded" as `a >= 0x1p-20f && a <= 0x1p60f` does); guard_o is the second, in the form the
+// kernel had. tests/test_guard_predicate_cpu.py compares guard_a with the two float compares.
+VCRT_HD bool guard_a(float a) {
+    return __builtin_bit_cast(uint32_t, a) - 0x35800000u <= 0x28000000u;  // 2^-20 .. 2^60
+}
+VCRT_HD bool guard_a_plain(float a) { return a >= 0x1p-20f && a <= 0x1p60f; }
+VCRT_HD bool guard_o(f3 o) {
+    return __builtin_fabsf(o.x) <= 0x1p30f && __builtin_fabsf(o.y) <= 0x1p30f &&
+           __builtin_fabsf(o.z) <= 0x1p30f;
+}
+
+// ---------------------------------------------------------------------------------------
 // canonical sin: fp32 argument widened to double, reduced to [-pi/4, pi/4] (Cody-Waite for
 // |x| < 2^20, exact 96-bit integer reduction by 2/pi above), fdlibm kernels, one rounding.
 // Equals the correctly rounded sinf except in astronomically rare double-rounding ties
@@ -205,23 +221,45 @@ VCRT_HD float sin_canonical(float xf) {
     return (float)s;
 }
 
+// The fast sine's polynomial: s(r) = r + r^3 P(r^2) on |r| <= pi/2, P of degree 6, the minimax
+// of the relative error |s(r) - sin r| / |sin r| (weighted Remez, tools/sin_minimax.py, which
+// prints these literals: 2^-52.2 with the coefficients rounded to double). VCRT_SIN_TOP is the
+// coefficient of r^15 and VCRT_SIN_REST(X) those of r^13 .. r^3 with their kSinC slots, one
+// Horner step each. (-DVCRT_SIN_TAYLOR builds the earlier form for A/B timing: the Taylor terms
+// to r^19, 2^-51.8, two more steps.)
+#ifdef VCRT_SIN_TAYLOR
+#define VCRT_SIN_TOP -0x1.2f49b46814157p-57  // (-1)^j / (2j+1)!, j = 9 .. 1
+#define VCRT_SIN_REST(X)                                                                   \
+    X(5, 0x1.952c77030ad4ap-49) X(6, -0x1.ae7f3e733b81fp-41) X(7, 0x1.6124613a86d09p-33)  \
+    X(8, -0x1.ae64567f544e4p-26) X(9, 0x1.71de3a556c734p-19) X(10, -0x1.a01a01a01a01ap-13) \
+    X(11, 0x1.1111111111111p-7) X(12, -0x1.5555555555555p-3)
+#define VCRT_SIN_PAD
+#else
+#define VCRT_SIN_TOP -0x1.9f1516b1690b8p-41
+#define VCRT_SIN_REST(X)                                                                   \
+    X(5, 0x1.60e6bed64df77p-33) X(6, -0x1.ae6355aa673ddp-26) X(7, 0x1.71de3806ad158p-19)  \
+    X(8, -0x1.a01a019a659b9p-13) X(9, 0x1.111111110a573p-7) X(10, -0x1.55555555554a8p-3)
+#define VCRT_SIN_PAD 0.0, 0.0  // kSinC keeps its 13 entries (TraceParams.sin_c)
+#endif
 // The fast sine's constants in the order sin_fast_try_n reads them from a table (kTab): 1/pi,
-// the 1.5 * 2^52 shifter, pi_hi, pi_mid, then (-1)^j / (2j+1)! for j = 9 .. 1. The host copies
-// them into TraceParams.sin_c; the literals in sin_fast_try_n are the same values.
+// the 1.5 * 2^52 shifter, pi_hi, pi_mid, then the polynomial's coefficients from r^15 down to
+// r^3 (and two unused entries). The host copies them into TraceParams.sin_c; the literals in
+// sin_fast_try and sin_fast_try_n are the same values.
+#define VCRT_SIN_LIST(j, lit) lit,
 constexpr double kSinC[13] = {0.31830988618379067154, 0x1.8p52, 0x1.921fb544p+1,
-                              0x1.0b4611a626331p-33, -0x1.2f49b46814157p-57,
-                              0x1.952c77030ad4ap-49, -0x1.ae7f3e733b81fp-41,
-                              0x1.6124613a86d09p-33, -0x1.ae64567f544e4p-26,
-                              0x1.71de3a556c734p-19, -0x1.a01a01a01a01ap-13,
-                              0x1.1111111111111p-7, -0x1.5555555555555p-3};
+                              0x1.0b4611a626331p-33, VCRT_SIN_TOP,
+                              VCRT_SIN_REST(VCRT_SIN_LIST) VCRT_SIN_PAD};
+#undef VCRT_SIN_LIST
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // The canonical sin on the device, by Ziv's method: one branch-free evaluation for every lane
 // (sin_canonical evaluates both fdlibm kernels under divergence, since the quadrant varies per
 // lane), accepted when it provably rounds to the same fp32 as sin_canonical, else
 // sin_canonical itself. Fast value s: x reduced modulo pi (k = rint(x / pi); r = x - k pi with
-// pi split as pi_hi (33 bits: k pi_hi exact for |k| < 2^20) + pi_mid, FMAs), then Taylor to
-// r^19 on |r| <= pi/2 (truncation < 2^-51.8 |sin r|), sign (-1)^k. For |x| < 2^19 and
+// pi split as pi_hi (33 bits: k pi_hi exact for |k| < 2^20) + pi_mid, FMAs), then the degree-15
+// minimax polynomial above on |r| <= pi/2 (approximation error < 2^-52.2 |sin r|, below the
+// 2^-51.8 of the Taylor form this analysis was made for, with two rounded steps fewer), sign
+// (-1)^k. For |x| < 2^19 and
 // |r| >= 2^-12 the error of s and that of sin_canonical's double result (2-term Cody-Waite
 // reduction, fdlibm kernels)
 // are each below 2^-48 |sin x|; if s lies farther than 2^-44 |s| from every fp32 rounding
@@ -261,15 +299,10 @@ __device__ __forceinline__ bool sin_fast_try(float xf, float& out) {
     double r = __builtin_fma(-k, VCRT_DC(0x1.921fb544p+1), x);
     r = __builtin_fma(-k, VCRT_DC(0x1.0b4611a626331p-33), r);
     const double r2 = r * r;
-    double p = VCRT_DC(-0x1.2f49b46814157p-57);  // (-1)^j / (2j+1)!, j = 9 .. 1
-    p = fma_vvs(p, r2, VCRT_DC(0x1.952c77030ad4ap-49));
-    p = fma_vvs(p, r2, VCRT_DC(-0x1.ae7f3e733b81fp-41));
-    p = fma_vvs(p, r2, VCRT_DC(0x1.6124613a86d09p-33));
-    p = fma_vvs(p, r2, VCRT_DC(-0x1.ae64567f544e4p-26));
-    p = fma_vvs(p, r2, VCRT_DC(0x1.71de3a556c734p-19));
-    p = fma_vvs(p, r2, VCRT_DC(-0x1.a01a01a01a01ap-13));
-    p = fma_vvs(p, r2, VCRT_DC(0x1.1111111111111p-7));
-    p = fma_vvs(p, r2, VCRT_DC(-0x1.5555555555555p-3));
+    double p = VCRT_DC(VCRT_SIN_TOP);
+#define VCRT_SIN1_STEP(j, lit) p = fma_vvs(p, r2, VCRT_DC(lit));
+    VCRT_SIN_REST(VCRT_SIN1_STEP)
+#undef VCRT_SIN1_STEP
     double s = __builtin_fma(r * r2, p, r);
     const uint64_t tb = __builtin_bit_cast(uint64_t, t);
     const uint64_t sb = __builtin_bit_cast(uint64_t, s) ^ (tb << 63);  // (-1)^k
@@ -312,7 +345,7 @@ __device__ __forceinline__ bool sin_fast_try_n(const float* xf, float* out,
     }
     for (int i = 0; i < N; ++i) r2[i] = r[i] * r[i];
     {
-        const double c = VCRT_SC(4, -0x1.2f49b46814157p-57);  // (-1)^j / (2j+1)!, j = 9 .. 1
+        const double c = VCRT_SC(4, VCRT_SIN_TOP);
         for (int i = 0; i < N; ++i) p[i] = c;
     }
 #define VCRT_SIN3_STEP(J, C)                                               \
@@ -320,14 +353,7 @@ __device__ __forceinline__ bool sin_fast_try_n(const float* xf, float* out,
         const double c = VCRT_SC(J, C);                                    \
         for (int i = 0; i < N; ++i) p[i] = fma_vvs(p[i], r2[i], c);        \
     }
-    VCRT_SIN3_STEP(5, 0x1.952c77030ad4ap-49)
-    VCRT_SIN3_STEP(6, -0x1.ae7f3e733b81fp-41)
-    VCRT_SIN3_STEP(7, 0x1.6124613a86d09p-33)
-    VCRT_SIN3_STEP(8, -0x1.ae64567f544e4p-26)
-    VCRT_SIN3_STEP(9, 0x1.71de3a556c734p-19)
-    VCRT_SIN3_STEP(10, -0x1.a01a01a01a01ap-13)
-    VCRT_SIN3_STEP(11, 0x1.1111111111111p-7)
-    VCRT_SIN3_STEP(12, -0x1.5555555555555p-3)
+    VCRT_SIN_REST(VCRT_SIN3_STEP)
 #undef VCRT_SIN3_STEP
 #undef VCRT_SC
     bool ok = true;
