@@ -23,5 +23,7 @@ VkResult EndRenderingOperation(void);
 VkResult SetRenderDescription(IN const vcrt_render_desc* desc);
 VkResult SetRenderScene(IN const vcrt_sphere* spheres, IN int32_t count);
 VkResult ReadFramebuffer(OUT float* rgba, IN size_t count);
+// Moves the camera of the running renderer (vcrt_set_camera); a later Begin starts from it too.
+VkResult SetRenderCamera(IN const vcrt_camera* camera);
 
 #endif

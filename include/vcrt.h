@@ -21,7 +21,9 @@
  * rank/world tile sharding and the tile re-assembly used after a multi-GPU gather; ray queries
  * on rays the caller supplies (vcrt_trace_rays: radiance and first hit) and occlusion queries
  * (vcrt_occlude_rays: is anything in the way within a per-ray reach); a thin lens for the
- * frames' camera (vcrt_render_desc.lens_radius, vcrt_lens_offsets).
+ * frames' camera (vcrt_render_desc.lens_radius, vcrt_lens_offsets); a camera that moves between
+ * frames without a new vcrt_begin (vcrt_set_camera: the camera-ray lists are rebuilt on the GPU;
+ * vcrt_get_camera_stats, vcrt_camera_lists_read).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -286,6 +288,52 @@ vcrt_result vcrt_assemble_tiles(const void* gathered, void* frame, int32_t width
 vcrt_result vcrt_get_stats(vcrt_stats* stats);
 /* Progressive mode: drop the accumulated frames (sample sequence restarts at 0). */
 vcrt_result vcrt_reset_accumulation(void);
+
+/* Moves the camera between frames (added; the reference's camera is compiled in). Requires
+ * vcrt_begin; a NULL camera or a call before vcrt_begin returns VCRT_ERROR_INITIALIZATION_FAILED
+ * before anything touches the GPU. The camera's values are taken as vcrt_begin takes them (not
+ * validated: a degenerate camera renders what it renders there).
+ * Every later frame is bit for bit the frame of a fresh renderer -- vcrt_begin with the same
+ * description and this camera, then vcrt_set_scene of the current scene -- vcrt_stats.segments and
+ * .kernel, the thin lens's frames and a later vcrt_set_scene included. Kept: the device, stream
+ * and code object, the scene and its culling tables, the framebuffers (a caller's
+ * vcrt_set_framebuffer_device too; the last frame stays in them until the next draw) and the
+ * communicator. Rebuilt: the pixel corners, the lens origins, both camera-ray lists and the
+ * camera-relative records. Reset: progressive accumulation restarts at sample 0 and the measured
+ * cost order is dropped. vcrt_trace_rays and vcrt_occlude_rays do not depend on the camera.
+ * The lists are built on the GPU by the camera-list kernels (csrc/camera_lists.hip), the very
+ * bytes vcrt_primary_lists / vcrt_primary_sphere_lists give for the new description, in buffers
+ * that are kept and only grow. VCRT_CAMERA_LISTS=host in the environment runs the host builders
+ * instead, and so does a code object without those kernels (an A/B build of an older tree).
+ * Local, not collective: under vcrt_comm_init every rank calls it with the same camera before
+ * the next draw. */
+vcrt_result vcrt_set_camera(const vcrt_camera* camera);
+
+/* The last vcrt_set_camera (all zero before the first). */
+typedef struct vcrt_camera_stats {
+    double   host_ms;       /* wall time of the call */
+    double   lists_ms;      /* HIP events around the list kernels, the 8-byte read-back of the
+                               totals between them included; 0 with the host builders */
+    int32_t  on_device;     /* 1: the camera-list kernels built the lists; 0: the host, or the
+                               renderer has no lists */
+    int32_t  reserved;      /* 0 */
+    uint64_t quarters;      /* 4 x local tiles (0: no lists) */
+    uint64_t group_ids;     /* entries of the group lists */
+    uint64_t pair_records;  /* pair records of the sphere lists */
+} vcrt_camera_stats;
+vcrt_result vcrt_get_camera_stats(vcrt_camera_stats* stats);
+
+/* Diagnostic: the camera-ray lists the next frame will use, copied back from the device in the
+ * form of the two host functions below (vcrt_primary_lists: group_info, ids;
+ * vcrt_primary_sphere_lists: sphere_info, rec), whoever built them: the host at vcrt_begin /
+ * vcrt_set_scene, or vcrt_set_camera. Returns the entries of each info (4 x local tiles), 0 when
+ * the renderer has no lists (no culling tables, a lens, VCRT_PRIMARY_LISTS=0), or a negative
+ * VkResult before vcrt_begin; *num_ids and *num_pairs receive the sizes. Writes the infos when
+ * cap_entries, ids when cap_ids and rec when cap_floats (12 per pair) are large enough; any
+ * pointer may be NULL. */
+int32_t vcrt_camera_lists_read(uint32_t* group_info, uint32_t* sphere_info, int32_t cap_entries,
+                               uint16_t* ids, int32_t cap_ids, float* rec, int32_t cap_floats,
+                               int32_t* num_ids, int32_t* num_pairs);
 /* The rank-local framebuffer encoded as sRGB8 RGBA (alpha linear), as the reference's
  * B8G8R8A8_SRGB swapchain stores it at present time (Frontend.cpp:43; shader.frag:14 copies the
  * texel): channel byte = round-to-nearest of 255 * sRGB(clamp(c, 0, 1)). bytes >= elements*4. */

@@ -137,6 +137,18 @@ class vcrt_ray_stats(ctypes.Structure):
     ]
 
 
+class vcrt_camera_stats(ctypes.Structure):
+    _fields_ = [
+        ("host_ms", ctypes.c_double),
+        ("lists_ms", ctypes.c_double),
+        ("on_device", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("quarters", ctypes.c_uint64),
+        ("group_ids", ctypes.c_uint64),
+        ("pair_records", ctypes.c_uint64),
+    ]
+
+
 class vcrt_comm_id(ctypes.Structure):
     _fields_ = [("internal", ctypes.c_char * 128)]  # an ncclUniqueId
 
@@ -165,6 +177,12 @@ SIGNATURES = {
                             [ctypes.c_int32] * 3 + [ctypes.c_uint32]),
     "vcrt_get_stats": (ctypes.c_int32, [ctypes.POINTER(vcrt_stats)]),
     "vcrt_reset_accumulation": (ctypes.c_int32, []),
+    "vcrt_set_camera": (ctypes.c_int32, [ctypes.POINTER(vcrt_camera)]),
+    "vcrt_get_camera_stats": (ctypes.c_int32, [ctypes.POINTER(vcrt_camera_stats)]),
+    "vcrt_camera_lists_read": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.POINTER(ctypes.c_int32)]),
     "vcrt_read_framebuffer_srgb8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_size_t]),
     "vcrt_selftest_sin": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.POINTER(ctypes.c_uint64),

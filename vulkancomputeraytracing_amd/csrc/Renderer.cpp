@@ -51,3 +51,9 @@ VkResult EndRenderingOperation(void) { return vcrt_end(); }
 VkResult ReadFramebuffer(OUT float* rgba, IN size_t count) {
     return vcrt_read_framebuffer(rgba, count);
 }
+
+VkResult SetRenderCamera(IN const vcrt_camera* camera) {
+    const VkResult r = vcrt_set_camera(camera);
+    if (r == VK_SUCCESS && g_desc_set) g_desc.camera = *camera;
+    return r;
+}

@@ -23,6 +23,7 @@
 #include <rccl/rccl.h>
 
 #include "Shader.hpp"
+#include "camera_lists_abi.h"
 #include "cluster.hpp"
 #include "comm_wait.hpp"
 #include "hip_status.hpp"
@@ -146,6 +147,25 @@ struct RendererState {
     uint16_t* d_prim_ids = nullptr;
     float4* d_cam_rec = nullptr;  // camera-relative records: big groups, sphere lists
     bool primary_lists = true;        // VCRT_PRIMARY_LISTS=0 turns them off
+    // the installed lists' sizes and their buffers' capacities (vcrt_set_camera reuses the
+    // buffers and grows them only): ids, pair records; info words, ids, floats of d_cam_rec
+    size_t prim_nids = 0, prim_npairs = 0;
+    size_t prim_info_cap = 0, prim_ids_cap = 0, cam_rec_cap = 0;
+    // the scene as vcrt_set_scene got it and its culling tables: vcrt_set_camera's host builders
+    // (VCRT_CAMERA_LISTS=host, or a code object without the list kernels) and sizes
+    std::vector<vcrt_sphere> h_spheres;
+    vcrt::CullTables h_ct;
+    // the camera-list kernels (camera_lists.hip; null: the code object predates them) and their
+    // scratch: grown boxes and sphere entries, counts + offsets + totals; kept and grown only
+    hipFunction_t k_cl_prepare = nullptr, k_cl_count = nullptr, k_cl_scan = nullptr,
+                  k_cl_fill = nullptr;
+    double* d_cl_boxes = nullptr;
+    double* d_cl_spheres = nullptr;
+    uint32_t* d_cl_counts = nullptr;
+    size_t cl_boxes_cap = 0, cl_spheres_cap = 0, cl_counts_cap = 0;  // elements
+    uint32_t* h_cl_totals = nullptr;  // pinned [2]
+    hipEvent_t ev_cl[2] = {nullptr, nullptr};
+    vcrt_camera_stats cam_stats{};
     // work decomposition
     int32_t quantum = 1;  // the accumulation quantum G (a power of two)
     int32_t chunk = 1, nchunks = 1;
@@ -458,6 +478,8 @@ void free_scene() {
     g.d_cam_rec = nullptr;
     g.d_prim_info = nullptr;
     g.d_prim_ids = nullptr;
+    g.prim_nids = g.prim_npairs = 0;
+    g.prim_info_cap = g.prim_ids_cap = g.cam_rec_cap = 0;
     g.d_cgroup = nullptr;
     g.d_cbound = nullptr;
     g.d_cbound_nf = nullptr;
@@ -578,6 +600,17 @@ VkResult bind_kernels() {
         (void)hipGetLastError();
         g.k_occlude_rays = nullptr;
     }
+    // optional: the camera-list kernels (vcrt_set_camera then runs the host builders)
+    const std::pair<hipFunction_t*, const char*> list_kernels[] = {
+        {&g.k_cl_prepare, "vcrt_camlist_prepare"},
+        {&g.k_cl_count, "vcrt_camlist_count"},
+        {&g.k_cl_scan, "vcrt_camlist_scan"},
+        {&g.k_cl_fill, "vcrt_camlist_fill"}};
+    for (const auto& [fp, name] : list_kernels)
+        if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
+            (void)hipGetLastError();
+            *fp = nullptr;
+        }
     VCRT_TRY(hipModuleGetFunction(&g.k_trace_cull_lane_lds_wide, m,
                                   "vcrt_trace_cull_lane_lds_wide"));
     VCRT_TRY(hipModuleGetFunction(&g.k_trace_cull_lane_lds_wide_stats, m,
@@ -990,6 +1023,136 @@ KernelChoice select_kernel() {
     return KernelChoice{f, fs, base, fc, fname, block, lds, variant};
 }
 
+// A device buffer of at least `rays` elements of `bytes_each`, kept between calls (the query
+// staging buffers, the camera lists): grown, its contents dropped, when too small.
+hipError_t grow(void** buf, size_t* cap, size_t rays, size_t bytes_each) {
+    if (rays <= *cap) return hipSuccess;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const hipError_t e = hipMalloc(buf, rays * bytes_each);
+    if (e == hipSuccess) *cap = rays;
+    return e;
+}
+
+// The camera-ray lists of primary.cpp into the buffers a frame reads (TraceParams.prim_info,
+// prim_ids, cam_rec): the two infos interleaved; the big groups' camera-relative records, then the
+// sphere lists' pairs, then 12 zero floats. The buffers are kept and only grow (free_scene drops
+// them), so a camera move allocates nothing once they are large enough.
+VkResult install_camera_lists(const vcrt::CullTables& ct, const vcrt::PrimaryLists& pl,
+                              const vcrt::PrimarySphereLists& sl) {
+    // camera rays of a tile start from its quarter's lists (primary.cpp): the groups
+    // for the main scan, the spheres for the camera fast trace; info interleaved
+    std::vector<uint32_t> info(2 * pl.info.size());
+    for (size_t e = 0; e < pl.info.size(); e++) {
+        info[2 * e] = pl.info[e];
+        info[2 * e + 1] = sl.info[e];
+    }
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_info), &g.prim_info_cap, info.size(),
+                  sizeof(uint32_t)));
+    VCRT_TRY(hipMemcpy(g.d_prim_info, info.data(), sizeof(uint32_t) * info.size(),
+                       hipMemcpyHostToDevice));
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_ids), &g.prim_ids_cap,
+                  pl.ids.size() + 1, sizeof(uint16_t)));
+    if (!pl.ids.empty())
+        VCRT_TRY(hipMemcpy(g.d_prim_ids, pl.ids.data(), sizeof(uint16_t) * pl.ids.size(),
+                           hipMemcpyHostToDevice));
+    // the camera fast trace's records: the big groups', then the sphere lists' pairs
+    std::vector<float> crec;
+    vcrt::build_camera_records(ct, camera_array().data(), crec);
+    crec.resize(static_cast<size_t>(ct.nbig) * 16);
+    crec.insert(crec.end(), sl.rec.begin(), sl.rec.end());
+    crec.resize(crec.size() + 12, 0.0f);  // never empty
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cam_rec), &g.cam_rec_cap, crec.size(),
+                  sizeof(float)));
+    VCRT_TRY(hipMemcpy(g.d_cam_rec, crec.data(), sizeof(float) * crec.size(),
+                       hipMemcpyHostToDevice));
+    g.prim_nids = pl.ids.size();
+    g.prim_npairs = sl.rec.size() / 12;
+    return VK_SUCCESS;
+}
+
+// The same lists built on the device (camera_lists.hip) from the tables vcrt_set_scene uploaded,
+// on the render stream: prepare, count, scan; the two totals come back (8 bytes) to size the
+// buffers; fill. The per-camera scalars are QuarterWalker's (primary.cpp), evaluated here once.
+VkResult build_camera_lists_device() {
+    const std::array<float, 12> cam = camera_array();
+    vcrt::CameraListParams p{};
+    for (int i = 0; i < 12; i++) p.cam[i] = cam[i];
+    const double* o = &p.cam[9];
+    const double on = std::sqrt(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]);
+    p.Q = (on + g.cmargin[0]) * (on + g.cmargin[0]) + g.cmargin[1];
+    const double* du = &p.cam[3];
+    const double* dv = &p.cam[6];
+    const double ndu = std::sqrt(du[0] * du[0] + du[1] * du[1] + du[2] * du[2]);
+    const double ndv = std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
+    constexpr double kExtra = 1e-3;
+    p.ex = kExtra / ndu;
+    p.ey = kExtra / ndv;
+    for (int a = 0; a < 3; a++) p.o[a] = cam[9 + a];
+    p.n = 4u * g.local_tiles;
+    p.ngroups = static_cast<uint32_t>(g.ncgroups);
+    p.nnodes = p.ngroups / static_cast<uint32_t>(vcrt::kNodeGroups);
+    p.ntops = (p.ngroups + 63u) / 64u;
+    p.nbig = static_cast<uint32_t>(g.ncbig);
+    p.nspheres = static_cast<uint32_t>(g.nspheres);
+    p.rank = static_cast<uint32_t>(g.desc.rank);
+    p.world = static_cast<uint32_t>(g.desc.world_size);
+    p.tiles_x = g.tiles_x;
+    p.ids_ok = p.ngroups <= 0xFFFFu ? 1u : 0u;
+    p.ctop = reinterpret_cast<const float*>(g.d_ctop);
+    p.cnode = reinterpret_cast<const float*>(g.d_cnode);
+    p.cbound = reinterpret_cast<const float*>(g.d_cbound);
+    p.cgroup = reinterpret_cast<const float*>(g.d_cgroup);
+    p.center_radius = reinterpret_cast<const float*>(g.d_center_radius);
+    const size_t nbox = static_cast<size_t>(p.ngroups) + p.nnodes + p.ntops;
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cl_boxes), &g.cl_boxes_cap,
+                  nbox * vcrt::kCamListBox, sizeof(double)));
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cl_spheres), &g.cl_spheres_cap,
+                  static_cast<size_t>(p.nspheres) * vcrt::kCamListBox, sizeof(double)));
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cl_counts), &g.cl_counts_cap,
+                  4 * static_cast<size_t>(p.n) + 2, sizeof(uint32_t)));
+    if (!g.h_cl_totals) VCRT_TRY(hipHostMalloc(&g.h_cl_totals, 2 * sizeof(uint32_t)));
+    for (int k = 0; k < 2; k++)
+        if (!g.ev_cl[k]) VCRT_TRY(hipEventCreate(&g.ev_cl[k]));
+    p.boxes = g.d_cl_boxes;
+    p.spheres = g.d_cl_spheres;
+    p.counts = g.d_cl_counts;
+    p.offsets = p.counts + 2 * static_cast<size_t>(p.n);
+    p.totals = p.offsets + 2 * static_cast<size_t>(p.n);
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_info), &g.prim_info_cap,
+                  2 * static_cast<size_t>(p.n), sizeof(uint32_t)));
+    p.prim_info = g.d_prim_info;
+    VCRT_TRY(hipEventRecord(g.ev_cl[0], g.stream));
+    const uint32_t quarter_blocks = (p.n + 255u) / 256u;
+    VkResult r = launch(g.k_cl_prepare,
+                        static_cast<uint32_t>(std::min<size_t>((nbox + p.nspheres + 255) / 256, 4096)),
+                        256, 0, p);
+    if (r != VK_SUCCESS) return r;
+    if ((r = launch(g.k_cl_count, quarter_blocks, 256, 0, p)) != VK_SUCCESS) return r;
+    if ((r = launch(g.k_cl_scan, 1, vcrt::kCamListScanThreads, 0, p)) != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(g.h_cl_totals, p.totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                            g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    const size_t nids = g.h_cl_totals[0], npairs = g.h_cl_totals[1];
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_ids), &g.prim_ids_cap, nids + 1,
+                  sizeof(uint16_t)));
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cam_rec), &g.cam_rec_cap,
+                  static_cast<size_t>(p.nbig) * 16 + npairs * 12 + 12, sizeof(float)));
+    p.prim_ids = g.d_prim_ids;
+    p.cam_rec = reinterpret_cast<float*>(g.d_cam_rec);
+    const uint32_t fill_threads = std::max(std::max(p.n, p.nbig), 12u);
+    if ((r = launch(g.k_cl_fill, (fill_threads + 255u) / 256u, 256, 0, p)) != VK_SUCCESS) return r;
+    VCRT_TRY(hipEventRecord(g.ev_cl[1], g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    float ms = 0.0f;
+    VCRT_TRY(hipEventElapsedTime(&ms, g.ev_cl[0], g.ev_cl[1]));
+    g.cam_stats.lists_ms = ms;
+    g.prim_nids = nids;
+    g.prim_npairs = npairs;
+    return VK_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1373,27 +1536,8 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
             vcrt::PrimarySphereLists sl;
             vcrt::build_primary_sphere_lists(ct, spheres, camera_array().data(), g.desc.width,
                                              g.desc.height, g.desc.rank, g.desc.world_size, sl);
-            std::vector<uint32_t> info(2 * pl.info.size());
-            for (size_t e = 0; e < pl.info.size(); e++) {
-                info[2 * e] = pl.info[e];
-                info[2 * e + 1] = sl.info[e];
-            }
-            VCRT_TRY(hipMalloc(&g.d_prim_info, sizeof(uint32_t) * info.size()));
-            VCRT_TRY(hipMemcpy(g.d_prim_info, info.data(), sizeof(uint32_t) * info.size(),
-                               hipMemcpyHostToDevice));
-            VCRT_TRY(hipMalloc(&g.d_prim_ids, sizeof(uint16_t) * (pl.ids.size() + 1)));
-            if (!pl.ids.empty())
-                VCRT_TRY(hipMemcpy(g.d_prim_ids, pl.ids.data(), sizeof(uint16_t) * pl.ids.size(),
-                                   hipMemcpyHostToDevice));
-            // the camera fast trace's records: the big groups', then the sphere lists' pairs
-            std::vector<float> crec;
-            vcrt::build_camera_records(ct, camera_array().data(), crec);
-            crec.resize(static_cast<size_t>(ct.nbig) * 16);
-            crec.insert(crec.end(), sl.rec.begin(), sl.rec.end());
-            crec.resize(crec.size() + 12, 0.0f);  // never empty
-            VCRT_TRY(hipMalloc(&g.d_cam_rec, sizeof(float) * crec.size()));
-            VCRT_TRY(hipMemcpy(g.d_cam_rec, crec.data(), sizeof(float) * crec.size(),
-                               hipMemcpyHostToDevice));
+            const VkResult ru = install_camera_lists(ct, pl, sl);
+            if (ru != VK_SUCCESS) return ru;
         }
     }
     VCRT_TRY(hipMalloc(&g.d_geom, sizeof(float) * table.size()));
@@ -1414,6 +1558,8 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
     VCRT_TRY(hipStreamSynchronize(nullptr));
     g.nspheres = count;
     g.stats.nspheres = count;
+    if (spheres != g.h_spheres.data()) g.h_spheres.assign(spheres, spheres + count);
+    g.h_ct = std::move(ct);
     if (g.desc.progressive && g.accumulated > 0) {
         // a new scene restarts progressive accumulation at sample 0: the jitter table holds
         // the last frame's sample indices
@@ -1959,6 +2105,12 @@ vcrt_result vcrt_end(void) {
     if (g.d_rq_counters) (void)hipFree(g.d_rq_counters);
     if (g.d_oq_tmax) (void)hipFree(g.d_oq_tmax);
     if (g.d_oq_occluded) (void)hipFree(g.d_oq_occluded);
+    if (g.d_cl_boxes) (void)hipFree(g.d_cl_boxes);
+    if (g.d_cl_spheres) (void)hipFree(g.d_cl_spheres);
+    if (g.d_cl_counts) (void)hipFree(g.d_cl_counts);
+    if (g.h_cl_totals) (void)hipHostFree(g.h_cl_totals);
+    for (int k = 0; k < 2; k++)
+        if (g.ev_cl[k]) (void)hipEventDestroy(g.ev_cl[k]);
     DestroyShaderStage(&g.stage);
     if (g.ev_start) (void)hipEventDestroy(g.ev_start);
     if (g.ev_stop) (void)hipEventDestroy(g.ev_stop);
@@ -1989,17 +2141,6 @@ vcrt_result ray_query_args(const float* origins, const float* dirs, uint32_t cou
     if (max_depth < 0 || count > kRayQueryMax) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
     if (!g.k_trace_rays) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     return VCRT_SUCCESS;
-}
-
-// A staging buffer of at least `rays` elements of `bytes_each`, kept between calls.
-hipError_t grow(void** buf, size_t* cap, size_t rays, size_t bytes_each) {
-    if (rays <= *cap) return hipSuccess;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc(buf, rays * bytes_each);
-    if (e == hipSuccess) *cap = rays;
-    return e;
 }
 
 // A query's grid: the blocks of kQueryBlock threads the occupancy query admits per CU, on every
@@ -2313,6 +2454,89 @@ vcrt_result vcrt_reset_accumulation(void) {
     VCRT_TRY(reset_sums());
     g.accumulated = 0;
     return setup_jitter(0);
+}
+
+vcrt_result vcrt_set_camera(const vcrt_camera* camera) {
+    if (!g.begun || !camera) return VCRT_ERROR_INITIALIZATION_FAILED;
+    const auto t0 = std::chrono::steady_clock::now();
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    g.desc.camera = *camera;
+    const vcrt_camera& c = g.desc.camera;
+    g.cam = vcrt::make_camera(g.desc.width, g.desc.height,
+                              vcrt::mk(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]),
+                              vcrt::mk(c.lookat[0], c.lookat[1], c.lookat[2]),
+                              vcrt::mk(c.vup[0], c.vup[1], c.vup[2]), c.vfov,
+                              [](double x) { return std::tan(x); });
+    g.cam_stats = vcrt_camera_stats{};
+    // the pixel corners, and the jitter and lens tables of sample 0 (accumulation restarts)
+    VkResult r = setup_jitter(0, g.total_pixels != 0);
+    if (r != VK_SUCCESS) return r;
+    if (g.d_prim_info != nullptr && g.ncgroups > 0) {  // the renderer has lists (vcrt_set_scene)
+        const char* how = std::getenv("VCRT_CAMERA_LISTS");
+        const bool device = !(how && std::strcmp(how, "host") == 0) && g.k_cl_prepare &&
+                            g.k_cl_count && g.k_cl_scan && g.k_cl_fill;
+        if (device) {
+            if ((r = build_camera_lists_device()) != VK_SUCCESS) return r;
+        } else {
+            vcrt::PrimaryLists pl;
+            vcrt::build_primary_lists(g.h_ct, camera_array().data(), g.desc.width, g.desc.height,
+                                      g.desc.rank, g.desc.world_size, pl);
+            vcrt::PrimarySphereLists sl;
+            vcrt::build_primary_sphere_lists(g.h_ct, g.h_spheres.data(), camera_array().data(),
+                                             g.desc.width, g.desc.height, g.desc.rank,
+                                             g.desc.world_size, sl);
+            if ((r = install_camera_lists(g.h_ct, pl, sl)) != VK_SUCCESS) return r;
+            // (the uploads ran on the null stream; the render stream does not wait for it)
+            VCRT_TRY(hipStreamSynchronize(nullptr));
+        }
+        g.cam_stats.on_device = device ? 1 : 0;
+        g.cam_stats.quarters = 4ull * g.local_tiles;
+        g.cam_stats.group_ids = g.prim_nids;
+        g.cam_stats.pair_records = g.prim_npairs;
+    }
+    g.accumulated = 0;
+    g.order_key = 0;  // the cost order is measured again
+    VCRT_TRY(reset_sums());
+    g.cam_stats.host_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return VCRT_SUCCESS;
+}
+
+vcrt_result vcrt_get_camera_stats(vcrt_camera_stats* stats) {
+    if (!g.begun || !stats) return VCRT_ERROR_INITIALIZATION_FAILED;
+    *stats = g.cam_stats;
+    return VCRT_SUCCESS;
+}
+
+int32_t vcrt_camera_lists_read(uint32_t* group_info, uint32_t* sphere_info, int32_t cap_entries,
+                               uint16_t* ids, int32_t cap_ids, float* rec, int32_t cap_floats,
+                               int32_t* num_ids, int32_t* num_pairs) {
+    if (!g.begun) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (num_ids) *num_ids = 0;
+    if (num_pairs) *num_pairs = 0;
+    if (g.d_prim_info == nullptr) return 0;  // no tables, a lens, or VCRT_PRIMARY_LISTS=0
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    const size_t n = 4 * static_cast<size_t>(g.local_tiles);
+    if (num_ids) *num_ids = static_cast<int32_t>(g.prim_nids);
+    if (num_pairs) *num_pairs = static_cast<int32_t>(g.prim_npairs);
+    if ((group_info || sphere_info) && cap_entries >= 0 && static_cast<size_t>(cap_entries) >= n) {
+        std::vector<uint32_t> info(2 * n);
+        VCRT_TRY(hipMemcpy(info.data(), g.d_prim_info, sizeof(uint32_t) * info.size(),
+                           hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < n; e++) {
+            if (group_info) group_info[e] = info[2 * e];
+            if (sphere_info) sphere_info[e] = info[2 * e + 1];
+        }
+    }
+    if (ids && g.prim_nids > 0 && cap_ids >= 0 && static_cast<size_t>(cap_ids) >= g.prim_nids)
+        VCRT_TRY(hipMemcpy(ids, g.d_prim_ids, sizeof(uint16_t) * g.prim_nids,
+                           hipMemcpyDeviceToHost));
+    const size_t floats = g.prim_npairs * 12;
+    if (rec && floats > 0 && cap_floats >= 0 && static_cast<size_t>(cap_floats) >= floats)
+        VCRT_TRY(hipMemcpy(rec, reinterpret_cast<const float*>(g.d_cam_rec) +
+                                    static_cast<size_t>(g.ncbig) * 16,
+                           sizeof(float) * floats, hipMemcpyDeviceToHost));
+    return static_cast<int32_t>(n);
 }
 
 vcrt_result vcrt_selftest_sin(uint32_t first, uint32_t count, uint64_t* mismatches,

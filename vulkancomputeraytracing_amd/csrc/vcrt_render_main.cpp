@@ -3,6 +3,7 @@
 // the frame as PFM (linear rgba32f, as the compute image holds it) or PPM (sRGB8 encoded on the
 // GPU, as the B8G8R8A8_SRGB swapchain shows it: Frontend.cpp:43).
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,7 +18,7 @@ int usage() {
     std::fprintf(stderr,
                  "usage: vcrt_render [--width W] [--height H] [--spp N] [--depth D] "
                  "[--scene final|three|red|stress4096] [--frames F] [--progressive 0|1] [--device I] "
-                 "[--lens-radius R] [--out file.ppm|file.pfm]\n");
+                 "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm]\n");
     return 2;
 }
 
@@ -27,6 +28,7 @@ int main(int argc, char** argv) {
     vcrt_render_desc desc;
     vcrt_default_desc(&desc);
     int scene = VCRT_SCENE_FINAL, frames = 1;
+    double orbit = 0.0;  // degrees about the world y axis through lookat, per frame
     std::string out;
     bool configured = false;  // any option that changes the description or the scene
     for (int i = 1; i < argc; i++) {
@@ -42,6 +44,7 @@ int main(int argc, char** argv) {
         else if (a == "--device") desc.device = std::atoi(v);
         else if (a == "--progressive") desc.progressive = std::atoi(v);
         else if (a == "--lens-radius") desc.lens_radius = std::strtof(v, nullptr);  // thin lens
+        else if (a == "--orbit") orbit = std::strtod(v, nullptr);
         else if (a == "--out") out = v;
         else if (a == "--scene") {
             const std::string s = v;
@@ -67,6 +70,19 @@ int main(int argc, char** argv) {
         return 1;
     }
     for (int f = 0; f < frames && r == VK_SUCCESS; f++) {
+        if (f >= 1 && orbit != 0.0) {
+            // frame f looks from the command line's lookfrom turned by f * DEG about the y axis
+            // through lookat (in double, rounded to float); the move rebuilds the lists on the GPU
+            const double th = f * orbit * 3.14159265358979323846 / 180.0;
+            const double dx = static_cast<double>(desc.camera.lookfrom[0]) - desc.camera.lookat[0];
+            const double dz = static_cast<double>(desc.camera.lookfrom[2]) - desc.camera.lookat[2];
+            vcrt_camera cam = desc.camera;
+            cam.lookfrom[0] = static_cast<float>(desc.camera.lookat[0] + dx * std::cos(th) +
+                                                 dz * std::sin(th));
+            cam.lookfrom[2] = static_cast<float>(desc.camera.lookat[2] - dx * std::sin(th) +
+                                                 dz * std::cos(th));
+            if ((r = SetRenderCamera(&cam)) != VK_SUCCESS) break;
+        }
         r = DrawNextFrame();
         vcrt_stats st;
         vcrt_get_stats(&st);

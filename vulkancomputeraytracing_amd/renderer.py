@@ -67,6 +67,21 @@ class RenderDesc:
             d.code_object_path = self._path_keepalive
         return d
 
+    def with_camera(self, lookfrom=None, lookat=None, vup=None, vfov=None) -> "RenderDesc":
+        """A copy of this description with the given camera fields; omitted ones keep their
+        value."""
+        import dataclasses
+        changes = {}
+        for name, v in (("lookfrom", lookfrom), ("lookat", lookat), ("vup", vup)):
+            if v is not None:
+                v = tuple(float(x) for x in v)
+                if len(v) != 3:
+                    raise ValueError(f"{name}: three components expected")
+                changes[name] = v
+        if vfov is not None:
+            changes["vfov"] = float(vfov)
+        return dataclasses.replace(self, **changes)
+
 
 def work_quantum(desc: RenderDesc) -> int:
     """The accumulation quantum G the renderer uses for `desc`, from the C ABI
@@ -367,6 +382,44 @@ class Renderer:
 
     def reset_accumulation(self) -> None:
         N.check("vcrt_reset_accumulation", self._L().vcrt_reset_accumulation())
+
+    def set_camera(self, lookfrom=None, lookat=None, vup=None, vfov=None) -> None:
+        """Move the camera between frames (vcrt_set_camera); omitted fields keep their value and
+        `self.desc` follows. Later frames are bit for bit those of a fresh Renderer with the new
+        description; the scene, its tables, the framebuffers and the device state are kept, the
+        camera-ray lists are rebuilt on the GPU and progressive accumulation restarts."""
+        new = self.desc.with_camera(lookfrom, lookat, vup, vfov)
+        cam = new.to_c().camera
+        N.check("vcrt_set_camera", self._L().vcrt_set_camera(ctypes.byref(cam)))
+        self.desc = new
+        self._c_desc.camera = cam
+
+    def camera_stats(self) -> dict:
+        """The last set_camera (vcrt_get_camera_stats): host_ms, lists_ms, on_device, quarters,
+        group_ids, pair_records."""
+        s = N.vcrt_camera_stats()
+        N.check("vcrt_get_camera_stats", self._L().vcrt_get_camera_stats(ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in N.vcrt_camera_stats._fields_
+                if name != "reserved"}
+
+    def camera_lists(self) -> dict:
+        """The camera-ray lists the next frame will use, read back from the device
+        (vcrt_camera_lists_read) in the form of scene.primary_lists / primary_sphere_lists:
+        group_info, sphere_info uint32 [4 x local tiles], ids uint16, rec float32 [pairs, 12].
+        All empty when the renderer has no lists (no culling tables, a lens)."""
+        lib = self._L()
+        nids, npairs = ctypes.c_int32(0), ctypes.c_int32(0)
+        n = N.check_count("vcrt_camera_lists_read", lib.vcrt_camera_lists_read(
+            None, None, 0, None, 0, None, 0, ctypes.byref(nids), ctypes.byref(npairs)))
+        ginfo, sinfo = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        ids = np.zeros(nids.value, np.uint16)
+        rec = np.zeros((npairs.value, 12), np.float32)
+        if n:
+            N.check_count("vcrt_camera_lists_read", lib.vcrt_camera_lists_read(
+                ginfo.ctypes.data_as(ctypes.c_void_p), sinfo.ctypes.data_as(ctypes.c_void_p), n,
+                ids.ctypes.data_as(ctypes.c_void_p), len(ids),
+                rec.ctypes.data_as(ctypes.c_void_p), rec.size, None, None))
+        return {"group_info": ginfo, "ids": ids, "sphere_info": sinfo, "rec": rec}
 
     def framebuffer_device(self) -> tuple[int, int]:
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
