@@ -93,6 +93,7 @@ enum : uint32_t {
     // the group-footprint level (fact (5g)): entries, push trips, slices of the rare sliced push
     kLevelGroups, kPushGroups0, kPushGroups1, kPushGroups2, kPushGroups3, kSliceGroups, kPushSlice,
     kPushHeavy,  // the level's heavy-lane loop: one per lane whose groups the wave deals out
+    kGroupPass2,  // a group pass that took a second entry per lane (flat_group_pass2)
     kCount = 88
 };
 }  // namespace reg
@@ -900,11 +901,20 @@ __device__ __forceinline__ float hit_sign(float hb, float cc, float disc) {
 // passes run deepest stack first; the final drain's partial passes run top-down), which bounds
 // every stack: < 64 left over + at most 8 x 64 (node, group) or 4 x 64 (cand) pushed by one pass;
 // chunk entries (one per lane and chunk) are pushed between drains, onto < 64 left over.
+// The group-footprint scan (fact (5g)) has its own drain, flat_drain_groups: a group pass there
+// takes two entries per lane, one test after the other, wherever the rule would run a second
+// group pass right after the first (ng >= nact + th), and counts as two; it pushes at most
+// 2 x 4 x 64 candidates onto < 64 left over, 575 in all, which that scan keeps in its unused node
+// stack (see kNodeCap).
 // (Round 2: the chunk level was wave-uniform -- every lane tested the nodes of every chunk some
 // lane needed, with per-lane min/max box tests on scalar-loaded boxes; as passes the nodes are
 // tested only for the lanes that need the chunk, by the near/far box test.)
 constexpr int kPendSky = -2;  // trace_impl's pend_best for a deferred sky segment
 constexpr int kChunkCap = 128;
+// 63 + 8 x 64 node entries; or, in the group-footprint scan, whose node stack is never touched and
+// has the candidates' 16-bit type, that scan's candidates: 63 + 2 x 4 x 64 after a double group
+// pass, 575 too. `cand` (kCandCap: 63 + 4 x 64) holds the candidates of every other scan, and the
+// LDS stays as it was.
 constexpr int kNodeCap = 576;
 constexpr int kGroupCap = 576;
 constexpr int kCandCap = 320;
@@ -917,6 +927,14 @@ constexpr int kCandCap = 320;
 constexpr uint32_t kPushCap = VCRT_PUSH_CAP;
 constexpr int kPushBits = kPushCap <= 7u ? 3 : 4;
 static_assert(kPushCap >= 1u && kPushCap <= 15u, "light counts go through wave_prefix<kPushBits>");
+// The group-footprint scan's drain with double group passes (flat_drain_groups). For A/B runs
+// only: -DVCRT_GROUP_PASS2=0 builds flat_drain's single passes with the candidates in `cand`,
+// =2 flat_drain_groups with single passes only.
+#ifndef VCRT_GROUP_PASS2
+#define VCRT_GROUP_PASS2 1
+#endif
+constexpr bool kGroupPass2 = VCRT_GROUP_PASS2 != 0;
+constexpr bool kGroupPassDouble = VCRT_GROUP_PASS2 == 1;
 
 // Stack entries, by format kFmt:
 //   0 (narrow8, the LDS-table kernel, <= 256 groups): 16-bit owner << 8 | index, and 16-bit
@@ -946,6 +964,18 @@ struct WaveScratch {
 static_assert(sizeof(WaveScratch<0, false>) == kWaveScratchBytes8, "host LDS size");  // 3464
 static_assert(sizeof(WaveScratch<1>) == kWaveScratchBytes, "host LDS size");
 static_assert(sizeof(WaveScratch<2>) == kWaveScratchBytesWide, "host LDS size");
+static_assert(std::is_same<FlatFmt<0>::cand_t, FlatFmt<0>::entry_t>::value &&
+                  kNodeCap >= 63 + 2 * 4 * 64 && kCandCap >= 63 + 4 * 64,
+              "a double group pass's candidates fit the node stack, a single pass's `cand`");
+
+// The candidate stack: `node` for the group-footprint scan with double passes (see kNodeCap).
+template <bool kInNode, class WS>
+__device__ __forceinline__ auto* cand_stack(WS* ws) {
+    if constexpr (kInNode)
+        return ws->node;
+    else
+        return ws->cand;
+}
 
 // The flat scans' hierarchy group records, 80 B each: four pair-SoA float4s + the members'
 // world[] indices. Global records (kGRec, TraceParams.cgroup): the indices as int bits. LDS
@@ -1021,11 +1051,35 @@ struct FlatRay {  // this lane's ray, as the passes fetch it
     BoxRay br;
 };
 
+// The exact test of group entry e (owner << kShift | group) for the owner's ray: bit s set when
+// member s may be accepted (hit_sign).
+template <int kFmt, bool kGRec>
+__device__ __forceinline__ uint32_t group_hit_bits(uint32_t e, const GroupTab<kGRec>& tg,
+                                                   const FlatRay& my) {
+    using F = FlatFmt<kFmt>;
+    const int src = (int)(e >> F::kShift) << 2;
+    const float ox = from_lane(src, my.ox), oy = from_lane(src, my.oy), oz = from_lane(src, my.oz);
+    const float dx = from_lane(src, my.dx), dy = from_lane(src, my.dy), dz = from_lane(src, my.dz);
+    const float a = from_lane(src, my.a);
+    const float4* g = tg.rec(e & F::kMask);
+    const float4 q0 = g[0], q1 = g[1], q2 = g[2], q3 = g[3];
+    const v2f vox = {ox, ox}, voy = {oy, oy}, voz = {oz, oz};
+    const v2f vdx = {dx, dx}, vdy = {dy, dy}, vdz = {dz, dz}, a2 = {a, a};
+    v2f hb01, cc01, d01, hb23, cc23, d23;
+    pair_disc_cc(vox, voy, voz, vdx, vdy, vdz, a2, q0, q1, hb01, cc01, d01);
+    pair_disc_cc(vox, voy, voz, vdx, vdy, vdz, a2, q2, q3, hb23, cc23, d23);
+    uint32_t hits = push_sign(0u, hit_sign(hb23.y, cc23.y, d23.y));
+    hits = push_sign(hits, hit_sign(hb23.x, cc23.x, d23.x));
+    hits = push_sign(hits, hit_sign(hb01.y, cc01.y, d01.y));
+    return push_sign(hits, hit_sign(hb01.x, cc01.x, d01.x));
+}
+
 // One pass over the top min(n, nact) entries of a stack (n wave-uniform). kind 0: cand,
 // 1: group, 2: node. Lanes ranked past the entries run on their own ray and push nothing.
 // kKind 0: cand, 1: group, 2: node. n: this stack's height; pushed: the height of the stack
 // this pass pushes onto (group for node passes, cand for group passes).
-template <int kKind, int kFmt, bool kGRec, uint32_t kNS, int kSlab, class WS>
+template <int kKind, int kFmt, bool kGRec, uint32_t kNS, int kSlab, bool kCandInNode = false,
+          class WS>
 __device__ __forceinline__ void flat_pass(uint32_t& n, uint32_t& pushed, uint32_t nact,
                                           uint32_t rank, uint32_t lane, WS* ws,
                                           const float4* tbound, const float4* tnode, uint32_t ncg,
@@ -1085,21 +1139,7 @@ __device__ __forceinline__ void flat_pass(uint32_t& n, uint32_t& pushed, uint32_
         }
     } else if constexpr (kKind == 1) {  // group: exact test of the 4 members for the owner's ray
         const uint32_t e = act ? (uint32_t)ws->group[top + rank] : (lane << F::kShift);
-        const int src = (int)(e >> F::kShift) << 2;
-        const float ox = from_lane(src, my.ox), oy = from_lane(src, my.oy), oz = from_lane(src, my.oz);
-        const float dx = from_lane(src, my.dx), dy = from_lane(src, my.dy), dz = from_lane(src, my.dz);
-        const float a = from_lane(src, my.a);
-        const float4* g = tg.rec(e & F::kMask);
-        const float4 q0 = g[0], q1 = g[1], q2 = g[2], q3 = g[3];
-        const v2f vox = {ox, ox}, voy = {oy, oy}, voz = {oz, oz};
-        const v2f vdx = {dx, dx}, vdy = {dy, dy}, vdz = {dz, dz}, a2 = {a, a};
-        v2f hb01, cc01, d01, hb23, cc23, d23;
-        pair_disc_cc(vox, voy, voz, vdx, vdy, vdz, a2, q0, q1, hb01, cc01, d01);
-        pair_disc_cc(vox, voy, voz, vdx, vdy, vdz, a2, q2, q3, hb23, cc23, d23);
-        uint32_t hits = push_sign(0u, hit_sign(hb23.y, cc23.y, d23.y));
-        hits = push_sign(hits, hit_sign(hb23.x, cc23.x, d23.x));
-        hits = push_sign(hits, hit_sign(hb01.y, cc01.y, d01.y));
-        hits = push_sign(hits, hit_sign(hb01.x, cc01.x, d01.x));
+        uint32_t hits = group_hit_bits<kFmt>(e, tg, my);
         hits = act ? hits : 0u;
         uint32_t tot;
         uint32_t pos = pushed + wave_prefix<3>((uint32_t)__popc(hits), tot, rrow);
@@ -1110,11 +1150,11 @@ __device__ __forceinline__ void flat_pass(uint32_t& n, uint32_t& pushed, uint32_
                 region(rrow, reg::kPushGroup);
                 const uint32_t s = (uint32_t)__builtin_ctz(hits);
                 hits &= hits - 1;
-                ws->cand[pos++] = (typename F::cand_t)(tag | s);
+                cand_stack<kCandInNode>(ws)[pos++] = (typename F::cand_t)(tag | s);
             } while (hits);
         }
     } else {  // cand: the member's root (its hb, cc, disc recomputed as the packed test did)
-        const uint32_t e = act ? ws->cand[top + rank] : (lane << (F::kShift + 2));
+        const uint32_t e = act ? cand_stack<kCandInNode>(ws)[top + rank] : (lane << (F::kShift + 2));
         const int src = (int)(e >> (F::kShift + 2)) << 2;
         const float ox = from_lane(src, my.ox), oy = from_lane(src, my.oy), oz = from_lane(src, my.oz);
         const float dx = from_lane(src, my.dx), dy = from_lane(src, my.dy), dz = from_lane(src, my.dz);
@@ -1133,6 +1173,45 @@ __device__ __forceinline__ void flat_pass(uint32_t& n, uint32_t& pushed, uint32_
         const float t = candidate_t_fast(hb, disc, a, ya);
         if (act && t > kMinT && t < kInfinity)
             atomicMin(&ws->key[e >> (F::kShift + 2)], pack_hit(t, tg.index(gi, s)));
+    }
+}
+
+// A double group pass of the group-footprint scan: the top m = min(n, 2 nact) group entries, for
+// nact < n. Lane `rank` tests entry top + rank (m > nact: every live lane has one) and then entry
+// top + nact + rank when that lies below m, one after the other on the same registers: only the
+// first test's four hit bits and its entry stay live across the second. The eight hit bits take
+// one wave prefix and one push loop, a candidate's entry chosen by its bit's half. What one pass
+// costs whatever it holds (the guarded read, the prefix, the loop's set-up, flat_drain's
+// selection) is paid once for two passes' entries.
+template <int kFmt, bool kGRec, class WS>
+__device__ __forceinline__ void flat_group_pass2(uint32_t& n, uint32_t& pushed, uint32_t nact,
+                                                 uint32_t rank, uint32_t lane, WS* ws,
+                                                 const GroupTab<kGRec>& tg, const FlatRay& my,
+                                                 uint32_t* rrow = nullptr) {
+    using F = FlatFmt<kFmt>;
+    const uint32_t m = min(n, 2u * nact), top = n - m;
+    n = top;
+    const uint32_t e0 = ws->group[top + rank];
+    uint32_t hits = group_hit_bits<kFmt>(e0, tg, my);
+    // the second entry's index passes through the first test's result (an empty asm), so that
+    // nothing of the second test is scheduled into the first and holds registers beside it
+    uint32_t i1 = nact + rank;
+    asm volatile("" : "+v"(hits), "+v"(i1));
+    const bool act = i1 < m;
+    const uint32_t e1 = act ? (uint32_t)ws->group[top + i1] : (lane << F::kShift);
+    const uint32_t hits1 = group_hit_bits<kFmt>(e1, tg, my);
+    hits |= act ? hits1 << 4 : 0u;
+    uint32_t tot;
+    uint32_t pos = pushed + wave_prefix<4>((uint32_t)__popc(hits), tot, rrow);
+    pushed += tot;
+    if (hits) {
+        const uint32_t tag0 = e0 << 2, tag1 = e1 << 2;
+        do {
+            region(rrow, reg::kPushGroup);
+            const uint32_t s = (uint32_t)__builtin_ctz(hits);
+            hits &= hits - 1;
+            ws->node[pos++] = (typename F::cand_t)((s < 4u ? tag0 : tag1) | (s & 3u));
+        } while (hits);
     }
 }
 
@@ -1256,6 +1335,70 @@ __device__ __forceinline__ void flat_drain(uint32_t th, uint32_t nact, uint32_t 
     h.group = ng;
     h.node = nn;
     h.chunk = nk;
+}
+
+// flat_drain for the group-footprint scan (its kGroupsOnly form: only the group and candidate
+// stacks hold anything) with double group passes and the candidates in `node` (see kNodeCap).
+// th is 1 or nact, so flat_drain's rule comes down to two scalar compares a trip: a group pass
+// while fewer than nact candidates wait and the group stack holds th entries (a drain: any; full
+// passes only: nact), else a candidate pass while that stack holds th (nact of them run first
+// either way; a drain then takes the remainder), else done. The group pass is a double one where
+// the rule would choose a group pass again right after a single one, ng >= nact + th, and counts
+// as those two in n_groups and in the stats build's pass counters; between slices (th = nact) it
+// takes full halves only, so the remainder joins the next slice as it did.
+template <bool kStats, int kFmt, bool kGRec, class WS>
+__device__ __forceinline__ void flat_drain_groups(uint32_t th, uint32_t nact, uint32_t rank,
+                                                  uint32_t lane, WS* ws, FlatStacks& h,
+                                                  const GroupTab<kGRec>& tg, const FlatRay& my,
+                                                  uint32_t& n_groups, PhaseTicks& pt,
+                                                  uint32_t* rrow = nullptr) {
+    static_assert(kFmt == 0, "the candidates' type is the node entries' at kFmt 0");
+    uint32_t nc = h.cand, ng = h.group;
+    auto count_pass = [&](uint32_t n) {  // the stats build's occupancy of a pass over n entries
+        if constexpr (kStats) {
+            credit(pt.pass_entries, min(n, nact));
+            credit(pt.pass_lanes, nact);
+            credit(pt.partial_passes, n < nact);
+            credit(pt.passes, 1u);
+        }
+    };
+    for (;;) {
+        __builtin_amdgcn_wave_barrier();  // the entries were written by other lanes
+        region(rrow, reg::kDrainTrip);
+        uint64_t t0 = 0;
+        if constexpr (kStats) t0 = ticks();
+        if (nc < nact && ng >= th) {
+            region(rrow, reg::kPassGroup);
+            ++n_groups;
+            count_pass(ng);
+            if constexpr (kStats) credit(pt.group_entries, min(ng, nact));
+            if (kGroupPassDouble && ng >= nact + th) {
+                region(rrow, reg::kPassGroup);
+                region(rrow, reg::kGroupPass2);
+                ++n_groups;
+                count_pass(ng - nact);
+                if constexpr (kStats) credit(pt.group_entries, min(ng - nact, nact));
+                flat_group_pass2<kFmt, kGRec>(ng, nc, nact, rank, lane, ws, tg, my, rrow);
+            } else {
+                flat_pass<1, kFmt, kGRec, 0u, -1, true>(ng, nc, nact, rank, lane, ws, nullptr,
+                                                        nullptr, 0u, tg, my, false, rrow);
+            }
+            if constexpr (kStats) credit(pt.group, ticks() - t0);
+        } else if (nc >= th) {
+            region(rrow, reg::kPassCand);
+            count_pass(nc);
+            flat_pass<0, kFmt, kGRec, 0u, -1, true>(nc, nc, nact, rank, lane, ws, nullptr, nullptr,
+                                                    0u, tg, my, false, rrow);
+            if constexpr (kStats) {
+                credit(pt.cand, ticks() - t0);
+                credit(pt.cand_passes, 1u);
+            }
+        } else {
+            break;
+        }
+    }
+    h.cand = nc;
+    h.group = ng;
 }
 
 // The node mask of one ray from the footprint tables (fact (5); the LDS-table kernel's node
@@ -1518,9 +1661,14 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
                 }
                 ++slice;
             }
-            flat_drain<kStats, kFmt, kGRec, kNS, kSlab, true>(th, nact, rank, lane, ws, h, tbound,
-                                                              tnode, (uint32_t)ncg, tg, my,
-                                                              n_groups, n_bounds, pt, slab, rrow);
+            if constexpr (kGroupPass2)
+                flat_drain_groups<kStats, kFmt, kGRec>(th, nact, rank, lane, ws, h, tg, my,
+                                                       n_groups, pt, rrow);
+            else
+                flat_drain<kStats, kFmt, kGRec, kNS, kSlab, true>(th, nact, rank, lane, ws, h,
+                                                                  tbound, tnode, (uint32_t)ncg, tg,
+                                                                  my, n_groups, n_bounds, pt, slab,
+                                                                  rrow);
             if (th == 1u) break;
         }
     } else {
