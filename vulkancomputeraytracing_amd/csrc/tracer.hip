@@ -449,6 +449,29 @@ __device__ __forceinline__ bool may_hit(float hb, float cc, float disc) {
     return !(disc < 0.0f) && (hb < 0.0f || cc < 0.0f);
 }
 
+// Sign bit set when a member may be accepted: disc >= 0 and (hb < 0 or cc < 0), by sign bits
+// (a -0 hb only adds a candidate that the exact test then rejects; disc is never -0).
+__device__ __forceinline__ float hit_sign(float hb, float cc, float disc) {
+    return __uint_as_float((__float_as_uint(hb) | __float_as_uint(cc)) & ~__float_as_uint(disc));
+}
+
+// The big list's may-hit tests by sign bits (kBigSign: big_roots below) and its test in one
+// basic block with the first group apart from the loop (kBigPeel). With kBigPeel the second pair
+// of a big group is tested whether or not it has members: a padding member (centre 0,
+// r^2 = -3e38; the camera-relative record is computed from the same words) has cc = |o|^2 + 3e38,
+// finite, and hb^2 <= 1.001 a |o|^2 < a cc, so its disc is negative or -inf, never NaN, and
+// neither predicate accepts it -- as for the padding of the first pair and of the hierarchy's
+// groups, which were always tested. Without the wave-uniform branch on the member indices the
+// splat pairs {o.x, o.x} ... {a, a} and their uses share a block, where instruction selection
+// folds them into op_sel_hi (no v_mov pairs), and the 80-B record is one scalar load.
+// For A/B runs only: -DVCRT_BIG_SIGN=0 builds may_hit's float compares, the branch and the
+// callers' plain loops, =2 the sign bits alone, =3 the one-block test and peeled callers alone.
+#ifndef VCRT_BIG_SIGN
+#define VCRT_BIG_SIGN 1
+#endif
+constexpr bool kBigSign = VCRT_BIG_SIGN == 1 || VCRT_BIG_SIGN == 2;
+constexpr bool kBigPeel = VCRT_BIG_SIGN == 1 || VCRT_BIG_SIGN == 3;
+
 // pair_disc that also returns cc = |oc|^2 - r^2 (for may_hit).
 __device__ __forceinline__ void pair_disc_cc(const v2f ox, const v2f oy, const v2f oz,
                                              const v2f dx, const v2f dy, const v2f dz,
@@ -603,6 +626,53 @@ __device__ __forceinline__ uint32_t bound_pair_need(const BoxRay& r, const Bound
     return nonzero(n0) | (nonzero(n1) << 1);
 }
 
+// The roots of the big list's members (exact_group_uniform, exact_group_uniform_cam with
+// kBigSign), entered by hit_sign's sign bits h0..h3 in place of may_hit's float compares (which
+// cost two NaN-quieting v_max, a v_min and two v_cmp per member, and as many again for the gate's
+// max of the four disc: one v_bitop3 and one integer compare per member here).
+// Exactness: hit_sign's sign bit is may_hit except where hb = -0. cc is never -0 (a difference of
+// unequal numbers, or +0 under round-to-nearest) and disc neither (hb^2 - a cc: +0 or a nonzero
+// value); disc is finite for a ray of the guarded range (|hb| < 2^63, a |cc| < 2^123; a padding
+// member's is -inf, sign set), which both callers' rays are, so no NaN's sign bit is read.
+// With hb = -0 and cc >= 0 the bit is set where may_hit is false; if also disc >= 0 then
+// disc = RN(0 - RN(a cc)) >= 0 forces RN(a cc) = 0 (cc = 0, or a product that underflows) and
+// disc = +0, so sq = 0 and candidate_t_fast's roots are div_a(-hb - 0, a, ya) = (+0) ya = 0 and
+// div_a(-hb + 0, a, ya) = 0: both <= kMinT (tests/test_big_sign_cpu.py), and
+// `consider` (take only if t > kMinT) rejects them: max_t and best are may_hit's. (hb = -0 with
+// cc < 0: both forms accept.) The gate, "some member may hit", is tighter than the old "some disc
+// >= 0", which it implies: fewer entries of the block, the same entries of each member.
+// A missing second pair takes hb = cc = 0, disc = -1: (0 | 0) & ~bits(-1) = 0, sign clear.
+__device__ __forceinline__ void big_roots(float h0, float h1, float h2, float h3, v2f hb01,
+                                          v2f d01, v2f hb23, v2f d23, float4 idf, float a,
+                                          float ya, float& max_t, int& best, uint32_t* rrow,
+                                          uint32_t rb) {
+    const uint32_t any = (__float_as_uint(h0) | __float_as_uint(h1)) |
+                         (__float_as_uint(h2) | __float_as_uint(h3));
+    if (__ballot((int)any < 0)) {
+        region(rrow, rb);
+        if (__float_as_int(h0) < 0) {
+            region(rrow, rb + 1);
+            consider(candidate_t_fast(hb01.x, d01.x, a, ya, rrow), __float_as_int(idf.x), max_t,
+                     best);
+        }
+        if (__float_as_int(h1) < 0) {
+            region(rrow, rb + 2);
+            consider(candidate_t_fast(hb01.y, d01.y, a, ya, rrow), __float_as_int(idf.y), max_t,
+                     best);
+        }
+        if (__float_as_int(h2) < 0) {
+            region(rrow, rb + 3);
+            consider(candidate_t_fast(hb23.x, d23.x, a, ya, rrow), __float_as_int(idf.z), max_t,
+                     best);
+        }
+        if (__float_as_int(h3) < 0) {
+            region(rrow, rb + 4);
+            consider(candidate_t_fast(hb23.y, d23.y, a, ya, rrow), __float_as_int(idf.w), max_t,
+                     best);
+        }
+    }
+}
+
 // The exact test of one group for every lane (wave-uniform scalar loads of the 80-B record):
 // the big-sphere list, tested for every ray ahead of the hierarchy.
 __device__ __forceinline__ void exact_group_uniform(cfloat4* rec, const CullRay& r, v2f dx, v2f dy,
@@ -612,9 +682,15 @@ __device__ __forceinline__ void exact_group_uniform(cfloat4* rec, const CullRay&
     const float4 q0 = rec[0], q1 = rec[1], idf = rec[4];
     v2f hb01, cc01, d01, hb23 = {0.f, 0.f}, cc23 = {0.f, 0.f}, d23 = {-1.f, -1.f};
     pair_disc_cc(r.ox, r.oy, r.oz, dx, dy, dz, a2, q0, q1, hb01, cc01, d01);
-    // members 2 and 3 only when the group has them (wave-uniform)
-    if (__float_as_int(idf.z) >= 0 || __float_as_int(idf.w) >= 0)
+    // members 2 and 3 only when the group has them (wave-uniform); kBigPeel: always (above)
+    if (kBigPeel || __float_as_int(idf.z) >= 0 || __float_as_int(idf.w) >= 0)
         pair_disc_cc(r.ox, r.oy, r.oz, dx, dy, dz, a2, rec[2], rec[3], hb23, cc23, d23);
+    if constexpr (kBigSign) {
+        big_roots(hit_sign(hb01.x, cc01.x, d01.x), hit_sign(hb01.y, cc01.y, d01.y),
+                  hit_sign(hb23.x, cc23.x, d23.x), hit_sign(hb23.y, cc23.y, d23.y), hb01, d01,
+                  hb23, d23, idf, a, ya, max_t, best, rrow, rb);
+        return;
+    }
     const float m4 = fmaxf(fmaxf(d01.x, d01.y), fmaxf(d23.x, d23.y));
     if (__ballot(!(m4 < 0.0f))) {
         region(rrow, rb);
@@ -651,8 +727,14 @@ __device__ __forceinline__ void exact_group_uniform_cam(cfloat4* crec, cfloat4* 
     const float4 c0 = crec[0], c1 = crec[1], idf = rec[4];
     v2f hb01, cc01, d01, hb23 = {0.f, 0.f}, cc23 = {0.f, 0.f}, d23 = {-1.f, -1.f};
     pair_disc_cam(dx, dy, dz, a2, c0, c1, hb01, cc01, d01);
-    if (__float_as_int(idf.z) >= 0 || __float_as_int(idf.w) >= 0)
+    if (kBigPeel || __float_as_int(idf.z) >= 0 || __float_as_int(idf.w) >= 0)
         pair_disc_cam(dx, dy, dz, a2, crec[2], crec[3], hb23, cc23, d23);
+    if constexpr (kBigSign) {
+        big_roots(hit_sign(hb01.x, cc01.x, d01.x), hit_sign(hb01.y, cc01.y, d01.y),
+                  hit_sign(hb23.x, cc23.x, d23.x), hit_sign(hb23.y, cc23.y, d23.y), hb01, d01,
+                  hb23, d23, idf, a, ya, max_t, best, rrow, rb);
+        return;
+    }
     const float m4 = fmaxf(fmaxf(d01.x, d01.y), fmaxf(d23.x, d23.y));
     if (__ballot(!(m4 < 0.0f))) {
         region(rrow, rb);
@@ -874,12 +956,6 @@ __device__ __forceinline__ uint32_t push_bound_pairs4_nf(const BoxRay& r, const 
         for (int k = 3; k >= 0; k--) out = push_bound_pair_nf<false>(out, r, a, 80 * k);
     }
     return out;
-}
-
-// Sign bit set when a member may be accepted: disc >= 0 and (hb < 0 or cc < 0), by sign bits
-// (a -0 hb only adds a candidate that the exact test then rejects; disc is never -0).
-__device__ __forceinline__ float hit_sign(float hb, float cc, float disc) {
-    return __uint_as_float((__float_as_uint(hb) | __float_as_uint(cc)) & ~__float_as_uint(disc));
 }
 
 // ---- flattened scan (variant CULL_FLAT) ------------------------------------------------------
@@ -1516,9 +1592,33 @@ __device__ __forceinline__ void scan_culled_flat(const TraceParams& p, const flo
     r.oz = (v2f){o.z, o.z};
     {
         const v2f dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z}, a2 = {my.a, my.a};
+        if constexpr (kBigPeel) {
+            // The first group apart from the loop (the generated scenes have one): ahead of a
+            // loop with a run-time trip count the compiler copies every splat pair, max_t and
+            // best into registers of the loop's own (13 v_mov); the peeled test, one basic block
+            // (kBigPeel above), reads the ray's scalars through op_sel_hi, as the group passes do.
+            // The further groups' loop takes the scalars through an empty asm, so that its pairs
+            // are values of its own: one pair shared by both would again be built ahead of both.
+            if (p.nbig > 0) {
+                exact_group_uniform((cfloat4*)p.cgroup, r, dx, dy, dz, a2, my.a, my.ya, max_t,
+                                    best, rrow, reg::kMainBig);
+                if (p.nbig > 1) {
+                    float lox = o.x, loy = o.y, loz = o.z, ldx = d.x, ldy = d.y, ldz = d.z;
+                    float la = my.a;
+                    asm("" : "+v"(lox), "+v"(loy), "+v"(loz), "+v"(ldx), "+v"(ldy), "+v"(ldz),
+                        "+v"(la));
+                    const CullRay lr = {{lox, lox}, {loy, loy}, {loz, loz}};
+                    const v2f ex = {ldx, ldx}, ey = {ldy, ldy}, ez = {ldz, ldz}, ea = {la, la};
+                    for (int gb = 1; gb < p.nbig; ++gb)
+                        exact_group_uniform((cfloat4*)p.cgroup + 5 * gb, lr, ex, ey, ez, ea, la,
+                                            my.ya, max_t, best, rrow, reg::kMainBig);
+                }
+            }
+        } else {
         for (int gb = 0; gb < p.nbig; ++gb)  // the big spheres, for every ray (scalar loads)
             exact_group_uniform((cfloat4*)p.cgroup + 5 * gb, r, dx, dy, dz, a2, my.a, my.ya, max_t,
                                 best, rrow, reg::kMainBig);
+        }
     }
     if constexpr (kStats) credit(pt.big, ticks() - t_in);
     uint32_t n_bounds = 0, n_groups = (uint32_t)p.nbig;
@@ -2737,9 +2837,21 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                     cfloat4* crec = (cfloat4*)P.cam_rec;
                     const float ya = recip_a(aa);
                     const v2f dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z}, a2 = {aa, aa};
+                    if constexpr (kBigPeel) {  // the first group apart (see scan_culled_flat)
+                        if (P.nbig > 0) {
+                            exact_group_uniform_cam(crec, (cfloat4*)P.cgroup, dx, dy, dz, a2, aa,
+                                                    ya, mt, bst, rrow, reg::kCamBig);
+                            for (int gb = 1; gb < P.nbig; ++gb) {  // the further groups
+                                exact_group_uniform_cam(crec + 4 * gb, (cfloat4*)P.cgroup + 5 * gb,
+                                                        dx, dy, dz, a2, aa, ya, mt, bst, rrow,
+                                                        reg::kCamBig);
+                            }
+                        }
+                    } else {
                     for (int gb = 0; gb < P.nbig; ++gb)  // the big spheres (scalar loads)
                         exact_group_uniform_cam(crec + 4 * gb, (cfloat4*)P.cgroup + 5 * gb, dx, dy,
                                                 dz, a2, aa, ya, mt, bst, rrow, reg::kCamBig);
+                    }
                     // the quarter's listed spheres, two per record (primary.cpp): the exact
                     // test's may-hit bits are collected first (bit 2k + s)...
                     const uint32_t cnt = inf & 15u;
