@@ -25,5 +25,8 @@ VkResult SetRenderScene(IN const vcrt_sphere* spheres, IN int32_t count);
 VkResult ReadFramebuffer(OUT float* rgba, IN size_t count);
 // Moves the camera of the running renderer (vcrt_set_camera); a later Begin starts from it too.
 VkResult SetRenderCamera(IN const vcrt_camera* camera);
+// Moves the spheres of the running renderer (vcrt_update_spheres: same count, the tables refitted
+// on the GPU); a later Begin starts from the new values too.
+VkResult UpdateSpheres(IN const vcrt_sphere* spheres, IN int32_t count);
 
 #endif

@@ -23,7 +23,9 @@
  * (vcrt_occlude_rays: is anything in the way within a per-ray reach); a thin lens for the
  * frames' camera (vcrt_render_desc.lens_radius, vcrt_lens_offsets); a camera that moves between
  * frames without a new vcrt_begin (vcrt_set_camera: the camera-ray lists are rebuilt on the GPU;
- * vcrt_get_camera_stats, vcrt_camera_lists_read).
+ * vcrt_get_camera_stats, vcrt_camera_lists_read); spheres that move between frames without a new
+ * vcrt_set_scene (vcrt_update_spheres: the scene's grouping is kept and its tables are refitted
+ * on the GPU; vcrt_get_scene_update_stats, vcrt_scene_table_host / _read).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -322,6 +324,102 @@ typedef struct vcrt_camera_stats {
     uint64_t pair_records;  /* pair records of the sphere lists */
 } vcrt_camera_stats;
 vcrt_result vcrt_get_camera_stats(vcrt_camera_stats* stats);
+
+/* Moves the spheres between frames (added): the whole array replaces the current scene's values
+ * -- centres, radii, colours and materials -- at the cost of a few small kernels, not of
+ * vcrt_set_scene. `count` must equal the current scene's (VCRT_ERROR_FORMAT_NOT_SUPPORTED
+ * otherwise, nothing changed); before vcrt_begin, or for NULL with count > 0,
+ * VCRT_ERROR_INITIALIZATION_FAILED before anything touches the GPU. vcrt_update_spheres takes a
+ * host pointer; vcrt_update_spheres_device a device pointer (40 B per sphere, readable on the
+ * renderer's device), waits on nothing but the render stream and returns when done.
+ * Every later frame and every later vcrt_trace_rays / vcrt_occlude_rays gives, bit for bit, the
+ * result of a fresh renderer -- vcrt_begin with the same description and the current camera,
+ * then vcrt_set_scene(spheres, count) -- vcrt_stats.segments included. vcrt_stats.kernel follows
+ * the refitted tables and may differ from the fresh renderer's.
+ * Kept: the device, stream and code object, the framebuffers, the communicator, every scene
+ * buffer and the scene's grouping: the members of the big list and of every hierarchy group
+ * (the index words of the group records). Rewritten in place, on the GPU by the kernels of
+ * csrc/scene_update.hip: the linear scan table, the per-sphere rows, the group records' geometry,
+ * the group, node and chunk boxes in both layouts, the node and group footprint tables, and --
+ * through vcrt_set_camera's list kernels -- both camera-ray lists and the camera-relative
+ * records. Recomputed on the host from a summary the kernels reduce (one small read-back): the
+ * box margins, the shared y slab, the footprint scalars and the kernel selection. Reset:
+ * progressive accumulation restarts at sample 0 and the measured cost order is dropped. Once the
+ * kept buffers exist the call allocates and frees no device memory.
+ * The grouping does not follow the spheres: the boxes are the members' boxes wherever the members
+ * go, so the culled scans stay exact, but after large moves the boxes grow and overlap and frames
+ * get slower, never wrong. vcrt_set_scene remains the rebuild: call it when the scene has moved
+ * far from where it was grouped.
+ * When the refit does not apply, the call does what vcrt_set_scene does with the new values (the
+ * device variant first copies them to the host) and reports rebuilt = 1: a renderer without
+ * culling tables (fewer than 16 spheres, or an unbounded scene), a new centre or radius that
+ * fails |v| <= 2^30 (NaN included), or a code object without the refit kernels (an A/B build of
+ * an older tree). VCRT_SCENE_UPDATE=host in the environment refits on the host instead
+ * (vcrt_scene_table_host's function) and uploads into the kept buffers (A/B runs and tests).
+ * Local, not collective, like vcrt_set_camera. */
+vcrt_result vcrt_update_spheres(const vcrt_sphere* spheres, int32_t count);
+vcrt_result vcrt_update_spheres_device(const vcrt_sphere* spheres, int32_t count);
+
+/* The last vcrt_update_spheres[_device] (all zero before the first). */
+typedef struct vcrt_scene_update_stats {
+    double   host_ms;          /* wall time of the call */
+    double   refit_ms;         /* HIP events around the refit kernels and the summary's read-back;
+                                  0 when the host refitted or the scene was rebuilt */
+    double   lists_ms;         /* the camera-list kernels (vcrt_camera_stats.lists_ms); 0: none */
+    int32_t  on_device;        /* 1: the refit kernels wrote the tables */
+    int32_t  rebuilt;          /* 1: the refit did not apply; the call ran vcrt_set_scene */
+    uint64_t groups;           /* group records rewritten (big groups included) */
+    uint64_t boxes;            /* group, node and chunk boxes rewritten */
+    uint64_t footprint_cells;  /* cells of the node and group footprint tables rewritten */
+} vcrt_scene_update_stats;
+vcrt_result vcrt_get_scene_update_stats(vcrt_scene_update_stats* stats);
+
+/* Diagnostics: one device table of a scene, as bytes in the device's layout. */
+#define VCRT_TABLE_LINEAR        0  /* the linear scan table, padding and prefetch group included */
+#define VCRT_TABLE_CENTER_RADIUS 1  /* [count][4] */
+#define VCRT_TABLE_SHADE         2  /* [count][4] */
+#define VCRT_TABLE_MATERIAL      3  /* [count][4] */
+#define VCRT_TABLE_GROUPS        4  /* [big + hierarchy groups][20]: geometry, 4 index words */
+#define VCRT_TABLE_BOUND         5  /* group-pair boxes, pair-SoA */
+#define VCRT_TABLE_BOUND_NF      6  /* the same, near/far layout */
+#define VCRT_TABLE_NODE          7
+#define VCRT_TABLE_NODE_NF       8  /* padded to whole chunks */
+#define VCRT_TABLE_TOP           9
+#define VCRT_TABLE_FOOT         10  /* the node footprint tables, packed as the kernel reads them */
+#define VCRT_TABLE_GROUP_FOOT   11
+#define VCRT_TABLE_SCALARS      12  /* a vcrt_scene_scalars */
+typedef struct vcrt_scene_scalars {
+    int32_t  nbig, ngroups;
+    float    margin[4];
+    int32_t  slab_on;
+    float    slab[2];
+    float    fp_x[2], fp_z[2], fp_y[2], fp_k2;
+    uint32_t fp_always;
+    uint32_t gf_n;
+    float    gf_x[2], gf_z[2], gf_k2;
+    uint32_t gf_always[4];
+    int32_t  gf_ok;
+    int32_t  bounded, radii_safe;
+} vcrt_scene_scalars;
+/* The bytes of one device table as a refit computes them on the host: the grouping
+ * vcrt_set_scene(grouping_of) chooses, filled with the values of `values` (same count; with
+ * values == grouping_of exactly what vcrt_set_scene uploads). Returns the size in bytes (writes
+ * when cap suffices), 0 when the table does not exist (no culling tables; no group footprint). */
+int64_t vcrt_scene_table_host(const vcrt_sphere* grouping_of, const vcrt_sphere* values,
+                              int32_t count, int32_t table, void* buf, size_t cap);
+/* The same table copied back from the renderer's device buffers, whoever wrote it (a negative
+ * VkResult before vcrt_begin). */
+int64_t vcrt_scene_table_read(int32_t table, void* buf, size_t cap);
+
+/* vcrt_primary_lists / vcrt_primary_sphere_lists (below) over refitted tables: the grouping of
+ * `grouping_of` filled with the values of `spheres`, as vcrt_scene_table_host. */
+int32_t vcrt_refit_primary_lists(const vcrt_sphere* grouping_of, const vcrt_sphere* spheres,
+                                 int32_t count, const vcrt_render_desc* desc, uint32_t* info,
+                                 int32_t cap_tiles, uint16_t* ids, int32_t cap_ids);
+int32_t vcrt_refit_primary_sphere_lists(const vcrt_sphere* grouping_of, const vcrt_sphere* spheres,
+                                        int32_t count, const vcrt_render_desc* desc,
+                                        uint32_t* info, int32_t cap_tiles, float* rec,
+                                        int32_t cap_floats);
 
 /* Diagnostic: the camera-ray lists the next frame will use, copied back from the device in the
  * form of the two host functions below (vcrt_primary_lists: group_info, ids;

@@ -149,6 +149,60 @@ class vcrt_camera_stats(ctypes.Structure):
     ]
 
 
+class vcrt_scene_update_stats(ctypes.Structure):
+    _fields_ = [
+        ("host_ms", ctypes.c_double),
+        ("refit_ms", ctypes.c_double),
+        ("lists_ms", ctypes.c_double),
+        ("on_device", ctypes.c_int32),
+        ("rebuilt", ctypes.c_int32),
+        ("groups", ctypes.c_uint64),
+        ("boxes", ctypes.c_uint64),
+        ("footprint_cells", ctypes.c_uint64),
+    ]
+
+
+class vcrt_scene_scalars(ctypes.Structure):
+    _fields_ = [
+        ("nbig", ctypes.c_int32),
+        ("ngroups", ctypes.c_int32),
+        ("margin", ctypes.c_float * 4),
+        ("slab_on", ctypes.c_int32),
+        ("slab", ctypes.c_float * 2),
+        ("fp_x", ctypes.c_float * 2),
+        ("fp_z", ctypes.c_float * 2),
+        ("fp_y", ctypes.c_float * 2),
+        ("fp_k2", ctypes.c_float),
+        ("fp_always", ctypes.c_uint32),
+        ("gf_n", ctypes.c_uint32),
+        ("gf_x", ctypes.c_float * 2),
+        ("gf_z", ctypes.c_float * 2),
+        ("gf_k2", ctypes.c_float),
+        ("gf_always", ctypes.c_uint32 * 4),
+        ("gf_ok", ctypes.c_int32),
+        ("bounded", ctypes.c_int32),
+        ("radii_safe", ctypes.c_int32),
+    ]
+
+
+# VCRT_TABLE_* (vcrt.h): name -> (id, numpy dtype of the table's words)
+SCENE_TABLES = {
+    "linear": (0, "float32"),
+    "center_radius": (1, "float32"),
+    "shade": (2, "float32"),
+    "material": (3, "float32"),
+    "groups": (4, "float32"),
+    "bound": (5, "float32"),
+    "bound_nf": (6, "float32"),
+    "node": (7, "float32"),
+    "node_nf": (8, "float32"),
+    "top": (9, "float32"),
+    "foot": (10, "uint32"),
+    "group_foot": (11, "uint32"),
+    "scalars": (12, "uint8"),
+}
+
+
 class vcrt_comm_id(ctypes.Structure):
     _fields_ = [("internal", ctypes.c_char * 128)]  # an ncclUniqueId
 
@@ -183,6 +237,12 @@ SIGNATURES = {
                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                                 ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(ctypes.c_int32)]),
+    "vcrt_update_spheres": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
+    "vcrt_update_spheres_device": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
+    "vcrt_get_scene_update_stats": (ctypes.c_int32, [ctypes.POINTER(vcrt_scene_update_stats)]),
+    "vcrt_scene_table_host": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t]),
+    "vcrt_scene_table_read": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t]),
     "vcrt_read_framebuffer_srgb8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_size_t]),
     "vcrt_selftest_sin": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.POINTER(ctypes.c_uint64),
@@ -223,6 +283,15 @@ SIGNATURES = {
                                                    ctypes.POINTER(vcrt_render_desc),
                                                    ctypes.c_void_p, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_int32]),
+    "vcrt_refit_primary_lists": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                  ctypes.POINTER(vcrt_render_desc),
+                                                  ctypes.c_void_p, ctypes.c_int32,
+                                                  ctypes.c_void_p, ctypes.c_int32]),
+    "vcrt_refit_primary_sphere_lists": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_int32,
+                                                         ctypes.POINTER(vcrt_render_desc),
+                                                         ctypes.c_void_p, ctypes.c_int32,
+                                                         ctypes.c_void_p, ctypes.c_int32]),
     "vcrt_lens_offsets": (ctypes.c_int32, [ctypes.POINTER(vcrt_render_desc), ctypes.c_uint32,
                                            ctypes.c_uint32, ctypes.c_void_p]),
     "vcrt_canonical_sin": (ctypes.c_float, [ctypes.c_float]),

@@ -57,3 +57,9 @@ VkResult SetRenderCamera(IN const vcrt_camera* camera) {
     if (r == VK_SUCCESS && g_desc_set) g_desc.camera = *camera;
     return r;
 }
+
+VkResult UpdateSpheres(IN const vcrt_sphere* spheres, IN int32_t count) {
+    const VkResult r = vcrt_update_spheres(spheres, count);
+    if (r == VK_SUCCESS && g_scene_set) g_scene.assign(spheres, spheres + count);
+    return r;
+}

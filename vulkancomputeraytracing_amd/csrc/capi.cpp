@@ -28,6 +28,7 @@
 #include "comm_wait.hpp"
 #include "hip_status.hpp"
 #include "scene.hpp"
+#include "scene_update_abi.h"
 #include "vcrt.h"
 #include "vcrt_kernel_abi.h"
 #include "vcrt_math.h"
@@ -166,6 +167,19 @@ struct RendererState {
     uint32_t* h_cl_totals = nullptr;  // pinned [2]
     hipEvent_t ev_cl[2] = {nullptr, nullptr};
     vcrt_camera_stats cam_stats{};
+    // vcrt_update_spheres: the refit kernels (scene_update.hip; null: the code object predates
+    // them), the staged spheres, the summary and its pinned copy; kept and grown only
+    hipFunction_t k_su_rows = nullptr, k_su_groups = nullptr, k_su_levels = nullptr,
+                  k_su_footprint = nullptr;
+    float* d_su_spheres = nullptr;
+    size_t su_spheres_cap = 0;  // floats
+    vcrt::SceneSummary* d_su_summary = nullptr;
+    vcrt::SceneSummary* h_su_summary = nullptr;  // pinned
+    hipEvent_t ev_su[2] = {nullptr, nullptr};
+    vcrt_scene_update_stats su_stats{};
+    // h_ct holds the grouping but not yet the tables of h_spheres: the device refit leaves them
+    // on the device, and current_tables() restates them when the host needs them
+    bool h_ct_stale = false;
     // work decomposition
     int32_t quantum = 1;  // the accumulation quantum G (a power of two)
     int32_t chunk = 1, nchunks = 1;
@@ -505,9 +519,8 @@ std::vector<uint32_t> pack_footprint(const vcrt::CullTables& ct) {
 }
 
 // A pair-SoA box table (cluster.hpp: 16 floats per pair of boxes) in the near/far layout of
-// TraceParams.cbound_nf (20 floats per pair: per axis lo0 lo1 hi0 hi1 lo0 lo1, then K0 K1),
-// uploaded to a new device buffer.
-hipError_t upload_near_far(const std::vector<float>& pairs, float4** out) {
+// TraceParams.cbound_nf (20 floats per pair: per axis lo0 lo1 hi0 hi1 lo0 lo1, then K0 K1).
+std::vector<float> near_far(const std::vector<float>& pairs) {
     const size_t n = pairs.size() / 16;
     std::vector<float> nf(n * 20);
     for (size_t i = 0; i < n; i++) {
@@ -522,9 +535,76 @@ hipError_t upload_near_far(const std::vector<float>& pairs, float4** out) {
         o[18] = b[12];
         o[19] = b[13];
     }
+    return nf;
+}
+
+// the flat scan's chunk passes read a chunk's 4 node pairs: the node table padded to whole chunks
+std::vector<float> node_near_far(const vcrt::CullTables& ct) {
+    std::vector<float> nodes = ct.node;
+    const size_t pairs = nodes.size() / 16, padded = (pairs + 3) / 4 * 4;
+    nodes.resize(padded * 16, 0.0f);
+    return near_far(nodes);
+}
+
+hipError_t upload_near_far(const std::vector<float>& nf, float4** out) {
     hipError_t e = hipMalloc(out, sizeof(float) * nf.size());
     if (e != hipSuccess) return e;
     return hipMemcpy(*out, nf.data(), sizeof(float) * nf.size(), hipMemcpyHostToDevice);
+}
+
+// The linear scan table of a scene (vcrt_set_scene): count / 4 groups rounded up, one more for
+// the prefetch, padding entries (0, 0, 0, r² = -3e38).
+std::vector<float> linear_table(const vcrt_sphere* spheres, int32_t count) {
+    const int32_t ngroups = (count + 3) / 4;
+    std::vector<float> table(static_cast<size_t>(ngroups + 1) * 16, 0.0f);
+    for (int32_t j = 0; j < 4 * (ngroups + 1); j++) {
+        float* gq = &table[static_cast<size_t>(j / 4) * 16];
+        const int pair = (j % 4) / 2, e = j % 2;
+        float cx = 0.f, cy = 0.f, cz = 0.f, r2 = -3.0e38f;
+        if (j < count) {
+            const vcrt_sphere& sp = spheres[j];
+            cx = sp.center[0];
+            cy = sp.center[1];
+            cz = sp.center[2];
+            r2 = sp.radius * sp.radius;
+        }
+        float* base = gq + 8 * pair;
+        base[0 + e] = cx;
+        base[2 + e] = cy;
+        base[4 + e] = cz;
+        base[6 + e] = r2;
+    }
+    return table;
+}
+
+// The per-sphere rows: (centre, radius), (colour, param), (material id, 1 / param, r0², 0).
+void sphere_rows(const vcrt_sphere* spheres, int32_t count, std::vector<float4>& cr,
+                 std::vector<float4>& shade, std::vector<float4>& mat) {
+    cr.resize(count);
+    shade.resize(count);
+    mat.resize(count);
+    for (int32_t i = 0; i < count; i++) {
+        const vcrt_sphere& sp = spheres[i];
+        cr[i] = make_float4(sp.center[0], sp.center[1], sp.center[2], sp.radius);
+        shade[i] = make_float4(sp.colour[0], sp.colour[1], sp.colour[2], sp.texture[1]);
+        // the glass scatter's two per-sphere quotients (textures.glsl:49-50, functions.glsl:58-60),
+        // fp32 and correctly rounded as the kernel would compute them
+        const float ior = sp.texture[1];
+        float r0 = (1.0f - ior) / (1.0f + ior);
+        r0 = r0 * r0;
+        mat[i] = make_float4(sp.texture[0], 1.0f / ior, r0, 0.0f);
+    }
+}
+
+// group records: the four pair-SoA float4s + the member indices (int bits); big groups first
+std::vector<float> group_records(const vcrt::CullTables& ct) {
+    const int32_t nall = ct.nbig + ct.ngroups;
+    std::vector<float> rec(static_cast<size_t>(nall) * 20);
+    for (int32_t gi = 0; gi < nall; gi++) {
+        std::memcpy(&rec[gi * 20], &ct.geom[gi * 16], 16 * sizeof(float));
+        std::memcpy(&rec[gi * 20 + 16], &ct.index[gi * 4], 4 * sizeof(int32_t));
+    }
+    return rec;
 }
 
 // hipModuleGetFunction of a required entry point: a code object without it (e.g. an A/B build of
@@ -607,6 +687,17 @@ VkResult bind_kernels() {
         {&g.k_cl_scan, "vcrt_camlist_scan"},
         {&g.k_cl_fill, "vcrt_camlist_fill"}};
     for (const auto& [fp, name] : list_kernels)
+        if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
+            (void)hipGetLastError();
+            *fp = nullptr;
+        }
+    // optional: the scene-refit kernels (vcrt_update_spheres then rebuilds as vcrt_set_scene)
+    const std::pair<hipFunction_t*, const char*> refit_kernels[] = {
+        {&g.k_su_rows, "vcrt_scene_rows"},
+        {&g.k_su_groups, "vcrt_scene_groups"},
+        {&g.k_su_levels, "vcrt_scene_levels"},
+        {&g.k_su_footprint, "vcrt_scene_footprint"}};
+    for (const auto& [fp, name] : refit_kernels)
         if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
             (void)hipGetLastError();
             *fp = nullptr;
@@ -1072,6 +1163,33 @@ VkResult install_camera_lists(const vcrt::CullTables& ct, const vcrt::PrimaryLis
     return VK_SUCCESS;
 }
 
+// The scene's tables on the host: vcrt_set_scene's, or after a device refit the host's
+// restatement of them for the same grouping and the current spheres (equal bytes).
+const vcrt::CullTables& current_tables() {
+    if (g.h_ct_stale) {
+        vcrt::tables_of_grouping(g.h_spheres.data(), static_cast<int32_t>(g.h_spheres.size()),
+                                 g.h_ct);
+        g.h_ct_stale = false;
+    }
+    return g.h_ct;
+}
+
+// The lists of the current scene and camera from the host builders, installed.
+VkResult build_camera_lists_host() {
+    const vcrt::CullTables& ct = current_tables();
+    vcrt::PrimaryLists pl;
+    vcrt::build_primary_lists(ct, camera_array().data(), g.desc.width, g.desc.height, g.desc.rank,
+                              g.desc.world_size, pl);
+    vcrt::PrimarySphereLists sl;
+    vcrt::build_primary_sphere_lists(ct, g.h_spheres.data(), camera_array().data(), g.desc.width,
+                                     g.desc.height, g.desc.rank, g.desc.world_size, sl);
+    const VkResult r = install_camera_lists(ct, pl, sl);
+    if (r != VK_SUCCESS) return r;
+    // (the uploads ran on the null stream; the render stream does not wait for it)
+    VCRT_TRY(hipStreamSynchronize(nullptr));
+    return VK_SUCCESS;
+}
+
 // The same lists built on the device (camera_lists.hip) from the tables vcrt_set_scene uploaded,
 // on the render stream: prepare, count, scan; the two totals come back (8 bytes) to size the
 // buffers; fill. The per-camera scalars are QuarterWalker's (primary.cpp), evaluated here once.
@@ -1424,50 +1542,15 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
     // r² = radius*radius as hit_sphere computes it (functions.glsl:18). The last group is
     // padded with far-away empty spheres and one extra group follows for the prefetch; the
     // kernel never accepts a padding index anyway.
-    const int32_t ngroups = (count + 3) / 4;
-    std::vector<float> table(static_cast<size_t>(ngroups + 1) * 16, 0.0f);
-    for (int32_t j = 0; j < 4 * (ngroups + 1); j++) {
-        float* gq = &table[static_cast<size_t>(j / 4) * 16];
-        const int pair = (j % 4) / 2, e = j % 2;
-        float cx = 0.f, cy = 0.f, cz = 0.f, r2 = -3.0e38f;
-        if (j < count) {
-            const vcrt_sphere& sp = spheres[j];
-            cx = sp.center[0];
-            cy = sp.center[1];
-            cz = sp.center[2];
-            r2 = sp.radius * sp.radius;
-        }
-        float* base = gq + 8 * pair;
-        base[0 + e] = cx;
-        base[2 + e] = cy;
-        base[4 + e] = cz;
-        base[6 + e] = r2;
-    }
-    std::vector<float4> cr(count), shade(count);
-    std::vector<float4> mat(count);
-    for (int32_t i = 0; i < count; i++) {
-        const vcrt_sphere& sp = spheres[i];
-        cr[i] = make_float4(sp.center[0], sp.center[1], sp.center[2], sp.radius);
-        shade[i] = make_float4(sp.colour[0], sp.colour[1], sp.colour[2], sp.texture[1]);
-        // the glass scatter's two per-sphere quotients (textures.glsl:49-50, functions.glsl:58-60),
-        // fp32 and correctly rounded as the kernel would compute them
-        const float ior = sp.texture[1];
-        float r0 = (1.0f - ior) / (1.0f + ior);
-        r0 = r0 * r0;
-        mat[i] = make_float4(sp.texture[0], 1.0f / ior, r0, 0.0f);
-    }
+    const std::vector<float> table = linear_table(spheres, count);
+    std::vector<float4> cr, shade, mat;
+    sphere_rows(spheres, count, cr, shade, mat);
     vcrt::CullTables ct;
     vcrt::build_cull_tables(spheres, count, ct);
     (void)hipStreamSynchronize(g.stream);
     free_scene();
     if (ct.ngroups > 0) {
-        // group records: the four pair-SoA float4s + the member indices (int bits)
-        const int32_t nall = ct.nbig + ct.ngroups;  // big-sphere groups first
-        std::vector<float> rec(static_cast<size_t>(nall) * 20);
-        for (int32_t gi = 0; gi < nall; gi++) {
-            std::memcpy(&rec[gi * 20], &ct.geom[gi * 16], 16 * sizeof(float));
-            std::memcpy(&rec[gi * 20 + 16], &ct.index[gi * 4], 4 * sizeof(int32_t));
-        }
+        const std::vector<float> rec = group_records(ct);
         VCRT_TRY(hipMalloc(&g.d_cgroup, sizeof(float) * rec.size()));
         VCRT_TRY(hipMalloc(&g.d_cbound, sizeof(float) * ct.bound.size()));
         VCRT_TRY(hipMalloc(&g.d_cnode, sizeof(float) * ct.node.size()));
@@ -1479,14 +1562,8 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
         VCRT_TRY(hipMemcpy(g.d_cbound, ct.bound.data(), sizeof(float) * ct.bound.size(),
                            hipMemcpyHostToDevice));
         // near/far layout of the group boxes for the flat scan (vcrt_kernel_abi.h, cbound_nf)
-        VCRT_TRY(upload_near_far(ct.bound, &g.d_cbound_nf));
-        {
-            // the flat scan's chunk passes read a chunk's 4 node pairs: pad to whole chunks
-            std::vector<float> nodes = ct.node;
-            const size_t pairs = nodes.size() / 16, padded = (pairs + 3) / 4 * 4;
-            nodes.resize(padded * 16, 0.0f);
-            VCRT_TRY(upload_near_far(nodes, &g.d_cnode_nf));
-        }
+        VCRT_TRY(upload_near_far(near_far(ct.bound), &g.d_cbound_nf));
+        VCRT_TRY(upload_near_far(node_near_far(ct), &g.d_cnode_nf));
         VCRT_TRY(hipMemcpy(g.d_cnode, ct.node.data(), sizeof(float) * ct.node.size(),
                            hipMemcpyHostToDevice));
         g.ncgroups = ct.ngroups;
@@ -1560,6 +1637,7 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
     g.stats.nspheres = count;
     if (spheres != g.h_spheres.data()) g.h_spheres.assign(spheres, spheres + count);
     g.h_ct = std::move(ct);
+    g.h_ct_stale = false;
     if (g.desc.progressive && g.accumulated > 0) {
         // a new scene restarts progressive accumulation at sample 0: the jitter table holds
         // the last frame's sample indices
@@ -2111,6 +2189,11 @@ vcrt_result vcrt_end(void) {
     if (g.h_cl_totals) (void)hipHostFree(g.h_cl_totals);
     for (int k = 0; k < 2; k++)
         if (g.ev_cl[k]) (void)hipEventDestroy(g.ev_cl[k]);
+    if (g.d_su_spheres) (void)hipFree(g.d_su_spheres);
+    if (g.d_su_summary) (void)hipFree(g.d_su_summary);
+    if (g.h_su_summary) (void)hipHostFree(g.h_su_summary);
+    for (int k = 0; k < 2; k++)
+        if (g.ev_su[k]) (void)hipEventDestroy(g.ev_su[k]);
     DestroyShaderStage(&g.stage);
     if (g.ev_start) (void)hipEventDestroy(g.ev_start);
     if (g.ev_stop) (void)hipEventDestroy(g.ev_stop);
@@ -2478,16 +2561,7 @@ vcrt_result vcrt_set_camera(const vcrt_camera* camera) {
         if (device) {
             if ((r = build_camera_lists_device()) != VK_SUCCESS) return r;
         } else {
-            vcrt::PrimaryLists pl;
-            vcrt::build_primary_lists(g.h_ct, camera_array().data(), g.desc.width, g.desc.height,
-                                      g.desc.rank, g.desc.world_size, pl);
-            vcrt::PrimarySphereLists sl;
-            vcrt::build_primary_sphere_lists(g.h_ct, g.h_spheres.data(), camera_array().data(),
-                                             g.desc.width, g.desc.height, g.desc.rank,
-                                             g.desc.world_size, sl);
-            if ((r = install_camera_lists(g.h_ct, pl, sl)) != VK_SUCCESS) return r;
-            // (the uploads ran on the null stream; the render stream does not wait for it)
-            VCRT_TRY(hipStreamSynchronize(nullptr));
+            if ((r = build_camera_lists_host()) != VK_SUCCESS) return r;
         }
         g.cam_stats.on_device = device ? 1 : 0;
         g.cam_stats.quarters = 4ull * g.local_tiles;
@@ -2537,6 +2611,407 @@ int32_t vcrt_camera_lists_read(uint32_t* group_info, uint32_t* sphere_info, int3
                                     static_cast<size_t>(g.ncbig) * 16,
                            sizeof(float) * floats, hipMemcpyDeviceToHost));
     return static_cast<int32_t>(n);
+}
+
+// ---- scene updates ------------------------------------------------------------------------
+
+namespace {
+
+bool values_bounded(const vcrt_sphere* s, int32_t count) {
+    for (int32_t i = 0; i < count; i++)
+        for (float v : {s[i].center[0], s[i].center[1], s[i].center[2], s[i].radius})
+            if (!(std::fabs(v) <= 0x1p30f)) return false;  // also rejects NaN
+    return true;
+}
+
+bool values_radii_safe(const vcrt_sphere* s, int32_t count) {
+    for (int32_t i = 0; i < count; i++)
+        if (!(std::fabs(s[i].radius) >= 0x1p-40f && std::fabs(s[i].radius) <= 0x1p30f))
+            return false;
+    return true;
+}
+
+// The scalars of refitted tables into the renderer's state, as vcrt_set_scene takes them.
+void install_scalars(const vcrt::CullTables& ct, bool bounded, bool radii_safe) {
+    std::memcpy(g.cmargin, ct.margin, sizeof(ct.margin));
+    g.cslab_on = ct.slab;
+    g.cslab[0] = ct.slab_lohi[0];
+    g.cslab[1] = ct.slab_lohi[1];
+    std::memcpy(g.cfp_x, ct.fp_x, sizeof(g.cfp_x));
+    std::memcpy(g.cfp_z, ct.fp_z, sizeof(g.cfp_z));
+    std::memcpy(g.cfp_y, ct.fp_y, sizeof(g.cfp_y));
+    g.cfp_k2 = ct.fp_k2;
+    g.cfp_always = ct.fp_always;
+    if (ct.gf_cells > 0 && g.d_gf_tab != nullptr) {
+        std::memcpy(g.cgf_x, ct.gf_x, sizeof(g.cgf_x));
+        std::memcpy(g.cgf_z, ct.gf_z, sizeof(g.cgf_z));
+        std::memcpy(g.cgf_always, ct.gf_always, sizeof(g.cgf_always));
+        g.cgf_k2 = ct.gf_k2;
+        g.cgf_n = static_cast<uint32_t>(ct.gf_cells);
+        g.cgf_ok = ct.gf_ok;
+    }
+    g.scene_bounded = bounded;
+    g.radii_safe = radii_safe;
+}
+
+vcrt_scene_scalars scalars_struct(const vcrt::CullTables& ct, bool bounded, bool radii_safe) {
+    vcrt_scene_scalars s{};
+    s.nbig = ct.nbig;
+    s.ngroups = ct.ngroups;
+    std::memcpy(s.margin, ct.margin, sizeof(s.margin));
+    s.slab_on = ct.slab ? 1 : 0;
+    std::memcpy(s.slab, ct.slab_lohi, sizeof(s.slab));
+    std::memcpy(s.fp_x, ct.fp_x, sizeof(s.fp_x));
+    std::memcpy(s.fp_z, ct.fp_z, sizeof(s.fp_z));
+    std::memcpy(s.fp_y, ct.fp_y, sizeof(s.fp_y));
+    s.fp_k2 = ct.fp_k2;
+    s.fp_always = ct.fp_always;
+    s.gf_n = static_cast<uint32_t>(ct.gf_cells);
+    std::memcpy(s.gf_x, ct.gf_x, sizeof(s.gf_x));
+    std::memcpy(s.gf_z, ct.gf_z, sizeof(s.gf_z));
+    s.gf_k2 = ct.gf_k2;
+    std::memcpy(s.gf_always, ct.gf_always, sizeof(s.gf_always));
+    s.gf_ok = ct.gf_ok ? 1 : 0;
+    s.bounded = bounded ? 1 : 0;
+    s.radii_safe = radii_safe ? 1 : 0;
+    return s;
+}
+
+// The renderer's scalars in the same form (a renderer without group tables: their defaults).
+vcrt_scene_scalars scalars_struct_state() {
+    vcrt::CullTables ct;
+    ct.nbig = g.ncbig;
+    ct.ngroups = g.ncgroups;
+    std::memcpy(ct.margin, g.cmargin, sizeof(ct.margin));
+    ct.slab = g.cslab_on;
+    if (ct.slab) std::memcpy(ct.slab_lohi, g.cslab, sizeof(ct.slab_lohi));
+    std::memcpy(ct.fp_x, g.cfp_x, sizeof(ct.fp_x));
+    std::memcpy(ct.fp_z, g.cfp_z, sizeof(ct.fp_z));
+    std::memcpy(ct.fp_y, g.cfp_y, sizeof(ct.fp_y));
+    ct.fp_k2 = g.cfp_k2;
+    ct.fp_always = g.cfp_always;
+    if (g.cgf_n > 0) {
+        ct.gf_cells = static_cast<int32_t>(g.cgf_n);
+        std::memcpy(ct.gf_x, g.cgf_x, sizeof(ct.gf_x));
+        std::memcpy(ct.gf_z, g.cgf_z, sizeof(ct.gf_z));
+        std::memcpy(ct.gf_always, g.cgf_always, sizeof(ct.gf_always));
+        ct.gf_k2 = g.cgf_k2;
+        ct.gf_ok = g.cgf_ok;
+    }
+    return scalars_struct(ct, g.scene_bounded, g.radii_safe);
+}
+
+// One table of (values, ct) as the bytes vcrt_set_scene uploads; false: no such table.
+bool table_bytes_host(const vcrt_sphere* v, int32_t count, const vcrt::CullTables& ct,
+                      int32_t table, std::vector<unsigned char>& out) {
+    auto put = [&out](const void* p, size_t n) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        out.assign(b, b + n);
+        return n > 0;
+    };
+    auto floats = [&put](const std::vector<float>& t) { return put(t.data(), sizeof(float) * t.size()); };
+    auto words = [&put](const std::vector<uint32_t>& t) {
+        return put(t.data(), sizeof(uint32_t) * t.size());
+    };
+    if (table == VCRT_TABLE_LINEAR) return floats(linear_table(v, count));
+    if (table == VCRT_TABLE_CENTER_RADIUS || table == VCRT_TABLE_SHADE ||
+        table == VCRT_TABLE_MATERIAL) {
+        std::vector<float4> cr, shade, mat;
+        sphere_rows(v, count, cr, shade, mat);
+        const std::vector<float4>& t = table == VCRT_TABLE_CENTER_RADIUS ? cr
+                                       : table == VCRT_TABLE_SHADE       ? shade
+                                                                         : mat;
+        return put(t.data(), sizeof(float4) * t.size());
+    }
+    if (ct.ngroups <= 0) return false;
+    switch (table) {
+        case VCRT_TABLE_GROUPS: return floats(group_records(ct));
+        case VCRT_TABLE_BOUND: return floats(ct.bound);
+        case VCRT_TABLE_BOUND_NF: return floats(near_far(ct.bound));
+        case VCRT_TABLE_NODE: return floats(ct.node);
+        case VCRT_TABLE_NODE_NF: return floats(node_near_far(ct));
+        case VCRT_TABLE_TOP: return floats(ct.top);
+        case VCRT_TABLE_FOOT: return words(pack_footprint(ct));
+        case VCRT_TABLE_GROUP_FOOT: return words(ct.gf_tab);
+        case VCRT_TABLE_SCALARS: {
+            const vcrt_scene_scalars s =
+                scalars_struct(ct, values_bounded(v, count), values_radii_safe(v, count));
+            return put(&s, sizeof(s));
+        }
+        default: return false;
+    }
+}
+
+// The device buffer of a table and its size in bytes (null: no such table).
+const void* table_device(int32_t table, size_t* bytes) {
+    const size_t n = static_cast<size_t>(g.nspheres), ng = static_cast<size_t>(g.ncgroups);
+    *bytes = 0;
+    if (table == VCRT_TABLE_LINEAR) {
+        *bytes = ((n + 3) / 4 + 1) * 64;
+        return g.d_geom;
+    }
+    if (table == VCRT_TABLE_CENTER_RADIUS || table == VCRT_TABLE_SHADE ||
+        table == VCRT_TABLE_MATERIAL) {
+        *bytes = n * 16;
+        return table == VCRT_TABLE_CENTER_RADIUS ? g.d_center_radius
+               : table == VCRT_TABLE_SHADE       ? g.d_shade
+                                                 : g.d_material;
+    }
+    if (ng == 0) return nullptr;
+    const size_t node_pairs = ng / vcrt::kNodeGroups / 2, tops = (ng + 63) / 64;
+    switch (table) {
+        case VCRT_TABLE_GROUPS: *bytes = (static_cast<size_t>(g.ncbig) + ng) * 80; return g.d_cgroup;
+        case VCRT_TABLE_BOUND: *bytes = ng / 2 * 64; return g.d_cbound;
+        case VCRT_TABLE_BOUND_NF: *bytes = ng / 2 * 80; return g.d_cbound_nf;
+        case VCRT_TABLE_NODE: *bytes = node_pairs * 64; return g.d_cnode;
+        case VCRT_TABLE_NODE_NF: *bytes = (node_pairs + 3) / 4 * 4 * 80; return g.d_cnode_nf;
+        case VCRT_TABLE_TOP: *bytes = (tops + (tops & 1)) / 2 * 64; return g.d_ctop;
+        case VCRT_TABLE_FOOT:
+            *bytes = sizeof(uint32_t) * vcrt::kFootCells * (ng > 128 ? 4 : 2);
+            return g.d_fp_tab;
+        case VCRT_TABLE_GROUP_FOOT: *bytes = sizeof(uint32_t) * 16 * g.cgf_n; return g.d_gf_tab;
+        default: return nullptr;
+    }
+}
+
+// The refit on the host: the tables of h_ct's grouping for h_spheres' values (cluster.cpp
+// tables_of_grouping), uploaded into the kept buffers on the render stream.
+VkResult refit_on_host() {
+    vcrt::tables_of_grouping(g.h_spheres.data(), g.nspheres, g.h_ct);
+    g.h_ct_stale = false;
+    // (the images stay until the stream has taken them)
+    std::vector<std::vector<unsigned char>> images(VCRT_TABLE_GROUP_FOOT + 1);
+    for (int32_t table = VCRT_TABLE_LINEAR; table <= VCRT_TABLE_GROUP_FOOT; table++) {
+        size_t bytes = 0;
+        void* dst = const_cast<void*>(table_device(table, &bytes));
+        std::vector<unsigned char>& image = images[table];
+        if (!dst || bytes == 0 ||
+            !table_bytes_host(g.h_spheres.data(), g.nspheres, g.h_ct, table, image))
+            continue;
+        if (image.size() != bytes) return VK_ERROR_INITIALIZATION_FAILED;  // another grouping
+        VCRT_TRY(hipMemcpyAsync(dst, image.data(), bytes, hipMemcpyHostToDevice, g.stream));
+    }
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    install_scalars(g.h_ct, true, values_radii_safe(g.h_spheres.data(), g.nspheres));
+    return VK_SUCCESS;
+}
+
+// The refit on the device (scene_update.hip) from `d_values` on the render stream: rows, groups,
+// levels and summary; the summary comes back (with the spheres, when `back` is set: the device
+// variant's values for h_spheres) in one synchronisation; the host computes the scalars with
+// cluster.cpp's own code; footprint tables. *unbounded: a value failed |v| <= 2^30 (the tables
+// are then garbage and the caller rebuilds).
+VkResult refit_on_device(const float* d_values, vcrt_sphere* back, bool* unbounded) {
+    *unbounded = false;
+    if (!g.d_su_summary) VCRT_TRY(hipMalloc(&g.d_su_summary, sizeof(vcrt::SceneSummary)));
+    if (!g.h_su_summary) VCRT_TRY(hipHostMalloc(&g.h_su_summary, sizeof(vcrt::SceneSummary)));
+    for (int k = 0; k < 2; k++)
+        if (!g.ev_su[k]) VCRT_TRY(hipEventCreate(&g.ev_su[k]));
+    vcrt::SceneUpdateParams p{};
+    p.spheres = d_values;
+    p.geom = reinterpret_cast<float*>(g.d_geom);
+    p.center_radius = reinterpret_cast<float*>(g.d_center_radius);
+    p.shade = reinterpret_cast<float*>(g.d_shade);
+    p.material = reinterpret_cast<float*>(g.d_material);
+    p.cgroup = reinterpret_cast<float*>(g.d_cgroup);
+    p.cbound = reinterpret_cast<float*>(g.d_cbound);
+    p.cbound_nf = reinterpret_cast<float*>(g.d_cbound_nf);
+    p.cnode = reinterpret_cast<float*>(g.d_cnode);
+    p.cnode_nf = reinterpret_cast<float*>(g.d_cnode_nf);
+    p.ctop = reinterpret_cast<float*>(g.d_ctop);
+    p.fp_tab = g.d_fp_tab;
+    p.gf_tab = reinterpret_cast<uint32_t*>(g.d_gf_tab);
+    p.summary = g.d_su_summary;
+    p.nspheres = static_cast<uint32_t>(g.nspheres);
+    p.nbig = static_cast<uint32_t>(g.ncbig);
+    p.ngroups = static_cast<uint32_t>(g.ncgroups);
+    p.nnodes = p.ngroups / static_cast<uint32_t>(vcrt::kNodeGroups);
+    p.ntops = (p.ngroups + 63u) / 64u;
+    VCRT_TRY(hipEventRecord(g.ev_su[0], g.stream));
+    const uint32_t entries = 4u * ((p.nspheres + 3u) / 4u + 1u);
+    VkResult r = launch(g.k_su_rows, (entries + 255u) / 256u, 256, 0, p);
+    if (r != VK_SUCCESS) return r;
+    if ((r = launch(g.k_su_groups, (p.nbig + p.ngroups + 255u) / 256u, 256, 0, p)) != VK_SUCCESS)
+        return r;
+    if ((r = launch(g.k_su_levels, 1, vcrt::kSceneSummaryThreads, 0, p)) != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(g.h_su_summary, g.d_su_summary, sizeof(vcrt::SceneSummary),
+                            hipMemcpyDeviceToHost, g.stream));
+    if (back)
+        VCRT_TRY(hipMemcpyAsync(back, d_values, sizeof(vcrt_sphere) * p.nspheres,
+                                hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    const vcrt::SceneSummary m = *g.h_su_summary;
+    if (!m.bounded) {
+        *unbounded = true;
+        return VK_SUCCESS;
+    }
+    vcrt::CullTables ct;  // the scalars alone
+    ct.nbig = g.ncbig;
+    ct.ngroups = g.ncgroups;
+    vcrt::scalars_of_summary(m, ct);
+    install_scalars(ct, true, m.radii_safe != 0u);
+    for (int k = 0; k < 2; k++) {
+        p.fp_x[k] = ct.fp_x[k];
+        p.fp_z[k] = ct.fp_z[k];
+        p.gf_x[k] = ct.gf_x[k];
+        p.gf_z[k] = ct.gf_z[k];
+    }
+    p.fp_ok = ct.fp_ok ? 1u : 0u;
+    p.gf_n = g.d_gf_tab ? g.cgf_n : 0u;
+    p.gf_keep_all = ct.gf_keep_all ? 1u : 0u;
+    const uint32_t cells = vcrt::kFootCells * (p.ngroups > 128u ? 4u : 2u) + 4u * p.gf_n;
+    if ((r = launch(g.k_su_footprint, (cells + 255u) / 256u, 256, 0, p)) != VK_SUCCESS) return r;
+    VCRT_TRY(hipEventRecord(g.ev_su[1], g.stream));
+    g.h_ct_stale = true;
+    return VK_SUCCESS;
+}
+
+vcrt_result update_spheres(const vcrt_sphere* spheres, int32_t count, bool on_device_ptr) {
+    if (!g.begun) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (count < 0 || (count > 0 && !spheres)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (count != g.nspheres) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto elapsed = [t0]() {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+            .count();
+    };
+    g.su_stats = vcrt_scene_update_stats{};
+    const bool kernels = g.k_su_rows && g.k_su_groups && g.k_su_levels && g.k_su_footprint;
+    const char* how = std::getenv("VCRT_SCENE_UPDATE");
+    const bool on_host = how && std::strcmp(how, "host") == 0;
+    // the values on the host, where the path needs them before it starts
+    std::vector<vcrt_sphere> fetched;
+    auto host_values = [&]() -> const vcrt_sphere* {
+        if (!on_device_ptr) return spheres;
+        if (fetched.empty() && count > 0) {
+            fetched.resize(count);
+            (void)hipStreamSynchronize(g.stream);
+            if (hipMemcpy(fetched.data(), spheres, sizeof(vcrt_sphere) * count,
+                          hipMemcpyDeviceToHost) != hipSuccess)
+                return nullptr;
+        }
+        return fetched.data();
+    };
+    auto rebuild = [&](const vcrt_sphere* values) -> vcrt_result {
+        if (!values && count > 0) return VCRT_ERROR_UNKNOWN;
+        const vcrt_result r = vcrt_set_scene(values, count);
+        g.su_stats.rebuilt = 1;
+        g.su_stats.host_ms = elapsed();
+        return r;
+    };
+    if (g.ncgroups == 0 || count == 0 || (!kernels && !on_host)) return rebuild(host_values());
+    bool device = false;
+    if (on_host) {
+        const vcrt_sphere* values = host_values();
+        if (!values) return VCRT_ERROR_UNKNOWN;
+        if (!values_bounded(values, count)) return rebuild(values);
+        if (values != g.h_spheres.data()) g.h_spheres.assign(values, values + count);
+        const VkResult r = refit_on_host();
+        if (r != VK_SUCCESS) return r;
+    } else {
+        const float* d_values = reinterpret_cast<const float*>(spheres);
+        if (!on_device_ptr) {
+            if (!values_bounded(spheres, count)) return rebuild(spheres);
+            const size_t floats = static_cast<size_t>(count) * 10;
+            VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_su_spheres), &g.su_spheres_cap, floats,
+                          sizeof(float)));
+            VCRT_TRY(hipMemcpyAsync(g.d_su_spheres, spheres, sizeof(float) * floats,
+                                    hipMemcpyHostToDevice, g.stream));
+            d_values = g.d_su_spheres;
+            if (spheres != g.h_spheres.data()) g.h_spheres.assign(spheres, spheres + count);
+        } else {
+            fetched.resize(count);
+        }
+        bool unbounded = false;
+        const VkResult r =
+            refit_on_device(d_values, on_device_ptr ? fetched.data() : nullptr, &unbounded);
+        if (r != VK_SUCCESS) return r;
+        if (unbounded) return rebuild(fetched.data());
+        if (on_device_ptr) g.h_spheres = std::move(fetched);
+        device = true;
+    }
+    // the camera-ray lists and camera-relative records of the refitted tables
+    if (g.d_prim_info != nullptr) {
+        const char* lists = std::getenv("VCRT_CAMERA_LISTS");
+        const bool lists_device = !(lists && std::strcmp(lists, "host") == 0) && g.k_cl_prepare &&
+                                  g.k_cl_count && g.k_cl_scan && g.k_cl_fill;
+        const vcrt_camera_stats last_move = g.cam_stats;  // vcrt_set_camera's record stays
+        const VkResult r = lists_device ? build_camera_lists_device() : build_camera_lists_host();
+        if (r != VK_SUCCESS) return r;
+        g.su_stats.lists_ms = lists_device ? g.cam_stats.lists_ms : 0.0;
+        g.cam_stats = last_move;
+    }
+    if (g.desc.progressive && g.accumulated > 0) {
+        // new values restart progressive accumulation at sample 0, as a new scene does
+        const VkResult rj = setup_jitter(0);
+        if (rj != VK_SUCCESS) return rj;
+    }
+    g.accumulated = 0;
+    g.order_key = 0;  // the cost order is measured again
+    VCRT_TRY(reset_sums());
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    g.stage.pName = select_kernel().name;
+    if (device) {
+        float ms = 0.0f;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_su[0], g.ev_su[1]));
+        g.su_stats.refit_ms = ms;
+    }
+    const uint64_t ng = static_cast<uint64_t>(g.ncgroups), tops = (ng + 63) / 64;
+    g.su_stats.on_device = device ? 1 : 0;
+    g.su_stats.groups = static_cast<uint64_t>(g.ncbig) + ng;
+    g.su_stats.boxes = ng + ng / vcrt::kNodeGroups + tops + (tops & 1);
+    g.su_stats.footprint_cells = 4ull * vcrt::kFootCells + 4ull * (g.d_gf_tab ? g.cgf_n : 0u);
+    g.su_stats.host_ms = elapsed();
+    return VCRT_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_update_spheres(const vcrt_sphere* spheres, int32_t count) {
+    return update_spheres(spheres, count, false);
+}
+
+vcrt_result vcrt_update_spheres_device(const vcrt_sphere* spheres, int32_t count) {
+    return update_spheres(spheres, count, true);
+}
+
+vcrt_result vcrt_get_scene_update_stats(vcrt_scene_update_stats* stats) {
+    if (!g.begun || !stats) return VCRT_ERROR_INITIALIZATION_FAILED;
+    *stats = g.su_stats;
+    return VCRT_SUCCESS;
+}
+
+int64_t vcrt_scene_table_host(const vcrt_sphere* grouping_of, const vcrt_sphere* values,
+                              int32_t count, int32_t table, void* buf, size_t cap) {
+    if (count < 0 || (count > 0 && (!grouping_of || !values))) return 0;
+    vcrt::CullTables ct;
+    // (values that fail the bound have no tables, as a scene that fails it has none)
+    if (vcrt::choose_grouping(grouping_of, count, ct) && values_bounded(values, count))
+        vcrt::tables_of_grouping(values, count, ct);
+    else
+        ct = vcrt::CullTables{};
+    std::vector<unsigned char> image;
+    if (!table_bytes_host(values, count, ct, table, image)) return 0;
+    if (buf && cap >= image.size()) std::memcpy(buf, image.data(), image.size());
+    return static_cast<int64_t>(image.size());
+}
+
+int64_t vcrt_scene_table_read(int32_t table, void* buf, size_t cap) {
+    if (!g.begun) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (table == VCRT_TABLE_SCALARS) {
+        if (g.ncgroups == 0) return 0;
+        const vcrt_scene_scalars s = scalars_struct_state();
+        if (buf && cap >= sizeof(s)) std::memcpy(buf, &s, sizeof(s));
+        return static_cast<int64_t>(sizeof(s));
+    }
+    size_t bytes = 0;
+    const void* src = table_device(table, &bytes);
+    if (!src || bytes == 0) return 0;
+    if (buf && cap >= bytes) {
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+        VCRT_TRY(hipMemcpy(buf, src, bytes, hipMemcpyDeviceToHost));
+    }
+    return static_cast<int64_t>(bytes);
 }
 
 vcrt_result vcrt_selftest_sin(uint32_t first, uint32_t count, uint64_t* mismatches,
@@ -2698,13 +3173,18 @@ vcrt::Camera desc_camera(const vcrt_render_desc& d) {
 }
 
 // (a lens desc has no camera-ray lists: its rays do not share an origin)
-bool host_camera_tables(const vcrt_sphere* spheres, int32_t count, const vcrt_render_desc* desc_in,
-                        vcrt::CullTables& ct, float cam[12]) {
+// The tables are those of `grouping_of`'s grouping filled with `spheres`' values (a refit; the
+// scene's own tables when the two are one).
+bool host_camera_tables(const vcrt_sphere* grouping_of, const vcrt_sphere* spheres, int32_t count,
+                        const vcrt_render_desc* desc_in, vcrt::CullTables& ct, float cam[12]) {
     vcrt_render_desc dv;
-    if (!read_desc(desc_in, dv) || !desc_valid(dv) || count < 0 || (count > 0 && !spheres))
+    if (!read_desc(desc_in, dv) || !desc_valid(dv) || count < 0 ||
+        (count > 0 && (!spheres || !grouping_of)))
         return false;
     if (dv.lens_radius > 0.0f) return false;
-    if (!vcrt::build_cull_tables(spheres, count, ct)) return false;
+    if (!vcrt::choose_grouping(grouping_of, count, ct) || !values_bounded(spheres, count))
+        return false;
+    vcrt::tables_of_grouping(spheres, count, ct);
     const vcrt::Camera cm = desc_camera(dv);
     const vcrt::f3 v[4] = {cm.pixel00, cm.delta_u, cm.delta_v, cm.center};
     for (int i = 0; i < 4; i++) {
@@ -2718,9 +3198,15 @@ bool host_camera_tables(const vcrt_sphere* spheres, int32_t count, const vcrt_re
 
 int32_t vcrt_primary_lists(const vcrt_sphere* spheres, int32_t count, const vcrt_render_desc* desc,
                            uint32_t* info, int32_t cap_tiles, uint16_t* ids, int32_t cap_ids) {
+    return vcrt_refit_primary_lists(spheres, spheres, count, desc, info, cap_tiles, ids, cap_ids);
+}
+
+int32_t vcrt_refit_primary_lists(const vcrt_sphere* grouping_of, const vcrt_sphere* spheres,
+                                 int32_t count, const vcrt_render_desc* desc, uint32_t* info,
+                                 int32_t cap_tiles, uint16_t* ids, int32_t cap_ids) {
     vcrt::CullTables ct;
     float cam[12];
-    if (!host_camera_tables(spheres, count, desc, ct, cam)) return -1;
+    if (!host_camera_tables(grouping_of, spheres, count, desc, ct, cam)) return -1;
     vcrt::PrimaryLists pl;
     vcrt::build_primary_lists(ct, cam, desc->width, desc->height, desc->rank, desc->world_size,
                               pl);
@@ -2734,9 +3220,17 @@ int32_t vcrt_primary_lists(const vcrt_sphere* spheres, int32_t count, const vcrt
 int32_t vcrt_primary_sphere_lists(const vcrt_sphere* spheres, int32_t count,
                                   const vcrt_render_desc* desc, uint32_t* info, int32_t cap_tiles,
                                   float* rec, int32_t cap_floats) {
+    return vcrt_refit_primary_sphere_lists(spheres, spheres, count, desc, info, cap_tiles, rec,
+                                           cap_floats);
+}
+
+int32_t vcrt_refit_primary_sphere_lists(const vcrt_sphere* grouping_of, const vcrt_sphere* spheres,
+                                        int32_t count, const vcrt_render_desc* desc,
+                                        uint32_t* info, int32_t cap_tiles, float* rec,
+                                        int32_t cap_floats) {
     vcrt::CullTables ct;
     float cam[12];
-    if (!host_camera_tables(spheres, count, desc, ct, cam)) return -1;
+    if (!host_camera_tables(grouping_of, spheres, count, desc, ct, cam)) return -1;
     vcrt::PrimarySphereLists sl;
     vcrt::build_primary_sphere_lists(ct, spheres, cam, desc->width, desc->height, desc->rank,
                                      desc->world_size, sl);

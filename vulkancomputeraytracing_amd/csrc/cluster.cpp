@@ -127,104 +127,82 @@ float key_float(int64_t k) {
     return x;
 }
 
-// The group-level footprint tables (cluster.hpp gf_*), by the node tables' rule over the group
-// boxes exactly as uploaded (out.bound): per cell i of n, with ue(i) the largest and le(i) the
-// smallest float of the cell by the kernel's own cell function and g = 8u |e| + 2^-100,
-//   A[i] = groups with lo <= ue(i) + g,   B[i] = groups with hi >= le(i) - g     (in double).
-void build_group_footprint(CullTables& out) {
-    const int32_t ng = out.ngroups;
-    const int n = group_footprint_cells(ng);
-    if (ng <= 0 || ng > kGroupFootprintMaxGroups || n < 2) return;
-    struct GBox {
-        float lo[3], hi[3], K;
-        int32_t index;
-    };
-    std::vector<GBox> gb;
-    for (int32_t gi = 0; gi < ng; gi++) {
+uint32_t bits_of(float x) {
+    uint32_t b;
+    std::memcpy(&b, &x, sizeof b);
+    return b;
+}
+
+float float_of(uint32_t b) {
+    float x;
+    std::memcpy(&x, &b, sizeof x);
+    return x;
+}
+
+// A box of a footprint level: element `index` of a pair-SoA table.
+struct FBox {
+    float lo[3], hi[3], K;
+    int32_t index;
+};
+
+FBox fbox_of(const std::vector<float>& table, int32_t i) {
+    const float* t = &table[static_cast<size_t>(i / 2) * 16];
+    const int e = i % 2;
+    return FBox{{t[0 + e], t[2 + e], t[4 + e]}, {t[6 + e], t[8 + e], t[10 + e]}, t[12 + e], i};
+}
+
+bool group_has_members(const CullTables& ct, int32_t gi) {
+    bool members = false;
+    for (int k = 0; k < 4; k++) members |= ct.index[(ct.nbig + gi) * 4 + k] >= 0;
+    return members;
+}
+
+// The boxes of a level that have members (a padding box never gets a bit): the hierarchy groups
+// (per = 1) or the nodes (per = kNodeGroups), exactly as uploaded.
+std::vector<FBox> boxes_with_members(const CullTables& ct, int per) {
+    std::vector<FBox> out;
+    for (int32_t i = 0; i < ct.ngroups / per; i++) {
         bool members = false;
-        for (int k = 0; k < 4; k++) members |= out.index[(out.nbig + gi) * 4 + k] >= 0;
-        if (!members) continue;  // a padding group never gets a bit
-        const float* t = &out.bound[static_cast<size_t>(gi / 2) * 16];
-        const int e = gi % 2;
-        gb.push_back(GBox{{t[0 + e], t[2 + e], t[4 + e]}, {t[6 + e], t[8 + e], t[10 + e]},
-                          t[12 + e], gi});
+        for (int32_t gi = i * per; gi < (i + 1) * per; gi++) members |= group_has_members(ct, gi);
+        if (members) out.push_back(fbox_of(per == 1 ? ct.bound : ct.node, i));
     }
-    if (gb.empty()) return;
-    out.gf_cells = n;
-    // one height: the same y extent in every group box with members, bit for bit (whatever
-    // VCRT_SLAB says: that only chooses how box tests are evaluated)
-    bool same = std::isfinite(gb[0].lo[1]) && std::isfinite(gb[0].hi[1]);
-    for (const GBox& b : gb)
-        same = same && std::memcmp(&b.lo[1], &gb[0].lo[1], sizeof(float)) == 0 &&
-               std::memcmp(&b.hi[1], &gb[0].hi[1], sizeof(float)) == 0;
-    out.gf_one_height = same;
-    const char* env = std::getenv("VCRT_GROUP_FOOT");
-    out.gf_ok = same && !(env && std::atoi(env) == 0);
-    // A scene the cells cannot describe (a degenerate extent, a coordinate bound below the 2^-20
-    // of the proof) keeps every group with members for every ray, as the node tables do.
-    auto keep_all = [&out, &gb, n]() {
-        uint32_t real[4] = {0, 0, 0, 0};
-        for (const GBox& b : gb) real[b.index >> 5] |= 1u << (b.index & 31);
-        out.gf_tab.resize(static_cast<size_t>(16) * n);
-        for (size_t i = 0; i < out.gf_tab.size(); i++) out.gf_tab[i] = real[i & 3];
-        std::memcpy(out.gf_always, real, sizeof(real));
-        out.gf_x[0] = out.gf_z[0] = 1.0f;
-        out.gf_x[1] = out.gf_z[1] = 0.0f;
-    };
-    if (!(out.margin[2] >= 0x1p-20f)) return keep_all();
-    double xlo[3], xhi[3];
-    for (int a = 0; a < 3; a++) {
-        xlo[a] = std::numeric_limits<double>::infinity();
-        xhi[a] = -xlo[a];
-        for (const GBox& b : gb) {
-            xlo[a] = std::min(xlo[a], static_cast<double>(b.lo[a]));
-            xhi[a] = std::max(xhi[a], static_cast<double>(b.hi[a]));
-        }
-    }
-    for (int a = 0; a < 3; a += 2) {
-        float* so = a == 0 ? out.gf_x : out.gf_z;
-        const double w = xhi[a] - xlo[a];
-        so[0] = static_cast<float>(n / w);
-        so[1] = static_cast<float>(-xlo[a] * static_cast<double>(so[0]));
-        if (!(w > 0.0 && std::isnormal(so[0]) && std::isfinite(so[1]))) return keep_all();
-    }
-    float kmax = 0.0f;
-    for (const GBox& b : gb) {
-        if (std::isinf(b.K))
-            out.gf_always[b.index >> 5] |= 1u << (b.index & 31);
-        else
-            kmax = std::max(kmax, b.K);
-    }
-    out.gf_k2 = round_up(2.0 * static_cast<double>(kmax));
-    out.gf_tab.assign(static_cast<size_t>(16) * n, 0u);
+    return out;
+}
+
+// One pair of footprint tables (axis a: A at tab, B at tab + n * words) by the rule of
+// cluster.hpp: per cell i of n, with ue(i) the largest and le(i) the smallest float of the cell
+// by the kernel's own cell function and g = 8u |e| + 2^-100,
+//   A[i] = boxes with lo <= ue(i) + g,   B[i] = boxes with hi >= le(i) - g     (in double).
+// Masks of `words` words (low first), bit = the box's index (none from 32 * words on).
+void fill_masks(const std::vector<FBox>& boxes, int a, const float so[2], int n, int words,
+                uint32_t* tab) {
+    uint32_t* A = tab;
+    uint32_t* B = tab + static_cast<size_t>(n) * words;
     const double inf = std::numeric_limits<double>::infinity();
-    for (int a = 0; a < 3; a += 2) {
-        const float* so = a == 0 ? out.gf_x : out.gf_z;
-        uint32_t* A = &out.gf_tab[static_cast<size_t>(a == 0 ? 0 : 2) * n * 4];
-        uint32_t* B = A + static_cast<size_t>(n) * 4;
-        double prev_ue = -inf;  // the largest float of the cell before
-        for (int i = 0; i < n; i++) {
-            double ue = inf;
-            if (i < n - 1) {  // the largest float whose cell is <= i: the cell never falls as x rises
-                int64_t lo = float_key(-std::numeric_limits<float>::infinity());
-                int64_t hi = float_key(std::numeric_limits<float>::infinity());
-                while (hi - lo > 1) {  // cell(lo) <= i < cell(hi)
-                    const int64_t mid = lo + (hi - lo) / 2;
-                    (footprint_cell_n(key_float(mid), so, n) <= i ? lo : hi) = mid;
-                }
-                ue = key_float(lo);
+    double prev_ue = -inf;  // the largest float of the cell before
+    for (int i = 0; i < n; i++) {
+        double ue = inf;
+        if (i < n - 1) {  // the largest float whose cell is <= i: the cell never falls as x rises
+            int64_t lo = float_key(-std::numeric_limits<float>::infinity());
+            int64_t hi = float_key(std::numeric_limits<float>::infinity());
+            while (hi - lo > 1) {  // cell(lo) <= i < cell(hi)
+                const int64_t mid = lo + (hi - lo) / 2;
+                (footprint_cell_n(key_float(mid), so, n) <= i ? lo : hi) = mid;
             }
-            // the smallest float of cell i is the one after prev_ue; comparing against prev_ue
-            // itself only widens the mask
-            const double le = prev_ue;
-            const double up = ue + (8.0 * kU * std::fabs(ue) + 0x1p-100);
-            const double dn = le - (8.0 * kU * std::fabs(le) + 0x1p-100);
-            for (const GBox& b : gb) {
-                if (static_cast<double>(b.lo[a]) <= up) A[4 * i + (b.index >> 5)] |= 1u << (b.index & 31);
-                if (static_cast<double>(b.hi[a]) >= dn) B[4 * i + (b.index >> 5)] |= 1u << (b.index & 31);
-            }
-            prev_ue = ue;
+            ue = key_float(lo);
         }
+        // the smallest float of cell i is the one after prev_ue; comparing against prev_ue
+        // itself only widens the mask
+        const double le = prev_ue;
+        const double up = ue + (8.0 * kU * std::fabs(ue) + 0x1p-100);
+        const double dn = le - (8.0 * kU * std::fabs(le) + 0x1p-100);
+        for (const FBox& b : boxes) {
+            if (b.index >= 32 * words) continue;
+            const uint32_t bit = 1u << (b.index & 31);
+            if (static_cast<double>(b.lo[a]) <= up) A[words * i + (b.index >> 5)] |= bit;
+            if (static_cast<double>(b.hi[a]) >= dn) B[words * i + (b.index >> 5)] |= bit;
+        }
+        prev_ue = ue;
     }
 }
 
@@ -242,7 +220,154 @@ int footprint_cell_n(float x, const float so[2], int n) {
     return static_cast<int>(c);  // truncation, as v_cvt_u32_f32
 }
 
-bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
+void summary_of_tables(const vcrt_sphere* s, int32_t count, const CullTables& ct,
+                       SceneSummary& m) {
+    m = SceneSummary{};
+    for (int a = 0; a < 3; a++) {
+        m.lo_min[a] = kKeyPosInf;
+        m.hi_max[a] = kKeyNegInf;
+    }
+    m.ylo_max = kKeyNegInf;
+    m.yhi_min = kKeyPosInf;
+    m.bounded = m.radii_safe = 1u;
+    for (int32_t i = 0; i < count; i++) {
+        for (float v : {s[i].center[0], s[i].center[1], s[i].center[2], s[i].radius})
+            if (!(std::fabs(v) <= 0x1p30f)) m.bounded = 0u;  // also rejects NaN
+        if (!(std::fabs(s[i].radius) >= 0x1p-40f && std::fabs(s[i].radius) <= 0x1p30f))
+            m.radii_safe = 0u;
+    }
+    // the per-ray margin constants (tracer.hip, box_ray) over the hierarchy's spheres
+    for (size_t e = static_cast<size_t>(ct.nbig) * 4; e < ct.index.size(); e++) {
+        const int32_t j = ct.index[e];
+        if (j < 0) continue;
+        const double r = std::fabs(static_cast<double>(s[j].radius));
+        m.rmax = std::max(m.rmax, r);
+        double c2 = 0.0;
+        for (int a = 0; a < 3; a++) {
+            const double c = s[j].center[a];
+            c2 += c * c;
+            m.lam = std::max(m.lam, std::fabs(c) + r);
+        }
+        m.c2max = std::max(m.c2max, c2);
+    }
+    const bool masks = ct.ngroups <= kGroupFootprintMaxGroups;
+    for (const FBox& b : boxes_with_members(ct, 1)) {
+        m.boxes++;
+        for (int a = 0; a < 3; a++) {
+            m.lo_min[a] = std::min(m.lo_min[a], float_order_key(bits_of(b.lo[a])));
+            m.hi_max[a] = std::max(m.hi_max[a], float_order_key(bits_of(b.hi[a])));
+        }
+        m.ylo_max = std::max(m.ylo_max, float_order_key(bits_of(b.lo[1])));
+        m.yhi_min = std::min(m.yhi_min, float_order_key(bits_of(b.hi[1])));
+        if (masks) m.group_real[b.index >> 5] |= 1u << (b.index & 31);
+        if (std::isinf(b.K)) {
+            if (masks) m.group_always[b.index >> 5] |= 1u << (b.index & 31);
+        } else {
+            m.group_kmax = std::max(m.group_kmax, bits_of(b.K));
+        }
+    }
+    for (const FBox& b : boxes_with_members(ct, kNodeGroups)) {
+        m.node_real |= b.index < 32 ? 1u << b.index : 0u;
+        if (std::isinf(b.K))
+            m.node_always |= b.index < 32 ? 1u << b.index : 0u;
+        else
+            m.node_kmax = std::max(m.node_kmax, bits_of(b.K));
+    }
+}
+
+void scalars_of_summary(const SceneSummary& m, CullTables& out) {
+    // sqrt rises with its argument, so the largest |c| is the root of the largest |c|^2
+    out.margin[0] = round_up(std::sqrt(m.c2max) * (1.0 + 1e-6));
+    out.margin[1] = round_up(m.rmax * m.rmax * (1.0 + 1e-6));
+    out.margin[2] = round_up(m.lam * (1.0 + 1e-6));
+    out.margin[3] = 0.0f;
+    out.fp_always = 0xffffffffu;
+    if (m.boxes == 0) return;
+    double xlo[3], xhi[3];
+    for (int a = 0; a < 3; a++) {
+        xlo[a] = float_of(float_order_bits(m.lo_min[a]));
+        xhi[a] = float_of(float_order_bits(m.hi_max[a]));
+    }
+    // The shared y slab: do all boxes with members have the same finite y extent, bit for bit?
+    // (Padding boxes, the far point, are left out: their groups hold no member a ray can accept.)
+    // A node's or chunk's y extent is the smallest lo and the largest hi of its groups', so the
+    // group boxes decide for every level.
+    const bool one_y = m.lo_min[1] == m.ylo_max && m.hi_max[1] == m.yhi_min &&
+                       std::isfinite(xlo[1]) && std::isfinite(xhi[1]);
+    // VCRT_SLAB=0 keeps the three-axis box tests (A/B and tests)
+    const char* slab_env = std::getenv("VCRT_SLAB");
+    if (one_y && !(slab_env && std::atoi(slab_env) == 0)) {
+        out.slab = true;
+        out.slab_lohi[0] = static_cast<float>(xlo[1]);
+        out.slab_lohi[1] = static_cast<float>(xhi[1]);
+    }
+    const bool coords_ok = out.margin[2] >= 0x1p-20f;
+    // scale and offset of n cells over [xlo, xhi] of axis a; false: the cells cannot describe it
+    auto cells = [&](int a, int n, float so[2]) {
+        const double w = xhi[a] - xlo[a];
+        so[0] = static_cast<float>(n / w);
+        so[1] = static_cast<float>(-xlo[a] * static_cast<double>(so[0]));
+        return w > 0.0 && std::isnormal(so[0]) && std::isfinite(so[1]);
+    };
+    // The group-level tables (fact (5g)). A scene the cells cannot describe (a degenerate extent,
+    // a coordinate bound below the 2^-20 of the proof) keeps every group with members for every
+    // ray, as the node tables do.
+    const int n = group_footprint_cells(out.ngroups);
+    if (out.ngroups <= kGroupFootprintMaxGroups && n >= 2) {
+        out.gf_cells = n;
+        // one height: the same y extent in every group box with members, bit for bit (whatever
+        // VCRT_SLAB says: that only chooses how box tests are evaluated)
+        out.gf_one_height = one_y;
+        const char* env = std::getenv("VCRT_GROUP_FOOT");
+        out.gf_ok = one_y && !(env && std::atoi(env) == 0);
+        out.gf_keep_all = !(coords_ok && cells(0, n, out.gf_x) && cells(2, n, out.gf_z));
+        if (out.gf_keep_all) {
+            std::memcpy(out.gf_always, m.group_real, sizeof(out.gf_always));
+            out.gf_x[0] = out.gf_z[0] = 1.0f;
+            out.gf_x[1] = out.gf_z[1] = 0.0f;
+        } else {
+            std::memcpy(out.gf_always, m.group_always, sizeof(out.gf_always));
+            out.gf_k2 = round_up(2.0 * static_cast<double>(float_of(m.group_kmax)));
+        }
+    }
+    // The node tables (cluster.hpp).
+    out.fp_y[0] = static_cast<float>(xlo[1]);  // box coordinates: exact
+    out.fp_y[1] = static_cast<float>(xhi[1]);
+    out.fp_k2 = round_up(2.0 * static_cast<double>(float_of(m.node_kmax)));
+    out.fp_ok = out.ngroups / kNodeGroups <= 32 && coords_ok && cells(0, kFootprintCells, out.fp_x) &&
+                cells(2, kFootprintCells, out.fp_z);
+    if (!out.fp_ok) {
+        out.fp_x[0] = out.fp_z[0] = 1.0f;
+        out.fp_x[1] = out.fp_z[1] = 0.0f;
+        return;
+    }
+    out.fp_always = m.node_always;
+}
+
+void fill_footprints(CullTables& out) {
+    if (out.gf_cells > 0) {
+        const int n = out.gf_cells;
+        out.gf_tab.assign(static_cast<size_t>(16) * n, 0u);
+        if (out.gf_keep_all) {
+            for (size_t i = 0; i < out.gf_tab.size(); i++) out.gf_tab[i] = out.gf_always[i & 3];
+        } else {
+            const std::vector<FBox> gb = boxes_with_members(out, 1);
+            fill_masks(gb, 0, out.gf_x, n, 4, &out.gf_tab[0]);
+            fill_masks(gb, 2, out.gf_z, n, 4, &out.gf_tab[static_cast<size_t>(2) * n * 4]);
+        }
+    }
+    // The footprint tables (cluster.hpp): the node boxes exactly as uploaded, compared in double
+    // with the exact edges of the kernel's own cell function.
+    constexpr int N = kFootprintCells;
+    out.fp_tab.assign(4 * N, 0xffffffffu);
+    if (!out.fp_ok) return;
+    out.fp_tab.assign(4 * N, 0u);
+    const std::vector<FBox> nb = boxes_with_members(out, kNodeGroups);
+    fill_masks(nb, 0, out.fp_x, N, 1, &out.fp_tab[0]);
+    fill_masks(nb, 2, out.fp_z, N, 1, &out.fp_tab[2 * N]);
+}
+
+bool choose_grouping(const vcrt_sphere* s, int32_t count, CullTables& out) {
     out = CullTables{};
     if (count < 16) return false;
     for (int32_t i = 0; i < count; i++)
@@ -308,19 +433,41 @@ bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
     const size_t nbig = bigg.size(), ng = groups.size(), nall = nbig + ng;
     out.nbig = static_cast<int32_t>(nbig);
     out.ngroups = static_cast<int32_t>(ng);
-    out.geom.assign(nall * 16, 0.0f);
     out.index.assign(nall * 4, -1);
+    for (size_t gi = 0; gi < nall; gi++) {
+        const Group& g = gi < nbig ? bigg[gi] : groups[gi - nbig];
+        for (int k = 0; k < 4; k++) out.index[gi * 4 + k] = g[k];
+    }
+    return true;
+}
+
+bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
+    if (!choose_grouping(s, count, out)) return false;
+    tables_of_grouping(s, count, out);
+    return true;
+}
+
+void tables_of_grouping(const vcrt_sphere* s, int32_t count, CullTables& out) {
+    {  // everything but the grouping starts from its default
+        CullTables fresh;
+        fresh.nbig = out.nbig;
+        fresh.ngroups = out.ngroups;
+        fresh.index = std::move(out.index);
+        out = std::move(fresh);
+    }
+    const size_t nbig = out.nbig, ng = out.ngroups, nall = nbig + ng;
+    out.geom.assign(nall * 16, 0.0f);
     out.bound.assign(ng / 2 * 16, 0.0f);
     out.node.assign(ng / kNodeGroups / 2 * 16, 0.0f);
     for (size_t gi = 0; gi < nall; gi++) {
-        const Group& g = gi < nbig ? bigg[gi] : groups[gi - nbig];
         // members: pair-SoA exactly as the linear table (r^2 = radius * radius in fp32)
         for (int k = 0; k < 4; k++) {
             float* base = &out.geom[gi * 16 + 8 * (k / 2)];
             const int e = k % 2;
+            const int32_t j = out.index[gi * 4 + k];
             float cx = 0.f, cy = 0.f, cz = 0.f, r2 = -3.0e38f;
-            if (g[k] >= 0) {
-                const vcrt_sphere& sp = s[g[k]];
+            if (j >= 0) {
+                const vcrt_sphere& sp = s[j];
                 cx = sp.center[0];
                 cy = sp.center[1];
                 cz = sp.center[2];
@@ -330,35 +477,14 @@ bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
             base[2 + e] = cy;
             base[4 + e] = cz;
             base[6 + e] = r2;
-            out.index[gi * 4 + k] = g[k];
         }
     }
-    auto members_of = [&](size_t g0, size_t g1) {
+    auto box_at = [&](size_t g0, size_t g1) {
         std::vector<int32_t> m;
         for (size_t gi = g0; gi < std::min(g1, ng); gi++)
             for (int k = 0; k < 4; k++)
-                if (groups[gi][k] >= 0) m.push_back(groups[gi][k]);
-        return m;
-    };
-    // The shared y slab: do all boxes with members have the same finite y extent, bit for bit?
-    // (Padding boxes, the far point, are left out: their groups hold no member a ray can accept.)
-    int slab_boxes = 0;
-    bool slab_same = true;
-    float slab_lo = 0.0f, slab_hi = 0.0f;
-    auto box_at = [&](size_t g0, size_t g1) {
-        const std::vector<int32_t> m = members_of(g0, g1);
-        const Box b = box_of(s, m);
-        if (!m.empty()) {
-            if (slab_boxes++ == 0) {
-                slab_lo = b.lo[1];
-                slab_hi = b.hi[1];
-                slab_same = std::isfinite(slab_lo) && std::isfinite(slab_hi);
-            } else if (std::memcmp(&b.lo[1], &slab_lo, sizeof(float)) != 0 ||
-                       std::memcmp(&b.hi[1], &slab_hi, sizeof(float)) != 0) {
-                slab_same = false;
-            }
-        }
-        return b;
+                if (out.index[(nbig + gi) * 4 + k] >= 0) m.push_back(out.index[(nbig + gi) * 4 + k]);
+        return box_of(s, m);
     };
     for (size_t gi = 0; gi < ng; gi++) put_box(out.bound, gi, box_at(gi, gi + 1));
     for (size_t ni = 0; ni < ng / kNodeGroups; ni++)
@@ -367,130 +493,11 @@ bool build_cull_tables(const vcrt_sphere* s, int32_t count, CullTables& out) {
     const size_t nt = (ng + 63) / 64, nt2 = nt + (nt & 1);
     out.top.assign(nt2 / 2 * 16, 0.0f);
     for (size_t ti = 0; ti < nt2; ti++) put_box(out.top, ti, box_at(ti * 64, ti * 64 + 64));
-    // VCRT_SLAB=0 keeps the three-axis box tests (A/B and tests)
-    const char* slab_env = std::getenv("VCRT_SLAB");
-    if (slab_boxes > 0 && slab_same && !(slab_env && std::atoi(slab_env) == 0)) {
-        out.slab = true;
-        out.slab_lohi[0] = slab_lo;
-        out.slab_lohi[1] = slab_hi;
-    }
-    // the per-ray margin constants (tracer.hip, box_ray) over the hierarchy's spheres
-    double rmax = 0.0, cmax = 0.0, lam = 0.0;
-    for (int32_t j : normal) {
-        const double r = std::fabs(static_cast<double>(s[j].radius));
-        rmax = std::max(rmax, r);
-        double c2 = 0.0;
-        for (int a = 0; a < 3; a++) {
-            const double c = s[j].center[a];
-            c2 += c * c;
-            lam = std::max(lam, std::fabs(c) + r);
-        }
-        cmax = std::max(cmax, std::sqrt(c2));
-    }
-    out.margin[0] = round_up(cmax * (1.0 + 1e-6));
-    out.margin[1] = round_up(rmax * rmax * (1.0 + 1e-6));
-    out.margin[2] = round_up(lam * (1.0 + 1e-6));
-    out.margin[3] = 0.0f;
 
-    build_group_footprint(out);  // the group-level tables (fact (5g)), from out.bound
-
-    // The footprint tables (cluster.hpp): the node boxes exactly as uploaded, compared in double
-    // with the exact edges of the kernel's own cell function.
-    constexpr int N = kFootprintCells;
-    out.fp_tab.assign(4 * N, 0xffffffffu);
-    out.fp_always = 0xffffffffu;
-    const size_t nnodes = ng / kNodeGroups;
-    std::vector<Box> nb;
-    std::vector<uint32_t> nbit;
-    for (size_t ni = 0; ni < nnodes; ni++) {
-        const std::vector<int32_t> m = members_of(ni * kNodeGroups, (ni + 1) * kNodeGroups);
-        if (m.empty()) continue;
-        nb.push_back(box_of(s, m));
-        nbit.push_back(ni < 32 ? 1u << ni : 0u);
-    }
-    if (nb.empty()) return true;
-    double xlo[3], xhi[3];
-    for (int a = 0; a < 3; a++) {
-        xlo[a] = std::numeric_limits<double>::infinity();
-        xhi[a] = -xlo[a];
-        for (const Box& b : nb) {
-            xlo[a] = std::min(xlo[a], static_cast<double>(b.lo[a]));
-            xhi[a] = std::max(xhi[a], static_cast<double>(b.hi[a]));
-        }
-    }
-    out.fp_y[0] = static_cast<float>(xlo[1]);  // box coordinates: exact
-    out.fp_y[1] = static_cast<float>(xhi[1]);
-    float kmax = 0.0f;
-    uint32_t always = 0u;
-    for (size_t k = 0; k < nb.size(); k++) {
-        if (std::isinf(nb[k].K))
-            always |= nbit[k];
-        else
-            kmax = std::max(kmax, nb[k].K);
-    }
-    out.fp_k2 = round_up(2.0 * static_cast<double>(kmax));
-    bool ok = nnodes <= 32 && out.margin[2] >= 0x1p-20f;
-    for (int a = 0; a < 3 && ok; a += 2) {
-        float* so = a == 0 ? out.fp_x : out.fp_z;
-        const double w = xhi[a] - xlo[a];
-        so[0] = static_cast<float>(N / w);
-        so[1] = static_cast<float>(-xlo[a] * static_cast<double>(so[0]));
-        ok = w > 0.0 && std::isnormal(so[0]) && std::isfinite(so[1]);
-    }
-    if (!ok) {
-        out.fp_x[0] = out.fp_z[0] = 1.0f;
-        out.fp_x[1] = out.fp_z[1] = 0.0f;
-        return true;
-    }
-    out.fp_always = always;
-    // floats in order: key(x) rises with x (-inf .. +inf, -0 below +0)
-    auto key_of = [](float x) {
-        uint32_t b;
-        std::memcpy(&b, &x, sizeof b);
-        return (b & 0x80000000u) ? static_cast<int64_t>(0x7fffffffu) - static_cast<int64_t>(b & 0x7fffffffu)
-                                 : static_cast<int64_t>(0x80000000u) + static_cast<int64_t>(b);
-    };
-    auto float_of = [](int64_t k) {
-        const uint32_t b = k >= static_cast<int64_t>(0x80000000u)
-                               ? static_cast<uint32_t>(k - static_cast<int64_t>(0x80000000u))
-                               : 0x80000000u | static_cast<uint32_t>(static_cast<int64_t>(0x7fffffffu) - k);
-        float x;
-        std::memcpy(&x, &b, sizeof x);
-        return x;
-    };
-    const double inf = std::numeric_limits<double>::infinity();
-    for (int a = 0; a < 3; a += 2) {
-        const float* so = a == 0 ? out.fp_x : out.fp_z;
-        uint32_t* A = &out.fp_tab[(a == 0 ? 0 : 2) * N];
-        uint32_t* B = A + N;
-        double prev_ue = -inf;  // the largest float of the cell before
-        for (int i = 0; i < N; i++) {
-            double ue = inf;
-            if (i < N - 1) {  // the largest float whose cell is <= i: the cell never falls as x rises
-                int64_t lo = key_of(-std::numeric_limits<float>::infinity());
-                int64_t hi = key_of(std::numeric_limits<float>::infinity());
-                while (hi - lo > 1) {  // cell(lo) <= i < cell(hi)
-                    const int64_t mid = lo + (hi - lo) / 2;
-                    (footprint_cell(float_of(mid), so) <= i ? lo : hi) = mid;
-                }
-                ue = float_of(lo);
-            }
-            // the smallest float of cell i is the one after prev_ue; comparing against prev_ue
-            // itself only widens the mask
-            const double le = prev_ue;
-            const double up = ue + (8.0 * kU * std::fabs(ue) + 0x1p-100);
-            const double dn = le - (8.0 * kU * std::fabs(le) + 0x1p-100);
-            uint32_t ma = 0u, mb = 0u;
-            for (size_t k = 0; k < nb.size(); k++) {
-                if (static_cast<double>(nb[k].lo[a]) <= up) ma |= nbit[k];
-                if (static_cast<double>(nb[k].hi[a]) >= dn) mb |= nbit[k];
-            }
-            A[i] = ma;
-            B[i] = mb;
-            prev_ue = ue;
-        }
-    }
-    return true;
+    SceneSummary m;
+    summary_of_tables(s, count, out, m);
+    scalars_of_summary(m, out);
+    fill_footprints(out);
 }
 
 int footprint_cell(float x, const float so[2]) {

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "scene_update_abi.h"
 #include "vcrt.h"
 
 namespace vcrt {
@@ -65,6 +66,10 @@ struct CullTables {
     uint32_t gf_always[4] = {0, 0, 0, 0};  // groups whose K is +inf
     bool gf_one_height = false;    // every group box with members has the y extent fp_y
     bool gf_ok = false;
+    // how scalars_of_summary left the two levels for fill_footprints and the refit kernels:
+    // the node masks follow the rule (else all-ones); every group cell keeps gf_always
+    bool fp_ok = false;
+    bool gf_keep_all = false;
 };
 
 constexpr int kFootprintCells = 84;  // = vcrt::kFootCells (vcrt_kernel_abi.h)
@@ -82,6 +87,24 @@ int footprint_cell(float x, const float scale_offset[2]);
 // Builds the grouped tables. Returns false (tables empty) when culling does not apply: fewer
 // than 16 spheres or any centre/radius outside +-2^30 (or not finite).
 bool build_cull_tables(const vcrt_sphere* spheres, int32_t count, CullTables& out);
+
+// Its two halves. choose_grouping fills nbig, ngroups and index alone (false as above);
+// tables_of_grouping fills everything else of `out` from the values of `spheres` and the
+// grouping `out` holds, which need not be the one choose_grouping gives for these values
+// (vcrt_update_spheres keeps a scene's grouping while its spheres move): the boxes are the
+// members' whatever the members are, so the culled scans stay exact and only get slower as the
+// groups spread. Every |centre|, |radius| must be <= 2^30.
+bool choose_grouping(const vcrt_sphere* spheres, int32_t count, CullTables& out);
+void tables_of_grouping(const vcrt_sphere* spheres, int32_t count, CullTables& out);
+
+// tables_of_grouping's steps after the boxes, apart so the device refit (scene_update.hip) can
+// take the middle one with a summary it reduced itself: the maxima and minima of the spheres and
+// boxes (scene_update_abi.h); every scalar of `out` from them (out.ngroups set, the scalars at
+// their defaults); the footprint tables from out's boxes and scalars.
+void summary_of_tables(const vcrt_sphere* spheres, int32_t count, const CullTables& ct,
+                       SceneSummary& m);
+void scalars_of_summary(const SceneSummary& m, CullTables& out);
+void fill_footprints(CullTables& out);
 
 // Primary-ray lists (the flat scan's camera rays skip the node level): for every 4x4-pixel
 // quarter of every local 8x8 tile, the hierarchy groups a camera ray through it may need, by a

@@ -421,6 +421,63 @@ class Renderer:
                 rec.ctypes.data_as(ctypes.c_void_p), rec.size, None, None))
         return {"group_info": ginfo, "ids": ids, "sphere_info": sinfo, "rec": rec}
 
+    def update_spheres(self, spheres) -> None:
+        """Replace the values of the current scene's spheres between frames
+        (vcrt_update_spheres): the count stays, the scene's grouping is kept and every table is
+        refitted on the GPU. Later frames and ray queries are bit for bit those of a fresh
+        Renderer with the new scene; after large moves they get slower, never wrong (set_scene
+        regroups). A numpy [n, 10] float32 array, or whatever set_scene accepts, goes through the
+        host call; a contiguous torch float32 [n, 10] tensor on the renderer's device goes
+        through the device call on its data_ptr(), after the caller's current stream is
+        synchronised. Progressive accumulation restarts."""
+        lib = self._L()
+        if _is_torch(spheres):
+            import torch
+            t = spheres
+            if t.dtype != torch.float32 or t.ndim != 2 or t.shape[1] != 10:
+                raise ValueError("spheres: a torch tensor must be float32 [n, 10]")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("spheres: a torch tensor must be contiguous and on a CUDA device")
+            if self.desc.device >= 0 and t.device.index != self.desc.device:
+                raise ValueError(f"spheres on {t.device}, the renderer on device {self.desc.device}")
+            torch.cuda.current_stream(t.device).synchronize()
+            N.check("vcrt_update_spheres_device",
+                    lib.vcrt_update_spheres_device(t.data_ptr(), int(t.shape[0])))
+            self._scene = None  # the values live on the device
+            return
+        arr = builtin_scene(spheres) if isinstance(spheres, (str, int)) else spheres
+        arr = np.asarray(arr)
+        if arr.dtype != SPHERE_DTYPE:
+            arr = np.ascontiguousarray(arr, dtype=np.float32)
+            if arr.ndim != 2 or arr.shape[1] != 10:
+                raise ValueError(f"spheres: shape [n, 10] expected, got {arr.shape}")
+            arr = arr.view(SPHERE_DTYPE).reshape(-1)
+        arr = np.ascontiguousarray(arr)
+        N.check("vcrt_update_spheres", lib.vcrt_update_spheres(arr.ctypes.data, len(arr)))
+        self._scene = arr
+
+    def scene_update_stats(self) -> dict:
+        """The last update_spheres (vcrt_get_scene_update_stats): host_ms, refit_ms, lists_ms,
+        on_device, rebuilt, groups, boxes, footprint_cells."""
+        s = N.vcrt_scene_update_stats()
+        N.check("vcrt_get_scene_update_stats",
+                self._L().vcrt_get_scene_update_stats(ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in N.vcrt_scene_update_stats._fields_}
+
+    def scene_table(self, name: str):
+        """One of the scene's device tables read back (vcrt_scene_table_read), whoever wrote it:
+        a flat numpy array of the table's words (`_native.SCENE_TABLES`), a dict for "scalars",
+        None when the renderer has no such table."""
+        from .scene import table_from_bytes
+        tid, _ = N.SCENE_TABLES[name]
+        lib = self._L()
+        n = N.check_count("vcrt_scene_table_read", lib.vcrt_scene_table_read(tid, None, 0))
+        if n == 0:
+            return None
+        buf = np.zeros(n, np.uint8)
+        N.check_count("vcrt_scene_table_read", lib.vcrt_scene_table_read(tid, buf.ctypes.data, n))
+        return table_from_bytes(name, buf)
+
     def framebuffer_device(self) -> tuple[int, int]:
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         N.check("vcrt_framebuffer_device",

@@ -192,3 +192,66 @@ def primary_sphere_lists(spheres: np.ndarray, desc) -> dict | None:
                                         info.ctypes.data, nt, rec.ctypes.data, rec.size)
     assert got == n
     return {"info": info, "rec": rec[:n]}
+
+
+def table_from_bytes(name: str, raw: np.ndarray):
+    """The bytes of a scene table (`_native.SCENE_TABLES`) as a flat array of its words, or for
+    "scalars" a dict of the vcrt_scene_scalars fields (arrays as tuples; floats as np.float32, so
+    two dicts compare equal exactly when the bytes do, NaN aside)."""
+    _, dtype = N.SCENE_TABLES[name]
+    if name != "scalars":
+        return np.frombuffer(raw.tobytes(), dtype=dtype).copy()
+    s = N.vcrt_scene_scalars.from_buffer_copy(raw.tobytes())
+    out = {}
+    for field, ctype in N.vcrt_scene_scalars._fields_:
+        v = getattr(s, field)
+        if hasattr(v, "__len__"):
+            out[field] = tuple(np.float32(x) if ctype._type_ is ctypes.c_float else int(x)
+                               for x in v)
+        else:
+            out[field] = np.float32(v) if ctype is ctypes.c_float else int(v)
+    return out
+
+
+def refit_table(grouping_of: np.ndarray, values: np.ndarray, name: str):
+    """One device table as a refit computes it (host computation, no GPU;
+    vcrt_scene_table_host): the grouping set_scene(grouping_of) chooses, filled with `values`
+    (same count) -- what Renderer.update_spheres(values) leaves on the device of a renderer whose
+    scene was set to `grouping_of`. With values == grouping_of, what set_scene uploads. The form
+    of Renderer.scene_table; None when the table does not exist."""
+    grouping_of = np.ascontiguousarray(grouping_of, dtype=SPHERE_DTYPE)
+    values = np.ascontiguousarray(values, dtype=SPHERE_DTYPE)
+    if len(values) != len(grouping_of):
+        raise ValueError("values and grouping_of must hold the same number of spheres")
+    tid, _ = N.SCENE_TABLES[name]
+    lib = N.lib()
+    n = lib.vcrt_scene_table_host(grouping_of.ctypes.data, values.ctypes.data, len(values), tid,
+                                  None, 0)
+    if n <= 0:
+        return None
+    buf = np.zeros(n, np.uint8)
+    lib.vcrt_scene_table_host(grouping_of.ctypes.data, values.ctypes.data, len(values), tid,
+                              buf.ctypes.data, n)
+    return table_from_bytes(name, buf)
+
+
+def refit_camera_lists(grouping_of: np.ndarray, values: np.ndarray, desc) -> dict | None:
+    """primary_lists and primary_sphere_lists over refitted tables (refit_table's), in the form
+    of Renderer.camera_lists: group_info, ids, sphere_info, rec. None without culling tables."""
+    grouping_of = np.ascontiguousarray(grouping_of, dtype=SPHERE_DTYPE)
+    values = np.ascontiguousarray(values, dtype=SPHERE_DTYPE)
+    lib = N.lib()
+    d = desc.to_c()
+    args = (grouping_of.ctypes.data, values.ctypes.data, len(values), ctypes.byref(d))
+    nids = lib.vcrt_refit_primary_lists(*args, None, 0, None, 0)
+    npairs = lib.vcrt_refit_primary_sphere_lists(*args, None, 0, None, 0)
+    if nids < 0 or npairs < 0:
+        return None
+    from .renderer import tiles_for_rank
+    nt = 4 * len(tiles_for_rank(desc.width, desc.height, desc.world_size, desc.rank))
+    ginfo, sinfo = np.zeros(nt, np.uint32), np.zeros(nt, np.uint32)
+    ids = np.zeros(max(nids, 1), np.uint16)
+    rec = np.zeros((max(npairs, 1), 12), np.float32)
+    lib.vcrt_refit_primary_lists(*args, ginfo.ctypes.data, nt, ids.ctypes.data, len(ids))
+    lib.vcrt_refit_primary_sphere_lists(*args, sinfo.ctypes.data, nt, rec.ctypes.data, rec.size)
+    return {"group_info": ginfo, "ids": ids[:nids], "sphere_info": sinfo, "rec": rec[:npairs]}
