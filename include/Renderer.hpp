@@ -28,5 +28,9 @@ VkResult SetRenderCamera(IN const vcrt_camera* camera);
 // Moves the spheres of the running renderer (vcrt_update_spheres: same count, the tables refitted
 // on the GPU); a later Begin starts from the new values too.
 VkResult UpdateSpheres(IN const vcrt_sphere* spheres, IN int32_t count);
+// The guide buffers of the frame's camera rays for sample indices first .. first + n - 1
+// (vcrt_draw_features: host pointers in the framebuffer's layout; any may be NULL, not all).
+VkResult DrawFeatures(IN uint32_t first, IN uint32_t n, OUT float* albedo, OUT float* normal_depth,
+                      OUT int32_t* sphere);
 
 #endif

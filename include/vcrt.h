@@ -25,7 +25,9 @@
  * frames without a new vcrt_begin (vcrt_set_camera: the camera-ray lists are rebuilt on the GPU;
  * vcrt_get_camera_stats, vcrt_camera_lists_read); spheres that move between frames without a new
  * vcrt_set_scene (vcrt_update_spheres: the scene's grouping is kept and its tables are refitted
- * on the GPU; vcrt_get_scene_update_stats, vcrt_scene_table_host / _read).
+ * on the GPU; vcrt_get_scene_update_stats, vcrt_scene_table_host / _read); the guide buffers of
+ * a frame for a denoiser (vcrt_draw_features: first-hit albedo, normal, depth, coverage and
+ * sphere id of the frame's own camera rays; vcrt_frame_rays).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -440,8 +442,9 @@ vcrt_result vcrt_read_framebuffer_srgb8(uint8_t* rgba8, size_t bytes);
 void vcrt_srgb8_thresholds(float thresholds[255]);
 
 /* Ray queries: the radiance (ray_color, functions.glsl:65-92) and the first hit of rays the caller
- * supplies, against the scene of the last vcrt_set_scene -- any camera model, picking, probes,
- * albedo and normal buffers. Added (the reference traces its own camera's rays only). */
+ * supplies, against the scene of the last vcrt_set_scene -- any camera model, picking, probes
+ * (the frame's own albedo and normal buffers: vcrt_draw_features). Added (the reference traces
+ * its own camera's rays only). */
 typedef struct vcrt_ray_hit {   /* 32 B; the path's first segment */
     float    t;          /* accepted root; the reference's `infinity` (globals.glsl:26) when sphere < 0 */
     int32_t  sphere;     /* index into the array given to vcrt_set_scene; -1: sky, or max_depth == 0 */
@@ -519,6 +522,79 @@ vcrt_result vcrt_occlude_rays(const float* origins, const float* dirs, const flo
  * done. */
 vcrt_result vcrt_occlude_rays_device(const float* origins, const float* dirs, const float* tmax,
                                      uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats);
+
+/* Feature buffers: the guide images a denoiser wants, of the frame's own camera rays -- first-hit
+ * albedo, normal and depth, a coverage channel and a sphere id for edge stopping and picking --
+ * generated on the GPU from the renderer's camera, jitter and lens, averaged per pixel in a fixed
+ * order, in the framebuffer's layout. Added.
+ *
+ * For a local pixel (x, y) and the sample indices i = first .. first + n - 1, ray_i(x, y) is
+ * exactly the ray the frame traces for sample index i (absolute, as lens_radius counts them):
+ *   pinhole:          origin = camera centre,        dir = (corner(x, y) + jitter_i) - centre
+ *   lens_radius > 0:  origin_i = centre + offset_i,  dir = (corner(x, y) + jitter_i) - origin_i
+ * (vcrt_lens_offsets; corner = pixel00 + x delta_u + y delta_v and jitter_i = jx delta_u + jy
+ * delta_v of shader.comp:43-49), every fp32 operation rounded on its own: vcrt_frame_rays is this
+ * definition as code. (t_i, s_i, normal_i) is the first hit_sphere scan of that ray, what
+ * vcrt_trace_rays reports in vcrt_ray_hit: strict <, the earliest index on ties, normal = (point -
+ * centre) / radius, not flipped, not renormalised. Per sample:
+ *   a_i  the albedo: sky (s_i < 0): sky_factor(d.y / length(d)), i.e. ray_color(origin, dir, 1)
+ *        of a miss; glass (material id 3): (1, 1, 1); anything else: the sphere's colour as
+ *        stored, without texture[1]
+ *   n_i  normal_i, or 0 for the sky
+ *   z_i  t_i, or 0 for the sky; t is in units of dir: for the pinhole the viewport point is at
+ *        t = 1, so z x focal length is planar depth
+ *   c_i  1 on a hit, else 0
+ * Outputs, each [elements] in the rank-local framebuffer layout (vcrt_local_layout: world 1
+ * [height][width]; world > 1 packed tiles [tiles][64], slots outside the frame left untouched; the
+ * float4 planes go through vcrt_assemble_tiles as frames do):
+ *   albedo        float4: rgb = (sum a_i) / n, a = (sum c_i) / n
+ *   normal_depth  float4: xyz = (sum n_i) / n, w = (sum z_i) / n
+ *   sphere        int32:  s of sample index `first` (-1: sky)
+ * Every sum is an fp32 sum that starts at +0 and adds in sample order, divided once by (float)n
+ * with correctly rounded division. One lane owns a pixel and runs its samples in order, so the
+ * bits depend on (desc, camera, scene, first, n) only -- not on the schedule, on kernel_variant,
+ * or on which scan served a ray (the camera-ray lists where the frame has them, else the scans of
+ * vcrt_trace_rays; VCRT_FEATURE_LISTS=0 in the environment turns the list route off: A/B runs and
+ * tests). The contract holds wherever the frame's does: a bounded scene and a finite camera;
+ * anything else is traced without a fault, deterministic, otherwise unspecified.
+ *
+ * Any output may be NULL, but not all three; stats may be NULL. The call is local, not collective,
+ * runs on the render stream and returns when done. It leaves alone the framebuffer, the
+ * progressive accumulation, vcrt_stats, the measured cost order and the frame's jitter and lens
+ * tables: it builds the jitter terms and lens origins of its own index range, with the kernel and
+ * host functions the frame uses, into buffers of its own that are kept, only grown, and freed by
+ * vcrt_end. After vcrt_set_camera, vcrt_update_spheres and vcrt_set_scene it sees the new state.
+ * vcrt_draw_features takes host pointers (staged through device buffers kept between calls);
+ * vcrt_draw_features_device device pointers, the float4 planes 16-B aligned.
+ * Errors: VCRT_ERROR_INITIALIZATION_FAILED, before anything touches the GPU, before vcrt_begin,
+ * when all three outputs are NULL and for a misaligned device plane;
+ * VCRT_ERROR_FORMAT_NOT_SUPPORTED for n == 0 or first + n > 2^19 (the index bound of
+ * vcrt_lens_offsets), checked before the renderer's state, so it reads the same before
+ * vcrt_begin; VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object has no
+ * vcrt_frame_features kernel (an A/B build of an older tree). */
+typedef struct vcrt_feature_stats {
+    uint64_t rays;          /* valid local pixels * n */
+    uint64_t listed_rays;   /* rays answered from the camera-ray lists */
+    uint64_t group_tests;   /* as vcrt_ray_stats */
+    uint64_t bound_tests;
+    double   kernel_ms;     /* the feature kernel, HIP events on the render stream */
+    double   host_ms;       /* wall time of the call */
+    char     kernel[48];    /* code-object symbol that ran */
+} vcrt_feature_stats;
+vcrt_result vcrt_draw_features(uint32_t first, uint32_t n, float* albedo, float* normal_depth,
+                               int32_t* sphere, vcrt_feature_stats* stats);
+vcrt_result vcrt_draw_features_device(uint32_t first, uint32_t n, float* albedo,
+                                      float* normal_depth, int32_t* sphere,
+                                      vcrt_feature_stats* stats);
+/* The frame's rays of listed pixels, the definition above as code (host only, no GPU): for pixel
+ * p = (xy[2 p], xy[2 p + 1]) of the whole frame and sample index first + k, k < n, origins and
+ * dirs [(p * n + k) * 3 ..] receive ray_{first + k}(x, y) of desc's camera and lens. Returns
+ * npixels, or a negative VkResult: VCRT_ERROR_INITIALIZATION_FAILED for an invalid desc, a
+ * negative npixels, a NULL pointer with npixels > 0 or a pixel outside the frame;
+ * VCRT_ERROR_FORMAT_NOT_SUPPORTED for n == 0 or first + n > 2^19. */
+int32_t vcrt_frame_rays(const vcrt_render_desc* desc, const int32_t* xy, int32_t npixels,
+                        uint32_t first, uint32_t n, float* origins /* [npixels][n][3] */,
+                        float* dirs /* [npixels][n][3] */);
 
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file

@@ -137,6 +137,18 @@ class vcrt_ray_stats(ctypes.Structure):
     ]
 
 
+class vcrt_feature_stats(ctypes.Structure):
+    _fields_ = [
+        ("rays", ctypes.c_uint64),
+        ("listed_rays", ctypes.c_uint64),
+        ("group_tests", ctypes.c_uint64),
+        ("bound_tests", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
 class vcrt_camera_stats(ctypes.Structure):
     _fields_ = [
         ("host_ms", ctypes.c_double),
@@ -262,6 +274,16 @@ SIGNATURES = {
                                                   ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.c_void_p,
                                                   ctypes.POINTER(vcrt_ray_stats)]),
+    "vcrt_draw_features": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(vcrt_feature_stats)]),
+    "vcrt_draw_features_device": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32,
+                                                   ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p,
+                                                   ctypes.POINTER(vcrt_feature_stats)]),
+    "vcrt_frame_rays": (ctypes.c_int32, [ctypes.POINTER(vcrt_render_desc), ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

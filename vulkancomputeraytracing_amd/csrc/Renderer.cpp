@@ -63,3 +63,9 @@ VkResult UpdateSpheres(IN const vcrt_sphere* spheres, IN int32_t count) {
     if (r == VK_SUCCESS && g_scene_set) g_scene.assign(spheres, spheres + count);
     return r;
 }
+
+VkResult DrawFeatures(IN uint32_t first, IN uint32_t n, OUT float* albedo, OUT float* normal_depth,
+                      OUT int32_t* sphere) {
+    return static_cast<VkResult>(
+        vcrt_draw_features(first, n, albedo, normal_depth, sphere, nullptr));
+}

@@ -87,6 +87,22 @@ struct RendererState {
     float* d_oq_tmax = nullptr;
     uint8_t* d_oq_occluded = nullptr;
     size_t oq_tmax_cap = 0, oq_occluded_cap = 0;  // in rays
+    // feature buffers (vcrt_draw_features; null: the code object predates them): the jitter
+    // terms and lens origins of the call's own sample indices (the frame's tables are left
+    // alone), the host call's staging planes and the tallies' slots; kept and grown only
+    hipFunction_t k_frame_features = nullptr;
+    bool feature_lists = true;  // VCRT_FEATURE_LISTS=0: no ray takes the camera-ray lists
+    float2* d_ft_jitter_in = nullptr;
+    float4* d_ft_jitter = nullptr;
+    float4* d_ft_lens = nullptr;
+    size_t ft_jitter_in_cap = 0, ft_jitter_cap = 0, ft_lens_cap = 0;  // in samples
+    std::vector<float2> h_ft_jitter;
+    std::vector<float4> h_ft_lens;
+    float4* d_ft_albedo = nullptr;
+    float4* d_ft_normal_depth = nullptr;
+    int32_t* d_ft_sphere = nullptr;
+    size_t ft_albedo_cap = 0, ft_normal_depth_cap = 0, ft_sphere_cap = 0;  // in elements
+    void* d_ft_counters = nullptr;
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -679,6 +695,11 @@ VkResult bind_kernels() {
     if (hipModuleGetFunction(&g.k_occlude_rays, m, "vcrt_occlude_rays") != hipSuccess) {
         (void)hipGetLastError();
         g.k_occlude_rays = nullptr;
+    }
+    // optional: the feature-buffer kernel (vcrt_draw_features answers the same)
+    if (hipModuleGetFunction(&g.k_frame_features, m, "vcrt_frame_features") != hipSuccess) {
+        (void)hipGetLastError();
+        g.k_frame_features = nullptr;
     }
     // optional: the camera-list kernels (vcrt_set_camera then runs the host builders)
     const std::pair<hipFunction_t*, const char*> list_kernels[] = {
@@ -1480,6 +1501,7 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
         return fail(r);
     if (const char* e = std::getenv("VCRT_DEBUG_STATS")) g.debug_stats = std::atoi(e);
     if (const char* e = std::getenv("VCRT_PRIMARY_LISTS")) g.primary_lists = std::atoi(e) != 0;
+    if (const char* e = std::getenv("VCRT_FEATURE_LISTS")) g.feature_lists = std::atoi(e) != 0;
     if (const char* e = std::getenv("VCRT_CULL_LANE_TABLES"))
         g.cull_lane_tables = std::strcmp(e, "lds") == 0      ? 1
                              : std::strcmp(e, "global") == 0 ? 2
@@ -2183,6 +2205,13 @@ vcrt_result vcrt_end(void) {
     if (g.d_rq_counters) (void)hipFree(g.d_rq_counters);
     if (g.d_oq_tmax) (void)hipFree(g.d_oq_tmax);
     if (g.d_oq_occluded) (void)hipFree(g.d_oq_occluded);
+    if (g.d_ft_jitter_in) (void)hipFree(g.d_ft_jitter_in);
+    if (g.d_ft_jitter) (void)hipFree(g.d_ft_jitter);
+    if (g.d_ft_lens) (void)hipFree(g.d_ft_lens);
+    if (g.d_ft_albedo) (void)hipFree(g.d_ft_albedo);
+    if (g.d_ft_normal_depth) (void)hipFree(g.d_ft_normal_depth);
+    if (g.d_ft_sphere) (void)hipFree(g.d_ft_sphere);
+    if (g.d_ft_counters) (void)hipFree(g.d_ft_counters);
     if (g.d_cl_boxes) (void)hipFree(g.d_cl_boxes);
     if (g.d_cl_spheres) (void)hipFree(g.d_cl_spheres);
     if (g.d_cl_counts) (void)hipFree(g.d_cl_counts);
@@ -2412,6 +2441,198 @@ vcrt_result vcrt_occlude_rays(const float* origins, const float* dirs, const flo
     if (r != VK_SUCCESS || n == 0) return r;
     VCRT_TRY(hipMemcpyAsync(occluded, g.d_oq_occluded, n, hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
+    return VCRT_SUCCESS;
+}
+
+// ---- feature buffers ----------------------------------------------------------------------
+
+namespace {
+
+constexpr uint64_t kFeatureMaxIndex = uint64_t{1} << 19;  // vcrt_lens_offsets' index bound
+// FeatureParams.tallies: slots of 64 B (listed rays, group tests, box tests), summed here
+constexpr size_t kFeatureCounterBytes = 64 * vcrt::kFeatureTallySlots;
+
+// The arguments both forms of the call check, before anything touches the GPU. The arguments'
+// own faults come first, so that they read the same with and without a renderer.
+vcrt_result feature_args(uint32_t first, uint32_t n, const void* albedo, const void* normal_depth,
+                         const void* sphere) {
+    if (!albedo && !normal_depth && !sphere) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (n == 0 || static_cast<uint64_t>(first) + n > kFeatureMaxIndex)
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    return VCRT_SUCCESS;
+}
+
+// The jitter terms (vcrt_setup_jitter, the frame's kernel) and, for a lens renderer, the lens
+// origins (the frame's host operations: setup_jitter above) of sample indices first .. first +
+// n - 1 in the call's own tables.
+VkResult feature_tables(uint32_t first, uint32_t n) {
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_jitter_in), &g.ft_jitter_in_cap, n,
+                  sizeof(float2)));
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_jitter), &g.ft_jitter_cap, n, sizeof(float4)));
+    g.h_ft_jitter.resize(n);
+    make_jitter(first, static_cast<int>(n), g.h_ft_jitter.data());
+    VCRT_TRY(hipMemcpyAsync(g.d_ft_jitter_in, g.h_ft_jitter.data(), sizeof(float2) * n,
+                            hipMemcpyHostToDevice, g.stream));
+    if (lens_on()) {
+        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_lens), &g.ft_lens_cap, n, sizeof(float4)));
+        g.h_ft_lens.resize(n);
+        for (uint32_t k = 0; k < n; k++) {
+            const vcrt::f3 o = vcrt::add(
+                g.cam.center, vcrt::lens_offset(first + k, g.desc.lens_radius, g.cam.u, g.cam.v));
+            g.h_ft_lens[k] = make_float4(o.x, o.y, o.z, 0.0f);
+        }
+        VCRT_TRY(hipMemcpyAsync(g.d_ft_lens, g.h_ft_lens.data(), sizeof(float4) * n,
+                                hipMemcpyHostToDevice, g.stream));
+    }
+    vcrt::SetupJitterParams sp{};
+    sp.jitter_in = g.d_ft_jitter_in;
+    sp.jitter = g.d_ft_jitter;
+    sp.nsamples = n;
+    const std::array<float, 12> cam = camera_array();
+    for (int i = 0; i < 12; i++) sp.cam[i] = cam[i];
+    sp.corner = nullptr;
+    sp.slots = g.total_pixels;
+    sp.tiles_x = g.tiles_x;
+    sp.rank = static_cast<uint32_t>(g.desc.rank);
+    sp.world = static_cast<uint32_t>(g.desc.world_size);
+    return launch(g.k_setup_jitter, std::min<uint32_t>((n + 255u) / 256u, 8192u), 256, 0, sp);
+}
+
+// The launch on device pointers (checked by the callers): one wave per local tile; returns when
+// the kernel is done.
+VkResult draw_features_device(uint32_t first, uint32_t n, float* albedo, float* normal_depth,
+                              int32_t* sphere, vcrt_feature_stats* stats) {
+    if (stats) {
+        *stats = vcrt_feature_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_features");
+    }
+    if (!g.d_ft_counters) VCRT_TRY(hipMalloc(&g.d_ft_counters, kFeatureCounterBytes));
+    const VkResult t = feature_tables(first, n);
+    if (t != VK_SUCCESS) return t;
+    vcrt::FeatureParams p{};
+    scene_params(p.scene);
+    p.scene.jitter = g.d_ft_jitter;
+    p.scene.lens = lens_on() ? g.d_ft_lens : nullptr;
+    p.scene.corner = g.d_corner;
+    p.scene.prim_info = g.d_prim_info;
+    p.scene.prim_ids = g.d_prim_ids;
+    p.scene.cam_rec = g.d_cam_rec;
+    p.scene.width = g.desc.width;
+    p.scene.height = g.desc.height;
+    p.scene.spp = static_cast<int32_t>(n);
+    p.scene.max_depth = 1;
+    p.scene.rank = g.desc.rank;
+    p.scene.world = g.desc.world_size;
+    p.scene.tiles_x = g.tiles_x;
+    p.scene.local_tiles = g.local_tiles;
+    const std::array<float, 12> cam = camera_array();
+    for (int i = 0; i < 12; i++) p.scene.cam[i] = cam[i];
+    // the lists go to a frame whose camera centre passes the range guard (trace_frame)
+    if (!(g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
+          std::fabs(cam[11]) <= 0x1p30f))
+        p.scene.prim_info = nullptr;
+    p.albedo = reinterpret_cast<float4*>(albedo);
+    p.normal_depth = reinterpret_cast<float4*>(normal_depth);
+    p.sphere = sphere;
+    p.n = n;
+    p.use_lists = g.feature_lists ? 1u : 0u;
+    p.tallies = static_cast<unsigned long long*>(g.d_ft_counters);
+    std::vector<unsigned long long> slots(kFeatureCounterBytes / 8, 0ull);
+    if (g.local_tiles > 0) {
+        VCRT_TRY(hipMemsetAsync(g.d_ft_counters, 0, kFeatureCounterBytes, g.stream));
+        VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
+        const VkResult r = launch(g.k_frame_features, (g.local_tiles + 3u) / 4u, 256, 0, p);
+        if (r != VK_SUCCESS) return r;
+        VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
+        if (stats)
+            VCRT_TRY(hipMemcpyAsync(slots.data(), g.d_ft_counters, kFeatureCounterBytes,
+                                    hipMemcpyDeviceToHost, g.stream));
+    }
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) {
+        unsigned long long counters[3] = {0, 0, 0};
+        for (size_t s = 0; s < slots.size(); s += 8)
+            for (int c = 0; c < 3; c++) counters[c] += slots[s + c];
+        float ms = 0.f;
+        if (g.local_tiles > 0) VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+        stats->kernel_ms = ms;
+        stats->rays = g.local_pixels * n;
+        stats->listed_rays = counters[0];
+        stats->group_tests = counters[1];
+        stats->bound_tests = counters[2];
+    }
+    return VK_SUCCESS;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+vcrt_result vcrt_draw_features_device(uint32_t first, uint32_t n, float* albedo,
+                                      float* normal_depth, int32_t* sphere,
+                                      vcrt_feature_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = feature_args(first, n, albedo, normal_depth, sphere);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernel's 16-byte stores (and the ids' 4-byte ones)
+    if (((reinterpret_cast<uintptr_t>(albedo) | reinterpret_cast<uintptr_t>(normal_depth)) & 15u) ||
+        (reinterpret_cast<uintptr_t>(sphere) & 3u))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_frame_features) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = draw_features_device(first, n, albedo, normal_depth, sphere, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_draw_features(uint32_t first, uint32_t n, float* albedo, float* normal_depth,
+                               int32_t* sphere, vcrt_feature_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = feature_args(first, n, albedo, normal_depth, sphere);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.k_frame_features) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t elems = g.local_elems;
+    if (albedo)
+        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_albedo), &g.ft_albedo_cap, elems,
+                      sizeof(float4)));
+    if (normal_depth)
+        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_normal_depth), &g.ft_normal_depth_cap,
+                      elems, sizeof(float4)));
+    if (sphere)
+        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_sphere), &g.ft_sphere_cap, elems,
+                      sizeof(int32_t)));
+    // packed tiles: the slots outside the frame keep what the caller's planes hold
+    if (g.desc.world_size > 1 && elems) {
+        if (albedo)
+            VCRT_TRY(hipMemcpyAsync(g.d_ft_albedo, albedo, sizeof(float4) * elems,
+                                    hipMemcpyHostToDevice, g.stream));
+        if (normal_depth)
+            VCRT_TRY(hipMemcpyAsync(g.d_ft_normal_depth, normal_depth, sizeof(float4) * elems,
+                                    hipMemcpyHostToDevice, g.stream));
+        if (sphere)
+            VCRT_TRY(hipMemcpyAsync(g.d_ft_sphere, sphere, sizeof(int32_t) * elems,
+                                    hipMemcpyHostToDevice, g.stream));
+    }
+    const VkResult r = draw_features_device(
+        first, n, albedo ? reinterpret_cast<float*>(g.d_ft_albedo) : nullptr,
+        normal_depth ? reinterpret_cast<float*>(g.d_ft_normal_depth) : nullptr,
+        sphere ? g.d_ft_sphere : nullptr, stats);
+    if (r != VK_SUCCESS) return r;
+    if (elems) {
+        if (albedo)
+            VCRT_TRY(hipMemcpyAsync(albedo, g.d_ft_albedo, sizeof(float4) * elems,
+                                    hipMemcpyDeviceToHost, g.stream));
+        if (normal_depth)
+            VCRT_TRY(hipMemcpyAsync(normal_depth, g.d_ft_normal_depth, sizeof(float4) * elems,
+                                    hipMemcpyDeviceToHost, g.stream));
+        if (sphere)
+            VCRT_TRY(hipMemcpyAsync(sphere, g.d_ft_sphere, sizeof(int32_t) * elems,
+                                    hipMemcpyDeviceToHost, g.stream));
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+    }
+    if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;
 }
 
@@ -3259,6 +3480,48 @@ int32_t vcrt_lens_offsets(const vcrt_render_desc* desc, uint32_t first, uint32_t
         out[2] = o.z;
     }
     return static_cast<int32_t>(count);
+}
+
+int32_t vcrt_frame_rays(const vcrt_render_desc* desc, const int32_t* xy, int32_t npixels,
+                        uint32_t first, uint32_t n, float* origins, float* dirs) {
+    vcrt_render_desc d;
+    if (!read_desc(desc, d) || !desc_valid(d) || npixels < 0 ||
+        (npixels > 0 && (!xy || !origins || !dirs)))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (n == 0 || static_cast<uint64_t>(first) + n > (uint64_t{1} << 19))
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    for (int32_t p = 0; p < npixels; p++)
+        if (xy[2 * p] < 0 || xy[2 * p] >= d.width || xy[2 * p + 1] < 0 || xy[2 * p + 1] >= d.height)
+            return VCRT_ERROR_INITIALIZATION_FAILED;
+    const vcrt::Camera cm = desc_camera(d);
+    // per sample index: the jitter term (tracer.hip viewport_jitter) and the ray's origin
+    std::vector<float2> jt(n);
+    make_jitter(first, static_cast<int>(n), jt.data());
+    std::vector<vcrt::f3> term(n), origin(n);
+    for (uint32_t k = 0; k < n; k++) {
+        term[k] = vcrt::add(vcrt::scale(jt[k].x, cm.delta_u), vcrt::scale(jt[k].y, cm.delta_v));
+        origin[k] = d.lens_radius > 0.0f
+                        ? vcrt::add(cm.center,
+                                    vcrt::lens_offset(first + k, d.lens_radius, cm.u, cm.v))
+                        : cm.center;
+    }
+    for (int32_t p = 0; p < npixels; p++) {
+        // tracer.hip viewport_corner
+        const vcrt::f3 corner = vcrt::add(
+            vcrt::add(cm.pixel00, vcrt::scale(static_cast<float>(xy[2 * p]), cm.delta_u)),
+            vcrt::scale(static_cast<float>(xy[2 * p + 1]), cm.delta_v));
+        for (uint32_t k = 0; k < n; k++) {
+            const vcrt::f3 dir = vcrt::sub(vcrt::add(corner, term[k]), origin[k]);
+            const size_t at = 3 * (static_cast<size_t>(p) * n + k);
+            origins[at + 0] = origin[k].x;
+            origins[at + 1] = origin[k].y;
+            origins[at + 2] = origin[k].z;
+            dirs[at + 0] = dir.x;
+            dirs[at + 1] = dir.y;
+            dirs[at + 2] = dir.z;
+        }
+    }
+    return npixels;
 }
 
 float vcrt_canonical_sin(float x) { return vcrt::sin_canonical(x); }

@@ -3931,3 +3931,160 @@ extern "C" __global__ __launch_bounds__(1024) void vcrt_trace_cull_flat_boxes_le
     trace_impl<false, false, 6, true, true>(p, lds_tab);
 }
 #endif
+
+// ---------------------------------------------------------------------------------------------
+// Feature buffers (vcrt_draw_features): first-hit albedo, normal, depth, coverage and sphere id
+// of the frame's own camera rays, a code-generation unit of its own (Makefile, part 8).
+// One wave per local 8x8 tile, one lane per slot; a lane runs its pixel's n samples in index
+// order and keeps the eight sums in registers, so the bits depend on the sample order alone.
+// Lanes of slots outside the frame sit out (the scans' ballots see the active lanes only).
+// A sample's ray is trace_impl's camera ray: (corner + jitter_i) - origin, the origin the camera
+// centre or, with a lens, the table's centre + offset_i. Its first hit comes from one of three
+// routes, which give the same sphere and t (facts (1)-(4) above):
+//  * the camera-ray lists (a pinhole frame that has them, the lane's quarter listed, guard_a):
+//    the big groups' camera-relative records, then the quarter's listed pairs -- the helper
+//    calls of trace_impl's camera fast trace;
+//  * else what vcrt_trace_rays runs: the per-lane culled scan on the global tables when the
+//    scene has them and every ray the wave's remaining lanes hold is in the guarded range,
+//  * else the linear scan.
+#if !defined(VCRT_PART) || VCRT_PART == 8
+extern "C" __global__ __launch_bounds__(256) void vcrt_frame_features(FeatureParams p_arg) {
+    // the arguments through a pointer to the kernarg segment, as trace_impl reads them
+    (void)p_arg;
+    const FeatureParams& p = *reinterpret_cast<const FeatureParams*>(
+        (__attribute__((address_space(4))) const FeatureParams*)
+            __builtin_amdgcn_kernarg_segment_ptr());
+    const TraceParams& S = p.scene;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lt = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (lt >= S.local_tiles) return;  // (the whole wave)
+    const uint32_t q = lt * 64u + lane;
+    const Pixel px = pixel_of(q, (uint32_t)S.width, (uint32_t)S.height, S.tiles_x,
+                              (uint32_t)S.world, (uint32_t)S.rank);
+    const uint32_t nsamples = p.n;
+    const bool lens = S.lens != nullptr;
+    uint32_t w_halves = 0u, w_bounds = 0u, listed = 0u;
+    if (px.valid) {
+        const f3 p00 = mk(S.cam[0], S.cam[1], S.cam[2]);
+        const f3 du = mk(S.cam[3], S.cam[4], S.cam[5]);
+        const f3 dv = mk(S.cam[6], S.cam[7], S.cam[8]);
+        const f3 cam = mk(S.cam[9], S.cam[10], S.cam[11]);
+        // shader.comp:43's pixel corner, vcrt_setup_jitter's operations (TraceParams.corner)
+        const f3 corner = viewport_corner(p00, du, dv, px.x, px.y);
+        // the sphere list of the lane's 4x4 quarter (slot 8 y + x), as trace_impl reads it
+        uint32_t inf = 15u;
+        if (p.use_lists != 0u && !lens && S.prim_info != nullptr)
+            inf = S.prim_info[2u * (lt * 4u + (((lane >> 5) & 1u) << 1) + ((lane >> 2) & 1u)) + 1u];
+        const int n = S.nspheres;
+        const float4* tgroup = S.cgroup + 5 * S.nbig;  // the hierarchy's group records
+        cfloat4* jitter = (cfloat4*)S.jitter;           // wave-uniform indices: scalar loads
+        cfloat4* lens_tab = (cfloat4*)S.lens;
+        f3 sum_a = mk(0.f, 0.f, 0.f), sum_n = mk(0.f, 0.f, 0.f);
+        float sum_c = 0.f, sum_z = 0.f;
+        int s_first = -1;
+        for (uint32_t k = 0; k < nsamples; ++k) {
+            const float4 j = jitter[k];
+            f3 o = cam;
+            if (lens) {
+                const float4 l = lens_tab[k];
+                o = mk(l.x, l.y, l.z);
+            }
+            const f3 d = sub(add(corner, mk(j.x, j.y, j.z)), o);
+            const float aa = dot(d, d);
+            float max_t = kInfinity;
+            int best = -1;
+            // (a pinhole ray starts at the camera centre: the host hands out prim_info only to
+            // a bounded scene and a centre within 2^30, the other half of the range guard)
+            const bool cam_now = (inf & 15u) != 15u && guard_a(aa);
+            if (cam_now) {
+                ++listed;
+                cfloat4* crec = (cfloat4*)S.cam_rec;
+                const float ya = recip_a(aa);
+                const v2f dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z}, a2 = {aa, aa};
+                for (int gb = 0; gb < S.nbig; ++gb)  // the big spheres (scalar loads)
+                    exact_group_uniform_cam(crec + 4 * gb, (cfloat4*)S.cgroup + 5 * gb, dx, dy,
+                                            dz, a2, aa, ya, max_t, best);
+                // the quarter's listed spheres, two per record (primary.cpp)
+                const uint32_t cnt = inf & 15u;
+                const float4* lr = S.cam_rec + 4u * (uint32_t)S.nbig + 3u * (inf >> 4);
+                uint32_t iters = 0u;
+                for (uint32_t m = 0; 2u * m < cnt; ++m) {
+                    ++iters;
+                    const float4 q0 = lr[3u * m], q1 = lr[3u * m + 1u], id = lr[3u * m + 2u];
+                    v2f hb, cc, dc;
+                    pair_disc_cam(dx, dy, dz, a2, q0, q1, hb, cc, dc);
+                    if (__float_as_int(hit_sign(hb.x, cc.x, dc.x)) < 0)
+                        consider(candidate_t_fast(hb.x, dc.x, aa, ya), __float_as_int(id.x),
+                                 max_t, best);
+                    if (__float_as_int(hit_sign(hb.y, cc.y, dc.y)) < 0)
+                        consider(candidate_t_fast(hb.y, dc.y, aa, ya), __float_as_int(id.y),
+                                 max_t, best);
+                }
+                // issued work as the frame counts it: a pair test is half a group test
+                tally(w_halves, 2u * (uint32_t)S.nbig + wave_max_small<3>(iters));
+            } else {
+                uint32_t hit_groups = 0u, lane_cnt = 0u;
+                const bool guarded = (S.flags & kFlagSceneBounded) != 0 && aa >= 0x1p-20f &&
+                                     aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f &&
+                                     fabsf(o.y) <= 0x1p30f && fabsf(o.z) <= 0x1p30f;
+                if (S.ncgroups > 0 && __ballot(!guarded) == 0u) {
+                    scan_culled_lane<false>(S, S.cbound, tgroup, o, d, max_t, best, w_halves,
+                                            w_bounds, lane_cnt, hit_groups);
+                } else {
+                    scan_spheres<false>(S, nullptr, n, o, d, max_t, best, hit_groups);
+                    tally(w_halves, 2u * (uint32_t)((n + 3) >> 2));
+                }
+            }
+            // ---- the sample's rows: sky (functions.glsl:85-89) or the hit's ----
+            if (best < 0) {
+                const float len = sqrt_fast(aa);  // length(d)
+                sum_a = add(sum_a, sky_factor(d.y / len));
+                // (normal, depth and coverage add +0)
+            } else {
+                const float4 cr = S.center_radius[best], sh = S.shade[best];
+                const float4 mat = S.material[best];
+                const f3 point = add(scale(max_t, d), o);
+                // shade_segment's normal: the unscaled division, else the full one (same bits)
+                const f3 pcv = sub(point, mk(cr.x, cr.y, cr.z));
+                const float yr = recip_a(cr.w);
+                f3 normal = mk(div_a(pcv.x, cr.w, yr), div_a(pcv.y, cr.w, yr),
+                               div_a(pcv.z, cr.w, yr));
+                const float nmin = fminf(fminf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+                const float nmax = fmaxf(fmaxf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+                if (!((S.flags & kFlagRadiiSafe) != 0u && nmin >= 0x1p-40f && nmax <= 0x1p30f)) {
+                    asm volatile("");
+                    normal = divs(pcv, cr.w);
+                }
+                const bool glass = (int)mat.x == 3;
+                sum_a = add(sum_a, glass ? mk(1.f, 1.f, 1.f) : mk(sh.x, sh.y, sh.z));
+                sum_n = add(sum_n, normal);
+                sum_z = sum_z + max_t;
+                sum_c = sum_c + 1.0f;
+            }
+            if (k == 0u) s_first = best;
+        }
+        const float fn = (float)nsamples;
+        if (p.albedo)
+            p.albedo[px.out_index] =
+                make_float4(sum_a.x / fn, sum_a.y / fn, sum_a.z / fn, sum_c / fn);
+        if (p.normal_depth)
+            p.normal_depth[px.out_index] =
+                make_float4(sum_n.x / fn, sum_n.y / fn, sum_n.z / fn, sum_z / fn);
+        if (p.sphere) p.sphere[px.out_index] = s_first;
+    }
+    // one atomic per wave and tally, into the block's slot (FeatureParams.tallies)
+    unsigned long long nl = listed, wh = w_halves, wb = w_bounds;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nl += __shfl_xor(nl, off);
+        wh += __shfl_xor(wh, off);
+        wb += __shfl_xor(wb, off);
+    }
+    if (lane == 0) {
+        unsigned long long* slot = p.tallies + 8u * (blockIdx.x & (kFeatureTallySlots - 1u));
+        if (nl) atomicAdd(slot + 0, nl);
+        if (wh) atomicAdd(slot + 1, wh / 2u);
+        if (wb) atomicAdd(slot + 2, wb);
+    }
+}
+#endif

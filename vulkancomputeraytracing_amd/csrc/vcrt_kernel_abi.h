@@ -247,6 +247,29 @@ struct OcclusionParams {
                                   //   boxes tested (per wave); zeroed before the launch
 };
 
+// Feature buffers (vcrt_draw_features): first-hit albedo, normal, depth, coverage and sphere id
+// of the frame's own camera rays, averaged per pixel. The scene block is a TraceParams filled as
+// a frame's is (scene_params, the camera lists prim_info / cam_rec, corner, cam, width, height,
+// rank, world, tiles_x, local_tiles); its jitter and lens tables are the call's own, built for
+// the sample indices first .. first + n - 1 and indexed from 0. One wave per local tile, one
+// lane per slot; the outputs are indexed as the rank-local framebuffer is.
+struct FeatureParams {
+    TraceParams scene;
+    float4* albedo;        // [elements] (sum a_i / n, sum c_i / n), or null
+    float4* normal_depth;  // [elements] (sum n_i / n, sum t_i / n), or null
+    int32_t* sphere;       // [elements] the sphere of the first sample index (-1: sky), or null
+    uint32_t n;            // samples per pixel of the call, >= 1
+    uint32_t use_lists;    // 0: every ray takes the query kernel's scans (VCRT_FEATURE_LISTS=0)
+    unsigned long long* tallies;  // [kFeatureTallySlots][8]: per slot (64 B), [0] rays answered
+                                  //   from the camera-ray lists, [1] groups of four put through
+                                  //   the exact test (per wave), [2] boxes tested (per wave);
+                                  //   zeroed before the launch, summed over the slots by the host
+};
+// A frame has one short wave per tile (130 000 at 4K), and atomics on one address serialise
+// (measured 8 ns each: three shared counters cost 0.79 ms at 1080p, whatever the samples): block
+// b adds to slot b % kFeatureTallySlots, each slot a cache line of its own.
+constexpr uint32_t kFeatureTallySlots = 256;
+
 // TraceParams.jitter from the host's jitter (vcrt_math.h rand2) and the camera: run at
 // vcrt_begin and for each progressive frame.
 struct SetupJitterParams {

@@ -1,7 +1,8 @@
 // vcrt_render -- headless replacement of the reference's main()
 // (VulkanComputeRayTracing.cpp:17-42): Begin -> DrawNextFrame x N -> End, then optionally writes
 // the frame as PFM (linear rgba32f, as the compute image holds it) or PPM (sRGB8 encoded on the
-// GPU, as the B8G8R8A8_SRGB swapchain shows it: Frontend.cpp:43).
+// GPU, as the B8G8R8A8_SRGB swapchain shows it: Frontend.cpp:43). --features PREFIX adds the
+// frame's guide buffers (vcrt_draw_features) as PREFIX_albedo.ppm and PREFIX_normal.ppm.
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -18,8 +19,29 @@ int usage() {
     std::fprintf(stderr,
                  "usage: vcrt_render [--width W] [--height H] [--spp N] [--depth D] "
                  "[--scene final|three|red|stress4096] [--frames F] [--progressive 0|1] [--device I] "
-                 "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm]\n");
+                 "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm] "
+                 "[--features PREFIX] [--feature-samples N]\n");
     return 2;
+}
+
+// The frame as PFM (rgba, bottom row first) or PPM (rgba8, top row first), three channels.
+bool write_image(const std::string& path, int width, int height, bool pfm,
+                 const std::vector<float>& rgba, const std::vector<uint8_t>& rgba8) {
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::fprintf(f, pfm ? "PF\n%d %d\n-1.0\n" : "P6\n%d %d\n255\n", width, height);
+    for (int y = pfm ? height - 1 : 0; pfm ? y >= 0 : y < height; y += pfm ? -1 : 1) {
+        for (int x = 0; x < width; x++) {
+            const size_t i = static_cast<size_t>(y) * width + x;
+            if (pfm) std::fwrite(&rgba[4 * i], sizeof(float), 3, f);
+            else std::fwrite(&rgba8[4 * i], 1, 3, f);
+        }
+    }
+    return std::fclose(f) == 0;
+}
+
+uint8_t unit_byte(float v) {  // clamp to [0, 1] (NaN: 0), round to nearest of 255 v
+    return static_cast<uint8_t>((v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f) * 255.0f + 0.5f);
 }
 
 }  // namespace
@@ -29,13 +51,15 @@ int main(int argc, char** argv) {
     vcrt_default_desc(&desc);
     int scene = VCRT_SCENE_FINAL, frames = 1;
     double orbit = 0.0;  // degrees about the world y axis through lookat, per frame
-    std::string out;
+    std::string out, features;
+    int feature_samples = 0;  // 0: the description's spp
     bool configured = false;  // any option that changes the description or the scene
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (i + 1 >= argc) return usage();
         const char* v = argv[++i];
-        configured = configured || (a != "--out" && a != "--frames");
+        configured = configured || (a != "--out" && a != "--frames" && a != "--features" &&
+                                    a != "--feature-samples");
         if (a == "--width") desc.width = std::atoi(v);
         else if (a == "--height") desc.height = std::atoi(v);
         else if (a == "--spp") desc.samples_per_pixel = std::atoi(v);
@@ -46,6 +70,8 @@ int main(int argc, char** argv) {
         else if (a == "--lens-radius") desc.lens_radius = std::strtof(v, nullptr);  // thin lens
         else if (a == "--orbit") orbit = std::strtod(v, nullptr);
         else if (a == "--out") out = v;
+        else if (a == "--features") features = v;
+        else if (a == "--feature-samples") feature_samples = std::atoi(v);
         else if (a == "--scene") {
             const std::string s = v;
             scene = s == "final" ? VCRT_SCENE_FINAL : s == "three" ? VCRT_SCENE_THREE
@@ -98,23 +124,35 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> srgb(pfm ? 0 : n * 4);
         r = pfm ? ReadFramebuffer(rgba.data(), rgba.size())
                 : vcrt_read_framebuffer_srgb8(srgb.data(), srgb.size());  // GPU sRGB encode
-        FILE* f = r == VK_SUCCESS ? std::fopen(out.c_str(), "wb") : nullptr;
-        if (f) {
-            std::fprintf(f, pfm ? "PF\n%d %d\n-1.0\n" : "P6\n%d %d\n255\n", desc.width,
-                         desc.height);
-            for (int y = pfm ? desc.height - 1 : 0; pfm ? y >= 0 : y < desc.height;
-                 y += pfm ? -1 : 1) {
-                for (int x = 0; x < desc.width; x++) {
-                    const size_t i = static_cast<size_t>(y) * desc.width + x;
-                    if (pfm) std::fwrite(&rgba[4 * i], sizeof(float), 3, f);
-                    else std::fwrite(&srgb[4 * i], 1, 3, f);
-                }
-            }
-            std::fclose(f);
-        } else {
+        if (r != VK_SUCCESS || !write_image(out, desc.width, desc.height, pfm, rgba, srgb)) {
             std::fprintf(stderr, "cannot write %s: %s\n", out.c_str(),
                          r == VK_SUCCESS ? std::strerror(errno) : vcrt_result_string(r));
             if (r == VK_SUCCESS) r = VK_ERROR_UNKNOWN;
+        }
+    }
+    if (r == VK_SUCCESS && !features.empty()) {
+        // the guide buffers of the last frame's camera: albedo as it is (linear, clamped), the
+        // averaged normal mapped (n + 1) / 2
+        const size_t n = static_cast<size_t>(desc.width) * desc.height;
+        const uint32_t samples = static_cast<uint32_t>(
+            feature_samples > 0 ? feature_samples : desc.samples_per_pixel);
+        std::vector<float> albedo(4 * n), normal(4 * n);
+        r = DrawFeatures(0, samples, albedo.data(), normal.data(), nullptr);
+        if (r == VK_SUCCESS) {
+            std::vector<uint8_t> a8(4 * n), n8(4 * n);
+            for (size_t i = 0; i < 4 * n; i++) {
+                a8[i] = unit_byte(albedo[i]);
+                n8[i] = unit_byte(0.5f * (normal[i] + 1.0f));
+            }
+            const std::vector<float> none;
+            if (!write_image(features + "_albedo.ppm", desc.width, desc.height, false, none, a8) ||
+                !write_image(features + "_normal.ppm", desc.width, desc.height, false, none, n8)) {
+                std::fprintf(stderr, "cannot write %s_*.ppm: %s\n", features.c_str(),
+                             std::strerror(errno));
+                r = VK_ERROR_UNKNOWN;
+            }
+        } else {
+            std::fprintf(stderr, "DrawFeatures: %s\n", vcrt_result_string(r));
         }
     }
     EndRenderingOperation();

@@ -116,6 +116,45 @@ def lens_offsets(desc: RenderDesc, first: int, count: int) -> np.ndarray:
     return out
 
 
+MAX_SAMPLE_INDEX = 1 << 19  # sample indices a renderer admits (vcrt.h vcrt_lens_offsets)
+
+
+def _check_sample_range(first, n) -> tuple[int, int]:
+    """(first, n) of a range of sample indices, validated before any native call."""
+    try:
+        first, n = int(first), int(n)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"first, samples: integers expected ({e})") from None
+    if first < 0:
+        raise ValueError("first must be >= 0")
+    if n < 1:
+        raise ValueError("at least one sample")
+    if first + n > MAX_SAMPLE_INDEX:
+        raise ValueError("first + samples must not exceed 2^19")
+    return first, n
+
+
+def frame_rays(desc: RenderDesc, xy, first: int, n: int) -> tuple[np.ndarray, np.ndarray]:
+    """The rays a frame of `desc` traces for the pixels xy [npixels, 2] (x, y) and the sample
+    indices first .. first + n - 1 (vcrt_frame_rays: host only, no GPU), the definition behind
+    Renderer.draw_features: (origins, dirs), float32 [npixels, n, 3] each."""
+    first, n = _check_sample_range(first, n)
+    try:
+        xy = np.ascontiguousarray(xy, dtype=np.int32)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"xy: not convertible to an int32 array ({e})") from None
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError(f"xy: shape [npixels, 2] expected, got {tuple(xy.shape)}")
+    if len(xy) and (xy.min() < 0 or xy[:, 0].max() >= desc.width or xy[:, 1].max() >= desc.height):
+        raise ValueError("xy: a pixel outside the frame")
+    origins = np.zeros((len(xy), n, 3), np.float32)
+    dirs = np.zeros((len(xy), n, 3), np.float32)
+    N.check_count("vcrt_frame_rays", N.lib().vcrt_frame_rays(
+        ctypes.byref(desc.to_c()), xy.ctypes.data, len(xy), first, n, origins.ctypes.data,
+        dirs.ctypes.data))
+    return origins, dirs
+
+
 def pixel_scale_log2(max_abs_quantum_sum: float) -> int:
     """s of a pixel's quantization scale 2^s from its largest |quantum sum| (vcrt_pixel_scale_log2:
     host only, no GPU): 32 below 2^12, else the largest s with max * 2^s < 2^44. The oracle
@@ -497,7 +536,8 @@ class Renderer:
     def trace_rays(self, origins, dirs, max_depth: int | None = None, hits: bool = False,
                    stats: bool = False):
         """Radiance and first hit of caller-supplied rays against the current scene
-        (vcrt_trace_rays): any camera model, picking, probes, albedo and normal buffers.
+        (vcrt_trace_rays): any camera model, picking, probes (the frame's own albedo and normal
+        buffers: draw_features).
 
         numpy inputs [n, 3] (anything np.ascontiguousarray(..., float32) takes) go through the
         host call and return the radiance as float32 [n, 4] (rgb = ray_color, alpha 1) and, with
@@ -546,6 +586,62 @@ class Renderer:
                         "bound_tests": st.bound_tests, "kernel_ms": st.kernel_ms,
                         "kernel": st.kernel.decode() or "vcrt_trace_rays"})
         return out[0] if len(out) == 1 else tuple(out)
+
+    def draw_features(self, samples: int | None = None, first: int = 0, albedo: bool = True,
+                      normal: bool = True, sphere: bool = True, stats: bool = False,
+                      device: bool = False) -> dict:
+        """The guide buffers of the frame's own camera rays for a denoiser (vcrt_draw_features):
+        per pixel, over the sample indices first .. first + samples - 1 (samples=None: the
+        description's spp), "albedo" float32 [..., 4] (rgb the mean first-hit albedo, the sky's
+        colour on a miss, a the coverage), "normal_depth" float32 [..., 4] (xyz the mean first-hit
+        normal, w the mean t) and "sphere" int32 [...] (the sphere of sample index `first`, -1 the
+        sky), for the planes asked for (`normal` selects normal_depth). The leading shape is the
+        rank-local framebuffer's: [height, width] at world 1, else the packed tiles [tiles, 64]
+        (slots outside the frame read 0).
+
+        The arrays are numpy through the host call; with device=True they are torch tensors on
+        the renderer's device, filled through the device call after the caller's current stream
+        is synchronised (no host round trip). With stats=True the dict also holds "stats": rays,
+        listed_rays, group_tests, bound_tests, kernel_ms, host_ms, kernel. Argument errors raise
+        ValueError before any native call. The framebuffer, the accumulation and the frame
+        statistics are left alone."""
+        first, n = _check_sample_range(first, self.desc.samples_per_pixel if samples is None
+                                       else samples)
+        if not (albedo or normal or sphere):
+            raise ValueError("at least one of albedo, normal, sphere")
+        lib = self._L()
+        elems, tiles = self.local_layout()
+        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
+                else (tiles, 64))
+        want = (("albedo", albedo, 4), ("normal_depth", normal, 4), ("sphere", sphere, 0))
+        st = N.vcrt_feature_stats()
+        out, ptrs = {}, []
+        if device:
+            import torch
+            dev = torch.device("cuda", self.desc.device if self.desc.device >= 0
+                               else torch.cuda.current_device())
+            for name, on, c in want:
+                if on:
+                    out[name] = torch.zeros(lead + ((c,) if c else ()), device=dev,
+                                            dtype=torch.float32 if c else torch.int32)
+                ptrs.append(out[name].data_ptr() if on else None)
+            torch.cuda.current_stream(dev).synchronize()
+            N.check("vcrt_draw_features_device", lib.vcrt_draw_features_device(
+                first, n, *ptrs, ctypes.byref(st)))
+        else:
+            for name, on, c in want:
+                if on:
+                    out[name] = np.zeros(lead + ((c,) if c else ()),
+                                         dtype=np.float32 if c else np.int32)
+                ptrs.append(out[name].ctypes.data if on else None)
+            N.check("vcrt_draw_features", lib.vcrt_draw_features(
+                first, n, *ptrs, ctypes.byref(st)))
+        if stats:
+            out["stats"] = {"rays": st.rays, "listed_rays": st.listed_rays,
+                            "group_tests": st.group_tests, "bound_tests": st.bound_tests,
+                            "kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
+                            "kernel": st.kernel.decode()}
+        return out
 
     def occluded(self, origins, dirs, tmax=None, stats: bool = False):
         """Is anything in the way within each ray's reach (vcrt_occlude_rays)? Shadow rays,
