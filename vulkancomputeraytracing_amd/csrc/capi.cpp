@@ -1013,10 +1013,12 @@ KernelChoice select_kernel() {
     const uint32_t tab_lds = static_cast<uint32_t>(16 * (g.ncgroups / 2 * 4 + g.ncgroups * 5));
     // flat: near/far boxes (80 B per pair, 336 B per node of 4 pairs: 16 B of bank padding),
     // 80-B group records (the uint16 member indices inside), the footprint tables of the node
-    // level (672 B, or 1344 B beyond 16 nodes)
+    // level (672 B, or 1344 B beyond 16 nodes), and where the group-level tables leave their zero
+    // row no room in those bytes, 16 B for it (vcrt_kernel_abi.h group_foot_zero_pad; none at the
+    // final scene)
     const uint32_t tab_lds_flat =
         static_cast<uint32_t>(16 * (g.ncgroups / 8 * 21 + g.ncgroups * 5)) +
-        vcrt::foot_lds_bytes(g.ncgroups);
+        vcrt::foot_lds_bytes(g.ncgroups) + 16u * vcrt::group_foot_zero_pad(g.ncgroups);
     const bool lane_lds = tab_lds <= g.max_lds && g.cull_lane_tables != 2;
     const bool lane_wide = lane_lds && tab_lds > 32768u;
     int variant = g.desc.kernel_variant;
@@ -1614,9 +1616,17 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
                           "group footprint limit");
             if (static_cast<uint32_t>(ct.gf_cells) != vcrt::group_foot_cells(ct.ngroups))
                 return VCRT_ERROR_INITIALIZATION_FAILED;
-            VCRT_TRY(hipMalloc(&g.d_gf_tab, sizeof(uint32_t) * ct.gf_tab.size()));
-            VCRT_TRY(hipMemcpy(g.d_gf_tab, ct.gf_tab.data(), sizeof(uint32_t) * ct.gf_tab.size(),
-                               hipMemcpyHostToDevice));
+            // behind the four tables their zero row (tracer.hip group_foot_mask; cell 4 gf_n of
+            // the LDS image, select_kernel's tab_lds_flat): it must lie ahead of the records
+            const size_t tab_bytes = sizeof(uint32_t) * ct.gf_tab.size();
+            if (tab_bytes != 64u * static_cast<size_t>(ct.gf_cells) ||
+                tab_bytes + 16u > 16u * (static_cast<size_t>(ct.ngroups) / 8u * 21u +
+                                         vcrt::group_foot_zero_pad(ct.ngroups)) +
+                                      vcrt::foot_lds_bytes(ct.ngroups))
+                return VCRT_ERROR_INITIALIZATION_FAILED;
+            VCRT_TRY(hipMalloc(&g.d_gf_tab, tab_bytes + 16u));
+            VCRT_TRY(hipMemcpy(g.d_gf_tab, ct.gf_tab.data(), tab_bytes, hipMemcpyHostToDevice));
+            VCRT_TRY(hipMemset(reinterpret_cast<char*>(g.d_gf_tab) + tab_bytes, 0, 16u));
             std::memcpy(g.cgf_x, ct.gf_x, sizeof(g.cgf_x));
             std::memcpy(g.cgf_z, ct.gf_z, sizeof(g.cgf_z));
             std::memcpy(g.cgf_always, ct.gf_always, sizeof(g.cgf_always));
@@ -1864,7 +1874,9 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     // Deferred fetches (tracer.hip, the flat scans): the LDS-table flat scan waits until 4 lanes
     // need an item (at most one iteration): C3 -0.6 % kernel time (its 16 items per pixel make
     // the fetch frequent), C4 and the 8-way shards within 0.1 %, same bits; the global-table and
-    // boxes-in-LDS scans fetch at once (C5 +0.6 % with it). profiles/r06_ab_log.md.
+    // boxes-in-LDS scans fetch at once (C5 +0.6 % with it). profiles/r06_ab_log.md. Swept again
+    // on round 14's scan (profiles/r14_ab_log.md): fetching at once costs C4 0.3-0.5 ms and C3
+    // 0.15-0.2 ms, and no other rule is ahead of this one by more than the spread.
     const bool lds_flat = kc.base == g.k_trace_cull_flat;
     p.fetch_min = g.fetch_min > 0u ? g.fetch_min : (lds_flat ? 4u : 1u);
     p.fetch_wait = g.fetch_min > 0u ? g.fetch_wait : (lds_flat ? 1u : 0u);

@@ -1011,6 +1011,13 @@ static_assert(kPushCap >= 1u && kPushCap <= 15u, "light counts go through wave_p
 #endif
 constexpr bool kGroupPass2 = VCRT_GROUP_PASS2 != 0;
 constexpr bool kGroupPassDouble = VCRT_GROUP_PASS2 == 1;
+// The group footprint's mask by two v_bitop3 a word and a zero row in the tables' place of the
+// select per word (group_foot_mask). For A/B runs only: -DVCRT_FOOT_BITOP=0 builds the and /
+// select / or form, which never reads the zero row.
+#ifndef VCRT_FOOT_BITOP
+#define VCRT_FOOT_BITOP 1
+#endif
+constexpr bool kFootBitop = VCRT_FOOT_BITOP != 0;
 
 // Stack entries, by format kFmt:
 //   0 (narrow8, the LDS-table kernel, <= 256 groups): 16-bit owner << 8 | index, and 16-bit
@@ -1530,9 +1537,25 @@ __device__ __forceinline__ uint4 group_foot_mask(const TraceParams& p, const Box
     const uint32_t iza = cell(za, p.gf_z), izb = cell(zb, p.gf_z);
     const uint32_t x0 = min(ixa, ixb), x1 = max(ixa, ixb), z0 = min(iza, izb), z1 = max(iza, izb);
     const uint4* t = reinterpret_cast<const uint4*>(gt);
-    const uint4 a = t[x1], b = t[n + x0], c = t[2u * n + z1], e = t[3u * n + z0];
     const bool none = tb < ta;  // the ray never reaches the y extent: only `always`
     uint4 m;
+    if constexpr (kFootBitop) {
+        // such a ray reads the zero row (cell 4 n) for its first row: 0 & b & c & e = 0, so its
+        // mask is `always` as the select per word gave it, for one select on an index; and the
+        // words as two v_bitop3 each, a & b & c and then (abc & e) | always
+        const uint4 a = t[none ? 4u * n : x1], b = t[n + x0], c = t[2u * n + z1],
+                    e = t[3u * n + z0];
+        auto word = [](uint32_t wa, uint32_t wb, uint32_t wc, uint32_t we, uint32_t always) {
+            return __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(wa, wb, wc, kBitopAnd3),
+                                               we, always, kBitopAndOr);
+        };
+        m.x = word(a.x, b.x, c.x, e.x, p.gf_always[0]);
+        m.y = word(a.y, b.y, c.y, e.y, p.gf_always[1]);
+        m.z = word(a.z, b.z, c.z, e.z, p.gf_always[2]);
+        m.w = word(a.w, b.w, c.w, e.w, p.gf_always[3]);
+        return m;
+    }
+    const uint4 a = t[x1], b = t[n + x0], c = t[2u * n + z1], e = t[3u * n + z0];
     m.x = (none ? 0u : a.x & b.x & c.x & e.x) | p.gf_always[0];
     m.y = (none ? 0u : a.y & b.y & c.y & e.y) | p.gf_always[1];
     m.z = (none ? 0u : a.z & b.z & c.z & e.z) | p.gf_always[2];
@@ -2154,10 +2177,12 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         // With kFlagGroupFoot (fact (5g)) the group-level tables, 4 x gf_n float4s, take the place
         // of the boxes and the node tables (the host: 4 gf_n <= nb + nf), ahead of the records.
         const bool gfoot = (P.flags & kFlagGroupFoot) != 0u;
-        const int rb = gfoot ? nb + nf : nb;  // where the group records start
+        // (and their zero row, cell 4 gf_n: within nb + nf, or the one float4 nz more)
+        const int nz = kFootBitop ? (int)group_foot_zero_pad(P.ncgroups) : 0;
+        const int rb = gfoot ? nb + nf + nz : nb;  // where the group records start
         if (gfoot) {
             const float4* gt = reinterpret_cast<const float4*>(P.gf_tab);
-            const int nt = min(4 * (int)P.gf_n, nb + nf);
+            const int nt = min(4 * (int)P.gf_n + (kFootBitop ? 1 : 0), nb + nf + nz);
             for (int i = threadIdx.x; i < nt; i += blockDim.x) lds_geom[i] = gt[i];
         } else {
             uint32_t* ft = reinterpret_cast<uint32_t*>(lds_geom + nb + ng);
@@ -2181,7 +2206,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
         tg.geom = lds_geom + rb;
         // (this kernel: the footprint tables, node level or group level)
         tnode = gfoot ? lds_geom : lds_geom + nb + ng;
-        ws = reinterpret_cast<WS*>(lds_geom + nb + ng + nf) + (threadIdx.x >> 6);
+        ws = reinterpret_cast<WS*>(lds_geom + nb + ng + nf + nz) + (threadIdx.x >> 6);
         static_assert(foot_lds_bytes(128) % 16u == 0u && foot_lds_bytes(256) % 16u == 0u,
                       "whole float4s");
         static_assert(kNS == 21u && sizeof(WS) == kWaveScratchBytes8,

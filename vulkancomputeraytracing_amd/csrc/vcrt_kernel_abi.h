@@ -192,6 +192,20 @@ constexpr uint32_t kGroupFootMaxGroups = 128;
 constexpr uint32_t group_foot_cells(int32_t ncgroups) {
     return (static_cast<uint32_t>(ncgroups) / 8u * 336u + foot_lds_bytes(ncgroups)) / 64u;
 }
+// The group tables' zero row (tracer.hip group_foot_mask): one all-zero 16-B mask behind the four
+// tables, at cell 4 gf_n of the LDS image, which a ray that never reaches the y extent reads in
+// place of its first row. The 64-B division above leaves it room except where the tables fill the
+// bytes exactly (groups / 8 = 2, 6, 10, 14): there the image grows by this one float4, ahead of
+// the group records. 0 at the final scene's 128 groups (32 B to spare).
+constexpr uint32_t group_foot_zero_pad(int32_t ncgroups) {
+    if (ncgroups <= 0 || static_cast<uint32_t>(ncgroups) > kGroupFootMaxGroups) return 0u;
+    const uint32_t bytes = static_cast<uint32_t>(ncgroups) / 8u * 336u + foot_lds_bytes(ncgroups);
+    return bytes - 64u * group_foot_cells(ncgroups) >= 16u ? 0u : 1u;
+}
+// v_bitop3_b32's truth-table bytes (bit 4 x + 2 y + z of the byte is the result for operand bits
+// x, y, z) of the two forms the footprint masks are combined with
+constexpr uint32_t kBitopAnd3 = 0x80;   // x & y & z
+constexpr uint32_t kBitopAndOr = 0xea;  // (x & y) | z
 constexpr uint32_t kWaveScratchBytes = 4360;  // CULL_FLAT per-wave LDS stacks, 16-bit entries
 constexpr uint32_t kWaveScratchBytes8 = 3464;  // 16-bit candidates, no chunk stack (LDS tables)
 constexpr uint32_t kWaveScratchBytesWide = 6920;  // the same with 32-bit entries (global tables)
