@@ -702,6 +702,14 @@ int32_t vcrt_lens_offsets(const vcrt_render_desc* desc, uint32_t first, uint32_t
 vcrt_result vcrt_selftest_sin(uint32_t first, uint32_t count, uint64_t* mismatches,
                               uint64_t* fallbacks, uint32_t* first_mismatch);
 
+/* Device self-test of the scatter's unit vector (tracer.hip unit_of, kernel vcrt_check_unit):
+ * out[i] = the device's normalize of triples[i] (three rand() values, none negative), which must
+ * equal triples[i] / sqrt(dot) with the correctly rounded fp32 sqrt and divisions bit for bit,
+ * inside the helper's one-reciprocal range and outside it. n <= 2^28. Diagnostic addition (the
+ * reference has no such call). Requires vcrt_begin. */
+vcrt_result vcrt_selftest_unit(const float* triples /* [n][3] */, uint32_t n,
+                               float* out /* [n][3] */);
+
 /* Canonical math as used by the kernel (host evaluation), for tests and tools. */
 float vcrt_canonical_sin(float x);
 float vcrt_canonical_rand(float x, float y);

@@ -7,7 +7,7 @@
 #   ab          A/B timing, interleaved single-process renders (tools/ab.py): the current tree
 #               against the tree in $PREV (an earlier commit built by tools/mkab_tree.sh; any ABI)
 #               and the code objects / env settings in $OBJS (tools/ab.py syntax: OBJ@VAR=V,...),
-#               on $AB_CFGS (default c4; also c2, c3, stress) for $ROUNDS rounds; digests must agree
+#               on $AB_CFGS (default c4; also c2, c3, stress, c5w: C5's scene at 256 spp) for $ROUNDS rounds; digests must agree
 #   sweep       the N-way shards of C4 rendered one after another (tools/shard_sweep.py), max and
 #               per-rank kernel ms for N in $WORLDS (default 2,4,8), $SWEEP_REPS times
 #   profile     the round's profile set for tools/collect_profile.py $TAG: bench lines (c4 c3 c2
@@ -32,6 +32,7 @@ cfg_args() {  # tools/ab.py / render_once.py arguments of a config
     c4) echo "--spp 1024";;
     c5) echo "--scene stress4096 --width 3840 --height 2160 --spp 4096 --depth 50";;
     stress) echo "--scene stress4096 --width 3840 --height 2160 --spp 32 --depth 50";;
+    c5w) echo "--scene stress4096 --width 3840 --height 2160 --spp 256 --depth 50";;  # C5's workload
   esac
 }
 

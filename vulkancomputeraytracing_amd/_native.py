@@ -260,6 +260,7 @@ SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint32)]),
+    "vcrt_selftest_unit": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "vcrt_srgb8_thresholds": (None, [ctypes.c_void_p]),
     "vcrt_trace_rays": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,

@@ -3277,6 +3277,32 @@ vcrt_result vcrt_selftest_sin(uint32_t first, uint32_t count, uint64_t* mismatch
     return VCRT_SUCCESS;
 }
 
+vcrt_result vcrt_selftest_unit(const float* triples, uint32_t n, float* out) {
+    if (!g.begun || (n && (!triples || !out)) || n > (1u << 28))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!n) return VCRT_SUCCESS;
+    hipFunction_t f = nullptr;
+    VCRT_TRY(hipModuleGetFunction(&f, static_cast<hipModule_t>(g.stage.module), "vcrt_check_unit"));
+    const size_t bytes = sizeof(float) * 3u * n;
+    void* buf = nullptr;  // the triples, then their unit vectors
+    VCRT_TRY(hipMalloc(&buf, 2 * bytes));
+    float* d_in = static_cast<float*>(buf);
+    float* d_out = d_in + 3u * static_cast<size_t>(n);
+    hipError_t e = hipMemcpyAsync(d_in, triples, bytes, hipMemcpyHostToDevice, g.stream);
+    vcrt::UnitCheckParams up{d_in, d_out, n};
+    VkResult r = e == hipSuccess ? launch(f, std::min<uint32_t>((n + 255u) / 256u, 4096u), 256, 0, up)
+                                 : to_vk(e);
+    if (r == VK_SUCCESS) {
+        e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, g.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        r = to_vk(e);
+    } else {
+        (void)hipStreamSynchronize(g.stream);
+    }
+    (void)hipFree(buf);
+    return r == VK_SUCCESS ? VCRT_SUCCESS : r;
+}
+
 vcrt_result vcrt_read_framebuffer_srgb8(uint8_t* rgba8, size_t bytes) {
     const FbView v = fb_view();
     if (!g.begun || (!rgba8 && v.elems)) return VCRT_ERROR_INITIALIZATION_FAILED;

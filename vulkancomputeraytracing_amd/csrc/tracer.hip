@@ -84,6 +84,7 @@ enum : uint32_t {
     kCamRootTrip, kShadeCam, kScan, kScanLinear, kMainBig, kMainBigM0, kMainBigM1, kMainBigM2,
     kMainBigM3, kListed, kLevelChunk, kLevelNodes, kDrainTrip, kPassCand, kPassGroup, kPassNode,
     kPassChunk, kShadeSkyMain, kSqrtFallback, kDivFallback, kSteal,
+    kUnitFallback,  // unit_of's full division (a scatter vector outside its guard)
     kShadeBase0 = 40, kShadeBase1 = 56,  // the shading's regions, per call site (camera phase,
                                          // main-scan sky), at these offsets:
     kShEntry = 0, kShHit, kShNormalDiv, kShSinFallback, kShLamMetal, kShLam, kShMetal, kShGlass,
@@ -380,7 +381,9 @@ __device__ __forceinline__ float candidate_t(float hb, float disc, float a) {
 //    changes special values. div_a runs that unscaled sequence: for |x| in [2^-103, 2^64) the
 //    same bits. A root that can be accepted (> min_t = 0.001 with a >= 2^-20) has |x| > 2^-30.
 //    For |x| < 2^-103 (or x = 0) both quotients are below 2^-83 in magnitude, so both roots
-//    are rejected alike (their sign or last bits never matter).
+//    are rejected alike (their sign or last bits never matter). (unit_of below uses the same
+//    sequence for the scatter's unit vector, with its own range argument: numerators 0 or in
+//    [2^-40, 1] against a length in [2^-20, 2].)
 //  * sqrt: hipcc's correctly rounded sqrt scales x < 2^-96, takes v_sqrt and picks between its
 //    neighbours by two FMA residuals, then special-cases 0 and inf; sqrt_unscaled runs the
 //    unscaled middle, the same bits for x in [2^-96, 2^126]. Lanes with disc < 2^-96 take the
@@ -415,6 +418,67 @@ __device__ __forceinline__ float sqrt_fast(float x, uint32_t* rrow = nullptr) {
         r = !(x >= 0x1p-96f) ? full : r;
     }
     return r;
+}
+
+// The scatter's unit vector ru / length(ru) (functions.glsl:43's normalize of three rand()
+// values) with one reciprocal: len = sqrt(dot(ru, ru)), recip_a(len) once and div_a per
+// component, the same bits as the three full divisions by div_a's argument above. Its two range
+// conditions, for numerators x in {0} or [2^-40, 1] and len in [2^-20, 2]:
+//  * v_div_scale's numerator bound: it leaves x and len alone when both are normal, x / len is
+//    normal and exp(x) - exp(len) < 96, exp(x) > 23. Here exp(x) - exp(len) <= 20, the quotient
+//    is at least 2^-41, and 2^-40 is far above 2^-103.
+//  * a zero numerator: the full division gives +0 (the components are never negative), and
+//    div_a gives q0 = 0 * ya = +0, q1 = fma(fma(-len, 0, 0), ya, 0) = +0 and +0 again.
+// tests/test_unit_rcp_cpu.py compares the two forms with the reciprocal moved by an ulp either
+// way. The guard is on the bits: a component passes when it is zero or at least 2^-40 (its bits
+// less one, as unsigned: zero wraps to the top), len when its bits lie in [2^-20, 2]; a NaN or
+// infinite component makes len NaN, and an all-zero vector len = 0, which both fail. A wave with
+// a lane outside the guard takes the full sqrt and divisions in a real branch (sqrt_fast is the
+// correctly rounded sqrt for every x, so that branch is the expression as it was).
+// -DVCRT_UNIT_RCP=0 builds that expression alone.
+#ifndef VCRT_UNIT_RCP
+#define VCRT_UNIT_RCP 1
+#endif
+// The first rand() argument of a hit: rand(point.xy) for glass (textures.glsl:51), rand(dir.xy)
+// otherwise. The operands by two selects and one rand_arg, instead of both products in
+// exec-masked blocks: the same multiplications and addition on the same operands.
+// -DVCRT_RAND_ARG_SEL=0 builds the two-sided form.
+#ifndef VCRT_RAND_ARG_SEL
+#define VCRT_RAND_ARG_SEL 1
+#endif
+__device__ __forceinline__ float rand_arg_first(bool glass, f3 point, f3 d) {
+#if VCRT_RAND_ARG_SEL
+    return rand_arg(glass ? point.x : d.x, glass ? point.y : d.y);
+#else
+    return glass ? rand_arg(point.x, point.y) : rand_arg(d.x, d.y);
+#endif
+}
+
+__device__ __forceinline__ bool unit_guard(f3 ru, float len) {
+    const uint32_t bx = __float_as_uint(ru.x) - 1u, by = __float_as_uint(ru.y) - 1u,
+                   bz = __float_as_uint(ru.z) - 1u;
+    const uint32_t m = min(min(bx, by), bz);
+    return m >= 0x2B800000u - 1u &&                          // each 0 or >= 2^-40
+           __float_as_uint(len) - 0x35800000u <= 0x0A800000u;  // 2^-20 <= len <= 2
+}
+
+__device__ __forceinline__ f3 unit_of(f3 ru, uint32_t* rrow = nullptr) {
+#if VCRT_UNIT_RCP
+    const float dd = dot(ru, ru);
+    const float len = sqrt_unscaled(dd);
+    const float yl = recip_a(len);
+    f3 u = mk(div_a(ru.x, len, yl), div_a(ru.y, len, yl), div_a(ru.z, len, yl));
+    const bool out = !unit_guard(ru, len);
+    if (__ballot(out)) {  // wave-uniform: no exec-mask save and restore
+        asm volatile("");
+        region(rrow, reg::kUnitFallback);
+        const f3 full = divs(ru, __builtin_sqrtf(dd));
+        u = mk(out ? full.x : u.x, out ? full.y : u.y, out ? full.z : u.z);
+    }
+    return u;
+#else
+    return divs(ru, sqrt_fast(dot(ru, ru), rrow));
+#endif
 }
 
 __device__ __forceinline__ float candidate_t_fast(float hb, float disc, float a, float ya,
@@ -2344,7 +2408,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
             // rand(point.xy) for glass (textures.glsl:51): three sines for every hit lane
             float s1, s2, s3;
             bool sin_fb = false;
-            sin3<true>((type == 3) ? rand_arg(point.x, point.y) : rand_arg(d.x, d.y),
+            sin3<true>(rand_arg_first(type == 3, point, d),
                        rand_arg(d.x, d.z), rand_arg(d.y, d.z), s1, s2, s3,
                        (cdouble*)&P.sin_c[0], kStats ? &sin_fb : nullptr);
             if constexpr (kStats) {
@@ -2356,7 +2420,7 @@ __device__ __forceinline__ void trace_impl(const TraceParams& p_arg, float4* lds
                 const float r2 = rand_of_sin(s2);
                 const float r3 = rand_of_sin(s3);
                 const f3 ru = mk(r1, r2, r3);  // random_in_unit_sphere(dir): normalize
-                const f3 u = divs(ru, sqrt_fast(dot(ru, ru), rrow));
+                const f3 u = unit_of(ru, rrow);
                 if (type == 1) {
                     region(rrow, rb + reg::kShLam);
                     d = add(normal, u);
@@ -3484,14 +3548,14 @@ __device__ __forceinline__ bool shade_segment(const TraceParams& S, float max_t,
     // rand(dir.xy), rand(dir.xz), rand(dir.yz) for lambertian/metal (functions.glsl:43),
     // rand(point.xy) for glass (textures.glsl:51)
     float s1, s2, s3;
-    sin3<true>((type == 3) ? rand_arg(point.x, point.y) : rand_arg(d.x, d.y), rand_arg(d.x, d.z),
-               rand_arg(d.y, d.z), s1, s2, s3, (cdouble*)&S.sin_c[0], nullptr);
+    sin3<true>(rand_arg_first(type == 3, point, d), rand_arg(d.x, d.z), rand_arg(d.y, d.z), s1,
+               s2, s3, (cdouble*)&S.sin_c[0], nullptr);
     const float r1 = rand_of_sin(s1);
     if (type == 1 || type == 2) {
         const float r2 = rand_of_sin(s2);
         const float r3 = rand_of_sin(s3);
         const f3 ru = mk(r1, r2, r3);  // random_in_unit_sphere(dir): normalize
-        const f3 u = divs(ru, sqrt_fast(dot(ru, ru)));
+        const f3 u = unit_of(ru);
         if (type == 1) {
             d = add(normal, u);
             atten = scale(param, mul(atten, albedo));
@@ -4110,6 +4174,22 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_frame_features(FeaturePar
         if (nl) atomicAdd(slot + 0, nl);
         if (wh) atomicAdd(slot + 1, wh / 2u);
         if (wb) atomicAdd(slot + 2, wb);
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// Self-test of unit_of (the scatter's unit vector) on caller-supplied triples, a code-generation
+// unit of its own (Makefile, part 9): out[i] = unit_of(in[i]), to be compared on the host with
+// the correctly rounded sqrt and divisions.
+#if !defined(VCRT_PART) || VCRT_PART == 9
+extern "C" __global__ __launch_bounds__(256) void vcrt_check_unit(UnitCheckParams p) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < p.count; i += stride) {
+        const f3 u = unit_of(mk(p.in[3u * i], p.in[3u * i + 1u], p.in[3u * i + 2u]));
+        p.out[3u * i] = u.x;
+        p.out[3u * i + 1u] = u.y;
+        p.out[3u * i + 2u] = u.z;
     }
 }
 #endif

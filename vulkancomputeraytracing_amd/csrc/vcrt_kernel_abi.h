@@ -335,6 +335,12 @@ struct SinCheckParams {
     double sin_c[13];            // vcrt_math.h kSinC, for the table form the tracer uses
 };
 
+struct UnitCheckParams {
+    const float* in;  // [count][3]: the scatter's three rand() values
+    float* out;       // [count][3]: tracer.hip unit_of of each triple
+    uint32_t count;
+};
+
 struct FillParams {
     float4* out;
     uint32_t count;

@@ -251,6 +251,60 @@ constexpr double kSinC[13] = {0.31830988618379067154, 0x1.8p52, 0x1.921fb544p+1,
                               VCRT_SIN_REST(VCRT_SIN_LIST) VCRT_SIN_PAD};
 #undef VCRT_SIN_LIST
 
+// The fast sine's accept predicate (sin_fast_try below), for N = 1, 2 or 3 sines at once: all N
+// arguments below 2^19 in magnitude, every reduced argument at least 2^VCRT_SIN_RMIN_LOG2, and
+// every `below` word (bits 28..0 of the fast value's double mantissa) more than 2^9 away from
+// 2^28, the fp32 rounding boundary. One definition for the device's three entry points and the
+// host (tests/test_sin_guard_cpu.py enumerates it as it stands here). `ok`: the conjunction so
+// far, for a caller that takes its arguments' tests one by one.
+//  * VCRT_SIN_ACCEPT3=1: the N tests of a kind are folded before they are compared: the largest
+//    |x| (v_max3_f32), the smallest biased `below` word (v_min3_u32), and the magnitude test
+//    taken on the smallest |result| in fp32 (v_min3_f32) instead of on each double r: |sin r|
+//    against the threshold instead of |r|, the same claim (any threshold from 2^-40 to 2^-12
+//    passes the exhaustive comparison). fmaxf and fminf drop a NaN operand, and a NaN or
+//    infinite x gives a NaN result, so for N > 1 the results' product-sum (NaN exactly when one
+//    of them is) times zero is added to the smallest |result|: a NaN argument is rejected as
+//    `|x| < 2^19` alone rejects it for N = 1.
+//  * VCRT_SIN_ACCEPT3=0: each sine's three compares on their own, the magnitude on r.
+// -DVCRT_SIN_ACCEPT3=0 -DVCRT_SIN_RMIN_LOG2=-12 is the predicate as it was before round 15.
+#ifndef VCRT_SIN_RMIN_LOG2
+#define VCRT_SIN_RMIN_LOG2 -20
+#endif
+#ifndef VCRT_SIN_ACCEPT3
+#define VCRT_SIN_ACCEPT3 1
+#endif
+static_assert(VCRT_SIN_RMIN_LOG2 >= -40 && VCRT_SIN_RMIN_LOG2 <= -12, "checked range of the guard");
+constexpr double kSinRmin =
+    __builtin_bit_cast(double, (uint64_t)(1023 + (VCRT_SIN_RMIN_LOG2)) << 52);
+constexpr float kSinRminF = __builtin_bit_cast(float, (uint32_t)(127 + (VCRT_SIN_RMIN_LOG2)) << 23);
+constexpr uint32_t kSinBelowLo = 0x10000000u - 0x200u, kSinBelowSpan = 0x400u;
+
+template <int N>
+VCRT_HD bool sin_accept(const float* xf, const float* out, const double* r,
+                        const uint32_t* below, bool ok = true) {
+    static_assert(N >= 1 && N <= 3, "one, two or three sines");
+#if VCRT_SIN_ACCEPT3
+    (void)r;
+    float xm = __builtin_fabsf(xf[0]), om = __builtin_fabsf(out[0]);
+    uint32_t bm = below[0] - kSinBelowLo;
+    for (int i = 1; i < N; ++i) {
+        xm = __builtin_fmaxf(xm, __builtin_fabsf(xf[i]));
+        om = __builtin_fminf(om, __builtin_fabsf(out[i]));
+        const uint32_t b = below[i] - kSinBelowLo;
+        bm = b < bm ? b : bm;
+    }
+    if constexpr (N == 2) om = __builtin_fmaf(out[0] * out[1], 0.0f, om);
+    if constexpr (N == 3) om = __builtin_fmaf(__builtin_fmaf(out[0], out[1], out[2]), 0.0f, om);
+    return ok && xm < 0x1p19f && om >= kSinRminF && bm > kSinBelowSpan;
+#else
+    (void)out;
+    for (int i = 0; i < N; ++i)
+        ok = ok && __builtin_fabsf(xf[i]) < 0x1p19f && __builtin_fabs(r[i]) >= kSinRmin &&
+             below[i] - kSinBelowLo > kSinBelowSpan;
+    return ok;
+#endif
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 // The canonical sin on the device, by Ziv's method: one branch-free evaluation for every lane
 // (sin_canonical evaluates both fdlibm kernels under divergence, since the quadrant varies per
@@ -259,12 +313,21 @@ constexpr double kSinC[13] = {0.31830988618379067154, 0x1.8p52, 0x1.921fb544p+1,
 // pi split as pi_hi (33 bits: k pi_hi exact for |k| < 2^20) + pi_mid, FMAs), then the degree-15
 // minimax polynomial above on |r| <= pi/2 (approximation error < 2^-52.2 |sin r|, below the
 // 2^-51.8 of the Taylor form this analysis was made for, with two rounded steps fewer), sign
-// (-1)^k. For |x| < 2^19 and
-// |r| >= 2^-12 the error of s and that of sin_canonical's double result (2-term Cody-Waite
-// reduction, fdlibm kernels)
-// are each below 2^-48 |sin x|; if s lies farther than 2^-44 |s| from every fp32 rounding
-// boundary, both round to the same float f. Otherwise (|r| < 2^-12, |x| >= 2^19, or s near a
-// boundary: ~2e-4 of the calls) the lane takes sin_canonical.
+// (-1)^k. Accepted (sin_accept above) when |x| < 2^19, the reduced argument is at least
+// 2^VCRT_SIN_RMIN_LOG2 (2^-20; taken on |s| in fp32 under VCRT_SIN_ACCEPT3) and s lies farther
+// than 2^-44 |s| from every fp32 rounding boundary. The bound: both reductions (this one's
+// pi_hi + pi_mid and sin_canonical's two-term Cody-Waite, no third term in either) leave an
+// absolute error near 2^-68 in r for |k| < 2^18, so a relative one below 2^-48 |sin x| down to
+// |r| = 2^-20 (2^-68 / 2^-20), and the polynomials' own errors (2^-52.2, fdlibm's 2^-57) are
+// relative; within the 2^-44 |s| margin the bound holds to about |r| = 2^-22. That estimate is
+// not what carries the claim: the exhaustive comparison is. Every fp32 input with |x| < 2^19,
+// both signs, 2.45e9 of them, is run through this arithmetic and sin_accept on the host
+// (tests/test_sin_guard_cpu.py) and no accepted value differs from sin_canonical's, at this
+// threshold and at 2^-40, whose accepted set holds that of every threshold up to 2^-12; the
+// device repeats it on all 2^32 inputs.
+// Otherwise (|r| below the threshold, |x| >= 2^19, or s near a boundary: 2.5e-6 of the
+// arguments from 2^-12 up, 6e-7 of them by the threshold; 6.9e-5 with the earlier 2^-12) the
+// lane takes sin_canonical.
 // tests/test_gpu_parity.py::test_sin_fast_exhaustive compares the two on all 2^32 inputs.
 // A double constant materialised in an SGPR pair where it is used: plain literals get hoisted
 // out of the tracer's loops into VGPR pairs, which then spill (v_fma_f64 takes no 64-bit
@@ -307,20 +370,20 @@ __device__ __forceinline__ bool sin_fast_try(float xf, float& out) {
     const uint64_t tb = __builtin_bit_cast(uint64_t, t);
     const uint64_t sb = __builtin_bit_cast(uint64_t, s) ^ (tb << 63);  // (-1)^k
     out = (float)__builtin_bit_cast(double, sb);
-    // bits 28..0 of s's mantissa (|s| >= 2^-13: normal in both formats)
+    // bits 28..0 of s's mantissa (an accepted |s| is normal in both formats)
     const uint32_t below = (uint32_t)sb & 0x1FFFFFFFu;
-    const bool ok = __builtin_fabsf(xf) < 0x1p19f && __builtin_fabs(r) >= 0x1p-12 &&
-                    below - (0x10000000u - 0x200u) > 0x400u;
-    return ok;
+    return sin_accept<1>(&xf, &out, &r, &below);
 }
 
 // sin_fast_try of N arguments at once, step by step: each constant is materialized once and
 // used by the N evaluations (sconst's two s_mov_b32 per use were ~90 SALU instructions per
 // scatter with three separate calls), each argument's operations unchanged.
 typedef __attribute__((address_space(4))) const double cdouble;
-template <int N, bool kTab = false>
-__device__ __forceinline__ bool sin_fast_try_n(const float* xf, float* out,
-                                               cdouble* kc = nullptr) {
+// (each(i) runs when argument i's values are complete: the accept test of that argument where
+// the tests are taken one by one, nothing where sin_accept folds them afterwards.)
+template <int N, bool kTab = false, typename Each>
+__device__ __forceinline__ void sin_fast_eval_n(const float* xf, float* out, double* r,
+                                                uint32_t* below, cdouble* kc, Each each) {
 #define VCRT_SC(j, lit)                                 \
     ([&]() -> double {                                  \
         if constexpr (kTab)                             \
@@ -328,7 +391,7 @@ __device__ __forceinline__ bool sin_fast_try_n(const float* xf, float* out,
         else                                            \
             return VCRT_DC(lit);                        \
     }())
-    double x[N], t[N], k[N], r[N], r2[N], p[N];
+    double x[N], t[N], k[N], r2[N], p[N];
     for (int i = 0; i < N; ++i) x[i] = (double)xf[i];
     {
         const double c = VCRT_SC(0, 0.31830988618379067154), sh = VCRT_SC(1, 0x1.8p52);
@@ -356,40 +419,63 @@ __device__ __forceinline__ bool sin_fast_try_n(const float* xf, float* out,
     VCRT_SIN_REST(VCRT_SIN3_STEP)
 #undef VCRT_SIN3_STEP
 #undef VCRT_SC
-    bool ok = true;
     for (int i = 0; i < N; ++i) {
         const double s = __builtin_fma(r[i] * r2[i], p[i], r[i]);
         const uint64_t tb = __builtin_bit_cast(uint64_t, t[i]);
         const uint64_t sb = __builtin_bit_cast(uint64_t, s) ^ (tb << 63);  // (-1)^k
         out[i] = (float)__builtin_bit_cast(double, sb);
-        const uint32_t below = (uint32_t)sb & 0x1FFFFFFFu;
-        ok = ok && __builtin_fabsf(xf[i]) < 0x1p19f && __builtin_fabs(r[i]) >= 0x1p-12 &&
-             below - (0x10000000u - 0x200u) > 0x400u;
+        below[i] = (uint32_t)sb & 0x1FFFFFFFu;
+        each(i);
     }
+}
+
+template <int N, bool kTab = false>
+__device__ __forceinline__ bool sin_fast_try_n(const float* xf, float* out,
+                                               cdouble* kc = nullptr) {
+    double r[N];
+    uint32_t below[N];
+#if VCRT_SIN_ACCEPT3
+    sin_fast_eval_n<N, kTab>(xf, out, r, below, kc, [](int) {});
+    return sin_accept<N>(xf, out, r, below);
+#else
+    bool ok = true;
+    sin_fast_eval_n<N, kTab>(xf, out, r, below, kc, [&](int i) {
+        ok = sin_accept<1>(xf + i, out + i, r + i, below + i, ok);
+    });
     return ok;
+#endif
 }
 
 // The three rand() values of a scatter (textures.glsl:21, :51, functions.glsl:43): sines of
 // a1, a2 by sin_fast_try_n<2> (shared constants: measured +1.0% at C4, +1.5-3% at C2 against
-// three separate calls; all three interleaved spilled a loop counter), a3 by sin_fast_try; a
-// lane whose fast values were not all accepted recomputes all three
-// canonically in one loop (one inlined copy of the fdlibm path instead of three).
+// three separate calls; all three interleaved spilled a loop counter), a3 by the same evaluation
+// for one, and the three accept tests as one (sin_accept<3>: 15 VALU and 3 scalar instructions
+// where three tests of their own took 15 and 9); a lane whose fast values were not all accepted
+// recomputes all three canonically in one loop (one inlined copy of the fdlibm path instead of
+// three).
 template <bool kTab = false>
 __device__ __forceinline__ void sin3(float a1, float a2, float a3, float& s1, float& s2,
                                      float& s3, cdouble* kc = nullptr, bool* fell_back = nullptr) {
-    const float a[2] = {a1, a2};
-    float sv[2];
+    const float a[3] = {a1, a2, a3};
+    float sv[3];
+#if VCRT_SIN_ACCEPT3
+    // the evaluations as below (two sines, then one), their accept tests as one of three
+    double r[3];
+    uint32_t below[3];
+    sin_fast_eval_n<2, kTab>(a, sv, r, below, kc, [](int) {});
+    sin_fast_eval_n<1, kTab>(a + 2, sv + 2, r + 2, below + 2, kc, [](int) {});
+    const bool ok = sin_accept<3>(a, sv, r, below);
+#else
     bool ok = sin_fast_try_n<2, kTab>(a, sv, kc);
     if constexpr (kTab) {
-        const float a3v[1] = {a3};
-        float s3v[1];
-        ok = ok & sin_fast_try_n<1, true>(a3v, s3v, kc);
-        s3 = s3v[0];
+        ok = ok & sin_fast_try_n<1, true>(a + 2, sv + 2, kc);
     } else {
-        ok = ok & sin_fast_try(a3, s3);
+        ok = ok & sin_fast_try(a3, sv[2]);
     }
+#endif
     s1 = sv[0];
     s2 = sv[1];
+    s3 = sv[2];
     if (fell_back) *fell_back = !ok;  // stats builds (tracer.hip region counters)
     if (!ok) {
 #pragma nounroll
