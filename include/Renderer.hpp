@@ -32,5 +32,9 @@ VkResult UpdateSpheres(IN const vcrt_sphere* spheres, IN int32_t count);
 // (vcrt_draw_features: host pointers in the framebuffer's layout; any may be NULL, not all).
 VkResult DrawFeatures(IN uint32_t first, IN uint32_t n, OUT float* albedo, OUT float* normal_depth,
                       OUT int32_t* sphere);
+// The ambient visibility buffer of the same rays (vcrt_draw_occlusion: m secondary rays of reach
+// `reach` per sample that hits; a host pointer in the framebuffer's layout).
+VkResult DrawOcclusion(IN uint32_t first, IN uint32_t n, IN uint32_t m, IN float reach,
+                       OUT float* visibility);
 
 #endif

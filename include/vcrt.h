@@ -27,7 +27,9 @@
  * vcrt_set_scene (vcrt_update_spheres: the scene's grouping is kept and its tables are refitted
  * on the GPU; vcrt_get_scene_update_stats, vcrt_scene_table_host / _read); the guide buffers of
  * a frame for a denoiser (vcrt_draw_features: first-hit albedo, normal, depth, coverage and
- * sphere id of the frame's own camera rays; vcrt_frame_rays).
+ * sphere id of the frame's own camera rays; vcrt_frame_rays) and its ambient visibility buffer
+ * (vcrt_draw_occlusion: the open share of short rays sent from those first hits;
+ * vcrt_ambient_dirs).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -595,6 +597,76 @@ vcrt_result vcrt_draw_features_device(uint32_t first, uint32_t n, float* albedo,
 int32_t vcrt_frame_rays(const vcrt_render_desc* desc, const int32_t* xy, int32_t npixels,
                         uint32_t first, uint32_t n, float* origins /* [npixels][n][3] */,
                         float* dirs /* [npixels][n][3] */);
+
+/* The ambient visibility buffer: for every pixel the share of short any-hit rays, sent from the
+ * first hits of the frame's own camera rays over the hemisphere, that nothing stops -- the usual
+ * companion of albedo, normal and depth as a denoiser guide, and with albedo the cheap preview
+ * shading of an editor (vcrt_set_camera, vcrt_update_spheres). The camera rays, their first hits
+ * and the secondary rays are generated on the GPU in one kernel; nothing per ray is uploaded.
+ * Added.
+ *
+ * For a local pixel (x, y) and the sample indices i = first .. first + n - 1, ray_i(x, y) =
+ * (o_i, d_i) is vcrt_draw_features' ray (vcrt_frame_rays) and (t_i, s_i, normal_i) its first hit
+ * as vcrt_ray_hit reports it. A sample that hits (s_i >= 0) sends m secondary rays, k < m, every
+ * fp32 operation rounded on its own, no contraction:
+ *   P   = o_i + t_i * d_i                       per component, the product then the sum
+ *   dn  = d.x n.x + d.y n.y + d.z n.z           summed left to right
+ *   N   = dn > 0 ? -normal_i : normal_i         the normal turned against the ray
+ *   u   = u_j, j = i * m + k                    vcrt_ambient_dirs, below
+ *   d'  = N + u                                 the reference's Lambertian lobe: normal + unit
+ *   open_{i,k} = !occluded(P, d', reach)        vcrt_occlude_rays' predicate: hit_sphere with
+ *                                               min_t = 0.001 and max_t = reach, t in units of d'
+ * u_j (vcrt_ambient_dirs: host only, no GPU), fj = (float)j:
+ *   a = rand(fj, fj + 0.5f), b = rand(fj + 0.5f, fj)      vcrt_canonical_rand
+ *   zc = 1 - 2 a, rr = sqrtf(max(0, 1 - zc zc)), phi = 6.2831855f * b
+ *   u = (rr sin(phi + 1.5707964f), rr sin(phi), zc)       vcrt_canonical_sin
+ * the lens offsets' recipe on a sphere, sqrtf correctly rounded.
+ * Output: visibility, float4 [elements] in the rank-local framebuffer layout (it goes through
+ * vcrt_assemble_tiles and the image writers as a frame does; slots outside the frame are left
+ * untouched). With C the number of samples that hit and U the number of open secondary rays over
+ * them, both integers:
+ *   rgb = (float)(U + m (n - C)) / (float)(n m)       a sky sample counts as fully open
+ *   a   = (float)C / (float)n                          the coverage, vcrt_draw_features' albedo.a
+ * one correctly rounded division each. The sums are integer counts, so the bits depend on (desc,
+ * camera, scene, first, n, m, reach) only: not on which lane took which ray, on the route that
+ * served a first hit (VCRT_FEATURE_LISTS) or on kernel_variant. The contract holds where the
+ * frame's does and for d' not all zero and a finite normal; anything else is traced without a
+ * fault, deterministic, otherwise unspecified.
+ *
+ * stats may be NULL. The call is local, not collective, runs on the render stream and returns
+ * when done. It leaves alone the framebuffer, the progressive accumulation, vcrt_stats, the
+ * measured cost order and the frame's jitter and lens tables (it shares vcrt_draw_features' own
+ * tables and keeps a u_j table and a staging plane, only grown, freed by vcrt_end). After
+ * vcrt_set_camera, vcrt_update_spheres and vcrt_set_scene it sees the new state.
+ * vcrt_draw_occlusion takes a host pointer, vcrt_draw_occlusion_device a device pointer, 16-B
+ * aligned.
+ * Errors: VCRT_ERROR_FORMAT_NOT_SUPPORTED unless 1 <= m <= 256, n >= 1, first + n <= 2^19,
+ * n m <= 4096 and (first + n) m <= 2^22 (every j + 0.5f is then exact), checked before the
+ * renderer's state, so it reads the same before vcrt_begin; VCRT_ERROR_INITIALIZATION_FAILED,
+ * before anything touches the GPU, for a NULL plane, a NaN reach (any other float is taken:
+ * +inf, and reach <= 0.001 leaves every ray open), a misaligned device plane and before
+ * vcrt_begin; VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object has no
+ * vcrt_frame_occlusion kernel (an A/B build of an older tree). */
+typedef struct vcrt_occlusion_buffer_stats {
+    uint64_t rays;            /* valid local pixels * n */
+    uint64_t hit_rays;        /* of them, the samples that hit a sphere */
+    uint64_t secondary_rays;  /* hit_rays * m */
+    uint64_t occluded;        /* secondary rays that something stops */
+    uint64_t listed_rays;     /* camera rays answered from the camera-ray lists */
+    uint64_t group_tests;     /* as vcrt_ray_stats, the camera and the secondary rays together */
+    uint64_t bound_tests;
+    double   kernel_ms;       /* the kernel, HIP events on the render stream */
+    double   host_ms;         /* wall time of the call */
+    char     kernel[48];      /* code-object symbol that ran */
+} vcrt_occlusion_buffer_stats;
+vcrt_result vcrt_draw_occlusion(uint32_t first, uint32_t n, uint32_t m, float reach,
+                                float* visibility, vcrt_occlusion_buffer_stats* stats);
+vcrt_result vcrt_draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, float reach,
+                                       float* visibility, vcrt_occlusion_buffer_stats* stats);
+/* u_j of j = first .. first + count - 1, the definition above as code (host only, no GPU), into
+ * out [count][3]. Returns count, or a negative VkResult: VCRT_ERROR_FORMAT_NOT_SUPPORTED for
+ * first + count > 2^22, VCRT_ERROR_INITIALIZATION_FAILED for a NULL out with count > 0. */
+int32_t vcrt_ambient_dirs(uint32_t first, uint32_t count, float* out /* [count][3] */);
 
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file

@@ -2,7 +2,8 @@
 // of its own that calls it for the cases of tests/test_features_cpu.py (44 x 20, every pixel,
 // pinhole and lens radius 0.1, first 0 and 7, n = 5, two cameras) into exactly-sized heap
 // buffers, checks what must hold without a reference (finite rays; the pinhole's origins are the
-// camera centre; the argument errors) and exits 0. Build it with the library's host sources and
+// camera centre; the argument errors), does the same for vcrt_ambient_dirs (the last 4096
+// directions below 2^22, unit length) and exits 0. Build it with the library's host sources and
 // -fsanitize=address,undefined, from the repository root (ROCM=/opt/rocm):
 //   cd vulkancomputeraytracing_amd && g++ -O1 -g -std=c++17 -fsanitize=address,undefined \
 //     -fno-sanitize-recover=undefined -ffp-contract=off -D__HIP_PLATFORM_AMD__ -I../include \
@@ -80,6 +81,29 @@ int main() {
                VCRT_ERROR_INITIALIZATION_FAILED, "before vcrt_begin");
     expect(vcrt_draw_features(0, 0, one, nullptr, nullptr, nullptr) ==
                VCRT_ERROR_FORMAT_NOT_SUPPORTED, "n = 0 samples");
+    // the ambient visibility buffer's host-only table, into an exactly-sized heap buffer, and
+    // its call's argument errors
+    {
+        const uint32_t first = (1u << 22) - 4096, count = 4096;
+        std::vector<float> u(3 * static_cast<size_t>(count));
+        expect(vcrt_ambient_dirs(first, count, u.data()) == static_cast<int32_t>(count),
+               "the direction count comes back");
+        bool unit = true;
+        for (uint32_t k = 0; k < count; k++) {
+            const double l2 = static_cast<double>(u[3 * k]) * u[3 * k] +
+                              static_cast<double>(u[3 * k + 1]) * u[3 * k + 1] +
+                              static_cast<double>(u[3 * k + 2]) * u[3 * k + 2];
+            unit = unit && std::fabs(l2 - 1.0) <= 1e-6;
+        }
+        expect(unit, "unit directions");
+        expect(vcrt_ambient_dirs(first + 1, count, u.data()) == VCRT_ERROR_FORMAT_NOT_SUPPORTED,
+               "past the last direction");
+        expect(vcrt_ambient_dirs(0, 1, nullptr) == VCRT_ERROR_INITIALIZATION_FAILED, "NULL table");
+        expect(vcrt_draw_occlusion(0, 4, 8, 1e5f, one, nullptr) == VCRT_ERROR_INITIALIZATION_FAILED,
+               "before vcrt_begin");
+        expect(vcrt_draw_occlusion(0, 17, 256, 1e5f, one, nullptr) ==
+                   VCRT_ERROR_FORMAT_NOT_SUPPORTED, "n m > 4096");
+    }
     if (failures == 0) std::puts("frame_rays_check: ok");
     return failures == 0 ? 0 : 1;
 }

@@ -149,6 +149,21 @@ class vcrt_feature_stats(ctypes.Structure):
     ]
 
 
+class vcrt_occlusion_buffer_stats(ctypes.Structure):
+    _fields_ = [
+        ("rays", ctypes.c_uint64),
+        ("hit_rays", ctypes.c_uint64),
+        ("secondary_rays", ctypes.c_uint64),
+        ("occluded", ctypes.c_uint64),
+        ("listed_rays", ctypes.c_uint64),
+        ("group_tests", ctypes.c_uint64),
+        ("bound_tests", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
 class vcrt_camera_stats(ctypes.Structure):
     _fields_ = [
         ("host_ms", ctypes.c_double),
@@ -285,6 +300,14 @@ SIGNATURES = {
     "vcrt_frame_rays": (ctypes.c_int32, [ctypes.POINTER(vcrt_render_desc), ctypes.c_void_p,
                                          ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32,
                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "vcrt_draw_occlusion": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_float, ctypes.c_void_p,
+                                             ctypes.POINTER(vcrt_occlusion_buffer_stats)]),
+    "vcrt_draw_occlusion_device": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32,
+                                                    ctypes.c_uint32, ctypes.c_float,
+                                                    ctypes.c_void_p,
+                                                    ctypes.POINTER(vcrt_occlusion_buffer_stats)]),
+    "vcrt_ambient_dirs": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

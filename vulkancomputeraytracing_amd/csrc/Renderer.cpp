@@ -69,3 +69,8 @@ VkResult DrawFeatures(IN uint32_t first, IN uint32_t n, OUT float* albedo, OUT f
     return static_cast<VkResult>(
         vcrt_draw_features(first, n, albedo, normal_depth, sphere, nullptr));
 }
+
+VkResult DrawOcclusion(IN uint32_t first, IN uint32_t n, IN uint32_t m, IN float reach,
+                       OUT float* visibility) {
+    return static_cast<VkResult>(vcrt_draw_occlusion(first, n, m, reach, visibility, nullptr));
+}

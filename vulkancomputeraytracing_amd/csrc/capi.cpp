@@ -103,6 +103,14 @@ struct RendererState {
     int32_t* d_ft_sphere = nullptr;
     size_t ft_albedo_cap = 0, ft_normal_depth_cap = 0, ft_sphere_cap = 0;  // in elements
     void* d_ft_counters = nullptr;
+    // the ambient visibility buffer (vcrt_draw_occlusion; null: the code object predates it): the
+    // u_j table of the call and the host call's staging plane, kept and grown only; the jitter and
+    // lens tables and the tallies' slots are the feature buffers'
+    hipFunction_t k_frame_occlusion = nullptr;
+    float4* d_ao_dirs = nullptr;
+    float4* d_ao_plane = nullptr;
+    size_t ao_dirs_cap = 0, ao_plane_cap = 0;  // in directions, in elements
+    std::vector<float4> h_ao_dirs;
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -700,6 +708,11 @@ VkResult bind_kernels() {
     if (hipModuleGetFunction(&g.k_frame_features, m, "vcrt_frame_features") != hipSuccess) {
         (void)hipGetLastError();
         g.k_frame_features = nullptr;
+    }
+    // optional: the ambient-visibility kernel (vcrt_draw_occlusion answers the same)
+    if (hipModuleGetFunction(&g.k_frame_occlusion, m, "vcrt_frame_occlusion") != hipSuccess) {
+        (void)hipGetLastError();
+        g.k_frame_occlusion = nullptr;
     }
     // optional: the camera-list kernels (vcrt_set_camera then runs the host builders)
     const std::pair<hipFunction_t*, const char*> list_kernels[] = {
@@ -2224,6 +2237,8 @@ vcrt_result vcrt_end(void) {
     if (g.d_ft_normal_depth) (void)hipFree(g.d_ft_normal_depth);
     if (g.d_ft_sphere) (void)hipFree(g.d_ft_sphere);
     if (g.d_ft_counters) (void)hipFree(g.d_ft_counters);
+    if (g.d_ao_dirs) (void)hipFree(g.d_ao_dirs);
+    if (g.d_ao_plane) (void)hipFree(g.d_ao_plane);
     if (g.d_cl_boxes) (void)hipFree(g.d_cl_boxes);
     if (g.d_cl_spheres) (void)hipFree(g.d_cl_spheres);
     if (g.d_cl_counts) (void)hipFree(g.d_cl_counts);
@@ -2511,6 +2526,32 @@ VkResult feature_tables(uint32_t first, uint32_t n) {
     return launch(g.k_setup_jitter, std::min<uint32_t>((n + 255u) / 256u, 8192u), 256, 0, sp);
 }
 
+// The scene block of the kernels that trace the frame's own camera rays (FeatureParams,
+// OcclusionBufferParams): a frame's, with the call's own jitter and lens tables of n samples.
+void frame_ray_scene(vcrt::TraceParams& s, uint32_t n) {
+    scene_params(s);
+    s.jitter = g.d_ft_jitter;
+    s.lens = lens_on() ? g.d_ft_lens : nullptr;
+    s.corner = g.d_corner;
+    s.prim_info = g.d_prim_info;
+    s.prim_ids = g.d_prim_ids;
+    s.cam_rec = g.d_cam_rec;
+    s.width = g.desc.width;
+    s.height = g.desc.height;
+    s.spp = static_cast<int32_t>(n);
+    s.max_depth = 1;
+    s.rank = g.desc.rank;
+    s.world = g.desc.world_size;
+    s.tiles_x = g.tiles_x;
+    s.local_tiles = g.local_tiles;
+    const std::array<float, 12> cam = camera_array();
+    for (int i = 0; i < 12; i++) s.cam[i] = cam[i];
+    // the lists go to a frame whose camera centre passes the range guard (trace_frame)
+    if (!(g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
+          std::fabs(cam[11]) <= 0x1p30f))
+        s.prim_info = nullptr;
+}
+
 // The launch on device pointers (checked by the callers): one wave per local tile; returns when
 // the kernel is done.
 VkResult draw_features_device(uint32_t first, uint32_t n, float* albedo, float* normal_depth,
@@ -2523,27 +2564,7 @@ VkResult draw_features_device(uint32_t first, uint32_t n, float* albedo, float* 
     const VkResult t = feature_tables(first, n);
     if (t != VK_SUCCESS) return t;
     vcrt::FeatureParams p{};
-    scene_params(p.scene);
-    p.scene.jitter = g.d_ft_jitter;
-    p.scene.lens = lens_on() ? g.d_ft_lens : nullptr;
-    p.scene.corner = g.d_corner;
-    p.scene.prim_info = g.d_prim_info;
-    p.scene.prim_ids = g.d_prim_ids;
-    p.scene.cam_rec = g.d_cam_rec;
-    p.scene.width = g.desc.width;
-    p.scene.height = g.desc.height;
-    p.scene.spp = static_cast<int32_t>(n);
-    p.scene.max_depth = 1;
-    p.scene.rank = g.desc.rank;
-    p.scene.world = g.desc.world_size;
-    p.scene.tiles_x = g.tiles_x;
-    p.scene.local_tiles = g.local_tiles;
-    const std::array<float, 12> cam = camera_array();
-    for (int i = 0; i < 12; i++) p.scene.cam[i] = cam[i];
-    // the lists go to a frame whose camera centre passes the range guard (trace_frame)
-    if (!(g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
-          std::fabs(cam[11]) <= 0x1p30f))
-        p.scene.prim_info = nullptr;
+    frame_ray_scene(p.scene, n);
     p.albedo = reinterpret_cast<float4*>(albedo);
     p.normal_depth = reinterpret_cast<float4*>(normal_depth);
     p.sphere = sphere;
@@ -2642,6 +2663,126 @@ vcrt_result vcrt_draw_features(uint32_t first, uint32_t n, float* albedo, float*
         if (sphere)
             VCRT_TRY(hipMemcpyAsync(sphere, g.d_ft_sphere, sizeof(int32_t) * elems,
                                     hipMemcpyDeviceToHost, g.stream));
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+    }
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+// ---- the ambient visibility buffer ----------------------------------------------------------
+
+namespace {
+
+constexpr uint64_t kAmbientMaxRays = 4096;               // n * m of one call
+constexpr uint64_t kAmbientMaxIndex = uint64_t{1} << 22;  // j + 0.5f is exact below 2^23
+
+// The arguments both forms of the call check, before anything touches the GPU: the ranges
+// first, so that they read the same with and without a renderer.
+vcrt_result ambient_args(uint32_t first, uint32_t n, uint32_t m, float reach,
+                         const void* visibility) {
+    const uint64_t end = static_cast<uint64_t>(first) + n;
+    if (n == 0 || m == 0 || m > 256 || end > kFeatureMaxIndex ||
+        static_cast<uint64_t>(n) * m > kAmbientMaxRays || end * m > kAmbientMaxIndex)
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (!visibility || std::isnan(reach)) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    return VCRT_SUCCESS;
+}
+
+// The launch on a device plane (checked by the callers): one wave per local tile; returns when
+// the kernel is done.
+VkResult draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, float reach,
+                               float* visibility, vcrt_occlusion_buffer_stats* stats) {
+    if (stats) {
+        *stats = vcrt_occlusion_buffer_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_occlusion");
+    }
+    if (!g.d_ft_counters) VCRT_TRY(hipMalloc(&g.d_ft_counters, kFeatureCounterBytes));
+    const VkResult t = feature_tables(first, n);
+    if (t != VK_SUCCESS) return t;
+    // u_j of j = first m .. (first + n) m - 1, sample-major (vcrt_ambient_dirs' values)
+    const uint32_t ndirs = n * m;
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ao_dirs), &g.ao_dirs_cap, ndirs, sizeof(float4)));
+    g.h_ao_dirs.resize(ndirs);
+    for (uint32_t k = 0; k < ndirs; k++) {
+        const vcrt::f3 u = vcrt::ambient_dir(first * m + k);
+        g.h_ao_dirs[k] = make_float4(u.x, u.y, u.z, 0.0f);
+    }
+    VCRT_TRY(hipMemcpyAsync(g.d_ao_dirs, g.h_ao_dirs.data(), sizeof(float4) * ndirs,
+                            hipMemcpyHostToDevice, g.stream));
+    vcrt::OcclusionBufferParams p{};
+    frame_ray_scene(p.scene, n);
+    p.visibility = reinterpret_cast<float4*>(visibility);
+    p.dirs = g.d_ao_dirs;
+    p.n = n;
+    p.m = m;
+    p.reach = reach;
+    p.use_lists = g.feature_lists ? 1u : 0u;
+    p.tallies = static_cast<unsigned long long*>(g.d_ft_counters);
+    std::vector<unsigned long long> slots(kFeatureCounterBytes / 8, 0ull);
+    if (g.local_tiles > 0) {
+        VCRT_TRY(hipMemsetAsync(g.d_ft_counters, 0, kFeatureCounterBytes, g.stream));
+        VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
+        const VkResult r = launch(g.k_frame_occlusion, (g.local_tiles + 3u) / 4u, 256, 0, p);
+        if (r != VK_SUCCESS) return r;
+        VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
+        if (stats)
+            VCRT_TRY(hipMemcpyAsync(slots.data(), g.d_ft_counters, kFeatureCounterBytes,
+                                    hipMemcpyDeviceToHost, g.stream));
+    }
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) {
+        unsigned long long counters[5] = {0, 0, 0, 0, 0};
+        for (size_t s = 0; s < slots.size(); s += 8)
+            for (int c = 0; c < 5; c++) counters[c] += slots[s + c];
+        float ms = 0.f;
+        if (g.local_tiles > 0) VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+        stats->kernel_ms = ms;
+        stats->rays = g.local_pixels * n;
+        stats->hit_rays = counters[3];
+        stats->secondary_rays = counters[3] * m;
+        stats->occluded = counters[4];
+        stats->listed_rays = counters[0];
+        stats->group_tests = counters[1];
+        stats->bound_tests = counters[2];
+    }
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, float reach,
+                                       float* visibility, vcrt_occlusion_buffer_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = ambient_args(first, n, m, reach, visibility);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernel's 16-byte stores
+    if (reinterpret_cast<uintptr_t>(visibility) & 15u) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_frame_occlusion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = draw_occlusion_device(first, n, m, reach, visibility, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_draw_occlusion(uint32_t first, uint32_t n, uint32_t m, float reach,
+                                float* visibility, vcrt_occlusion_buffer_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = ambient_args(first, n, m, reach, visibility);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.k_frame_occlusion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t elems = g.local_elems;
+    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ao_plane), &g.ao_plane_cap, elems,
+                  sizeof(float4)));
+    // packed tiles: the slots outside the frame keep what the caller's plane holds
+    if (g.desc.world_size > 1 && elems)
+        VCRT_TRY(hipMemcpyAsync(g.d_ao_plane, visibility, sizeof(float4) * elems,
+                                hipMemcpyHostToDevice, g.stream));
+    const VkResult r = draw_occlusion_device(first, n, m, reach,
+                                             reinterpret_cast<float*>(g.d_ao_plane), stats);
+    if (r != VK_SUCCESS) return r;
+    if (elems) {
+        VCRT_TRY(hipMemcpyAsync(visibility, g.d_ao_plane, sizeof(float4) * elems,
+                                hipMemcpyDeviceToHost, g.stream));
         VCRT_TRY(hipStreamSynchronize(g.stream));
     }
     if (stats) stats->host_ms = ms_since(t0);
@@ -3560,6 +3701,19 @@ int32_t vcrt_frame_rays(const vcrt_render_desc* desc, const int32_t* xy, int32_t
         }
     }
     return npixels;
+}
+
+int32_t vcrt_ambient_dirs(uint32_t first, uint32_t count, float* out) {
+    if (static_cast<uint64_t>(first) + count > (uint64_t{1} << 22))
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (count > 0 && !out) return VCRT_ERROR_INITIALIZATION_FAILED;
+    for (uint32_t k = 0; k < count; k++) {
+        const vcrt::f3 u = vcrt::ambient_dir(first + k);
+        out[3 * k + 0] = u.x;
+        out[3 * k + 1] = u.y;
+        out[3 * k + 2] = u.z;
+    }
+    return static_cast<int32_t>(count);
 }
 
 float vcrt_canonical_sin(float x) { return vcrt::sin_canonical(x); }

@@ -3725,8 +3725,9 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_trace_rays(RayQueryParams
 
 // ---------------------------------------------------------------------------------------------
 // Occlusion queries: is any sphere accepted by hit_sphere between min_t and the ray's own reach
-// (fact (6))? A code-generation unit of its own (Makefile, part 4).
-#if !defined(VCRT_PART) || VCRT_PART == 4
+// (fact (6))? A code-generation unit of its own (Makefile, part 4); the scans serve the ambient
+// visibility buffer's secondary rays too (part 10).
+#if !defined(VCRT_PART) || VCRT_PART == 4 || VCRT_PART == 10
 namespace {
 
 // min_t < t < T: hit_sphere's strict comparisons on the candidate's t (fact (6))
@@ -3914,7 +3915,9 @@ __device__ __forceinline__ bool occlude_linear(const TraceParams& p, int n, cons
 }
 
 }  // namespace
+#endif
 
+#if !defined(VCRT_PART) || VCRT_PART == 4
 // One scan per ray and no work counter: wave w of the grid takes rays 64 w + lane, then strides
 // by the grid's waves (coalesced loads of 3 + 3 + 1 dwords per ray, one byte stored per lane).
 // A wave takes the culled scan when the scene has tables and all its rays are in the guarded
@@ -4036,6 +4039,66 @@ extern "C" __global__ __launch_bounds__(1024) void vcrt_trace_cull_flat_boxes_le
 //  * else what vcrt_trace_rays runs: the per-lane culled scan on the global tables when the
 //    scene has them and every ray the wave's remaining lanes hold is in the guarded range,
 //  * else the linear scan.
+#if !defined(VCRT_PART) || VCRT_PART == 10
+namespace {
+
+// The first hit of one sample's camera ray (o, d), aa = dot(d, d), by the three routes above, as
+// a function for the ambient visibility kernel (part 10): inf is the list word of the lane's
+// quarter (15 in its low bits: no list), max_t and best enter as (kInfinity, -1). The statements
+// are vcrt_frame_features' own, which keeps its copy: called from there the function moves that
+// kernel's register allocation, and part 8's object file is to stay what it was.
+__device__ __forceinline__ void frame_first_hit(const TraceParams& S, const uint32_t inf,
+                                                const float4* tgroup, const int n, const f3 o,
+                                                const f3 d, const float aa, float& max_t,
+                                                int& best, uint32_t& listed, uint32_t& w_halves,
+                                                uint32_t& w_bounds) {
+    // (a pinhole ray starts at the camera centre: the host hands out prim_info only to
+    // a bounded scene and a centre within 2^30, the other half of the range guard)
+    const bool cam_now = (inf & 15u) != 15u && guard_a(aa);
+    if (cam_now) {
+        ++listed;
+        cfloat4* crec = (cfloat4*)S.cam_rec;
+        const float ya = recip_a(aa);
+        const v2f dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z}, a2 = {aa, aa};
+        for (int gb = 0; gb < S.nbig; ++gb)  // the big spheres (scalar loads)
+            exact_group_uniform_cam(crec + 4 * gb, (cfloat4*)S.cgroup + 5 * gb, dx, dy,
+                                    dz, a2, aa, ya, max_t, best);
+        // the quarter's listed spheres, two per record (primary.cpp)
+        const uint32_t cnt = inf & 15u;
+        const float4* lr = S.cam_rec + 4u * (uint32_t)S.nbig + 3u * (inf >> 4);
+        uint32_t iters = 0u;
+        for (uint32_t m = 0; 2u * m < cnt; ++m) {
+            ++iters;
+            const float4 q0 = lr[3u * m], q1 = lr[3u * m + 1u], id = lr[3u * m + 2u];
+            v2f hb, cc, dc;
+            pair_disc_cam(dx, dy, dz, a2, q0, q1, hb, cc, dc);
+            if (__float_as_int(hit_sign(hb.x, cc.x, dc.x)) < 0)
+                consider(candidate_t_fast(hb.x, dc.x, aa, ya), __float_as_int(id.x),
+                         max_t, best);
+            if (__float_as_int(hit_sign(hb.y, cc.y, dc.y)) < 0)
+                consider(candidate_t_fast(hb.y, dc.y, aa, ya), __float_as_int(id.y),
+                         max_t, best);
+        }
+        // issued work as the frame counts it: a pair test is half a group test
+        tally(w_halves, 2u * (uint32_t)S.nbig + wave_max_small<3>(iters));
+    } else {
+        uint32_t hit_groups = 0u, lane_cnt = 0u;
+        const bool guarded = (S.flags & kFlagSceneBounded) != 0 && aa >= 0x1p-20f &&
+                             aa <= 0x1p60f && fabsf(o.x) <= 0x1p30f &&
+                             fabsf(o.y) <= 0x1p30f && fabsf(o.z) <= 0x1p30f;
+        if (S.ncgroups > 0 && __ballot(!guarded) == 0u) {
+            scan_culled_lane<false>(S, S.cbound, tgroup, o, d, max_t, best, w_halves,
+                                    w_bounds, lane_cnt, hit_groups);
+        } else {
+            scan_spheres<false>(S, nullptr, n, o, d, max_t, best, hit_groups);
+            tally(w_halves, 2u * (uint32_t)((n + 3) >> 2));
+        }
+    }
+}
+
+}  // namespace
+#endif
+
 #if !defined(VCRT_PART) || VCRT_PART == 8
 extern "C" __global__ __launch_bounds__(256) void vcrt_frame_features(FeatureParams p_arg) {
     // the arguments through a pointer to the kernarg segment, as trace_impl reads them
@@ -4174,6 +4237,130 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_frame_features(FeaturePar
         if (nl) atomicAdd(slot + 0, nl);
         if (wh) atomicAdd(slot + 1, wh / 2u);
         if (wb) atomicAdd(slot + 2, wb);
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// The ambient visibility buffer (vcrt_draw_occlusion), a code-generation unit of its own (Makefile,
+// part 10): the feature kernel's shape -- one wave per local 8x8 tile, one lane per slot, the
+// pixel's n samples in index order, the first hit through frame_first_hit -- and after each
+// sample its m any-hit rays from P = o + t d along d' = N + u_j, N the hit's normal turned
+// against the ray, u_j the host's table (vcrt_ambient_dirs) read at wave-uniform indices, through
+// the occlusion queries' scans with the far limit `reach`. A lane whose sample missed enters them
+// occluded with a guarded dummy ray, as vcrt_occlude_rays' dead lanes do: it asks for nothing and
+// counts nothing. The wave takes the culled scan when the scene has tables and every lane's
+// (P, d') is in the guarded range, else the linear scan: the same answer (fact (6)). A lane keeps
+// two integers, its samples that hit and its secondary rays that were occluded, so the plane's
+// bits depend on the rays alone; two conversions, two divisions and one store at the end. No LDS.
+#if !defined(VCRT_PART) || VCRT_PART == 10
+extern "C" __global__ __launch_bounds__(256) void vcrt_frame_occlusion(
+    OcclusionBufferParams p_arg) {
+    // the arguments through a pointer to the kernarg segment, as trace_impl reads them
+    (void)p_arg;
+    const OcclusionBufferParams& p = *reinterpret_cast<const OcclusionBufferParams*>(
+        (__attribute__((address_space(4))) const OcclusionBufferParams*)
+            __builtin_amdgcn_kernarg_segment_ptr());
+    const TraceParams& S = p.scene;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lt = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (lt >= S.local_tiles) return;  // (the whole wave)
+    const uint32_t q = lt * 64u + lane;
+    const Pixel px = pixel_of(q, (uint32_t)S.width, (uint32_t)S.height, S.tiles_x,
+                              (uint32_t)S.world, (uint32_t)S.rank);
+    const uint32_t nsamples = p.n, nsecondary = p.m;
+    const bool lens = S.lens != nullptr;
+    uint32_t w_halves = 0u, w_bounds = 0u, listed = 0u, hits = 0u, blocked = 0u;
+    if (px.valid) {
+        const f3 p00 = mk(S.cam[0], S.cam[1], S.cam[2]);
+        const f3 du = mk(S.cam[3], S.cam[4], S.cam[5]);
+        const f3 dv = mk(S.cam[6], S.cam[7], S.cam[8]);
+        const f3 cam = mk(S.cam[9], S.cam[10], S.cam[11]);
+        const f3 corner = viewport_corner(p00, du, dv, px.x, px.y);
+        // the sphere list of the lane's 4x4 quarter (slot 8 y + x), as trace_impl reads it
+        uint32_t inf = 15u;
+        if (p.use_lists != 0u && !lens && S.prim_info != nullptr)
+            inf = S.prim_info[2u * (lt * 4u + (((lane >> 5) & 1u) << 1) + ((lane >> 2) & 1u)) + 1u];
+        const int n = S.nspheres;
+        const float4* tgroup = S.cgroup + 5 * S.nbig;  // the hierarchy's group records
+        cfloat4* jitter = (cfloat4*)S.jitter;           // wave-uniform indices: scalar loads
+        cfloat4* lens_tab = (cfloat4*)S.lens;
+        cfloat4* udir = (cfloat4*)p.dirs;
+        const float T = p.reach;
+        const bool any_reach = T > kMinT;  // else no root lies in (min_t, T): every ray is open
+        for (uint32_t k = 0; k < nsamples; ++k) {
+            const float4 j = jitter[k];
+            f3 o = cam;
+            if (lens) {
+                const float4 l = lens_tab[k];
+                o = mk(l.x, l.y, l.z);
+            }
+            const f3 d = sub(add(corner, mk(j.x, j.y, j.z)), o);
+            const float aa = dot(d, d);
+            float max_t = kInfinity;
+            int best = -1;
+            frame_first_hit(S, inf, tgroup, n, o, d, aa, max_t, best, listed, w_halves, w_bounds);
+            const bool hit = best >= 0;
+            if (hit) ++hits;
+            if (__ballot(hit && any_reach) == 0u) continue;
+            // ---- the hit's point and its normal turned against the ray ----
+            f3 P = mk(0.f, 0.f, 0.f), N = mk(0.f, 0.f, 0.f);
+            if (hit) {
+                const float4 cr = S.center_radius[best];
+                P = add(scale(max_t, d), o);
+                // shade_segment's normal: the unscaled division, else the full one (same bits)
+                const f3 pcv = sub(P, mk(cr.x, cr.y, cr.z));
+                const float yr = recip_a(cr.w);
+                N = mk(div_a(pcv.x, cr.w, yr), div_a(pcv.y, cr.w, yr), div_a(pcv.z, cr.w, yr));
+                const float nmin = fminf(fminf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+                const float nmax = fmaxf(fmaxf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+                if (!((S.flags & kFlagRadiiSafe) != 0u && nmin >= 0x1p-40f && nmax <= 0x1p30f)) {
+                    asm volatile("");
+                    N = divs(pcv, cr.w);
+                }
+                if (dot(d, N) > 0.0f) N = mk(-N.x, -N.y, -N.z);
+            }
+            const bool p_guarded = (S.flags & kFlagSceneBounded) != 0 && fabsf(P.x) <= 0x1p30f &&
+                                   fabsf(P.y) <= 0x1p30f && fabsf(P.z) <= 0x1p30f;
+            // ---- the sample's secondary rays ----
+            const uint32_t row = k * nsecondary;
+            for (uint32_t s = 0; s < nsecondary; ++s) {
+                const float4 u = udir[row + s];
+                // a lane without a hit: occluded from the start, a guarded ray
+                const f3 d2 = hit ? add(N, mk(u.x, u.y, u.z)) : mk(0.f, 1.f, 0.f);
+                const float a2 = dot(d2, d2);
+                const bool guarded = !hit || (p_guarded && a2 >= 0x1p-20f && a2 <= 0x1p60f);
+                bool occ = !hit;
+                if (S.ncgroups > 0 && __ballot(!guarded) == 0u)
+                    occ = occlude_culled_lane(S, S.cbound, tgroup, P, d2, T, occ, w_halves,
+                                              w_bounds);
+                else
+                    occ = occlude_linear(S, n, P, d2, T, occ, w_halves);
+                if (hit && occ) ++blocked;
+            }
+        }
+        // open = (hit samples' open rays) + m per sky sample = n m - blocked: integers, exact
+        const uint32_t all = nsamples * nsecondary;
+        const float v = (float)(all - blocked) / (float)all;
+        p.visibility[px.out_index] = make_float4(v, v, v, (float)hits / (float)nsamples);
+    }
+    // one atomic per wave and tally, into the block's slot (OcclusionBufferParams.tallies)
+    unsigned long long nl = listed, wh = w_halves, wb = w_bounds, nh = hits, nb = blocked;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nl += __shfl_xor(nl, off);
+        wh += __shfl_xor(wh, off);
+        wb += __shfl_xor(wb, off);
+        nh += __shfl_xor(nh, off);
+        nb += __shfl_xor(nb, off);
+    }
+    if (lane == 0) {
+        unsigned long long* slot = p.tallies + 8u * (blockIdx.x & (kFeatureTallySlots - 1u));
+        if (nl) atomicAdd(slot + 0, nl);
+        if (wh) atomicAdd(slot + 1, wh / 2u);
+        if (wb) atomicAdd(slot + 2, wb);
+        if (nh) atomicAdd(slot + 3, nh);
+        if (nb) atomicAdd(slot + 4, nb);
     }
 }
 #endif

@@ -284,6 +284,25 @@ struct FeatureParams {
 // b adds to slot b % kFeatureTallySlots, each slot a cache line of its own.
 constexpr uint32_t kFeatureTallySlots = 256;
 
+// The ambient visibility buffer (vcrt_draw_occlusion): per sample of the frame's camera rays the
+// first hit as the feature kernel finds it, then m any-hit rays from the hit point along normal +
+// u_j, counted in integers. The scene block is filled as FeatureParams' is (the call's own jitter
+// and lens tables, indexed from 0). One wave per local tile, one lane per slot.
+struct OcclusionBufferParams {
+    TraceParams scene;
+    float4* visibility;    // [elements] (open share x 3, hit share)
+    const float4* dirs;    // [n * m] u_j of j = first * m .. (first + n) * m - 1 (vcrt_ambient_dirs),
+                           //   sample-major; read at wave-uniform indices
+    uint32_t n;            // samples per pixel of the call, >= 1
+    uint32_t m;            // secondary rays per hit sample, 1 .. 256; n * m <= 4096
+    float reach;           // the secondary rays' max_t, not NaN
+    uint32_t use_lists;    // as FeatureParams.use_lists
+    unsigned long long* tallies;  // [kFeatureTallySlots][8]: per slot (64 B), [0] .. [2] as
+                                  //   FeatureParams.tallies (the primary and the secondary scans
+                                  //   together), [3] samples that hit, [4] secondary rays
+                                  //   occluded; zeroed before the launch, summed by the host
+};
+
 // TraceParams.jitter from the host's jitter (vcrt_math.h rand2) and the camera: run at
 // vcrt_begin and for each progressive frame.
 struct SetupJitterParams {

@@ -626,6 +626,20 @@ inline f3 lens_offset(uint32_t i, float radius, f3 u, f3 v) {
     const float lx = rho * sin_canonical(phi + kLensHalfPi), ly = rho * sin_canonical(phi);
     return add(scale(lx, u), scale(ly, v));
 }
+
+// The ambient visibility buffer's unit vectors (vcrt.h vcrt_ambient_dirs): the lens offsets'
+// recipe on a sphere. Index j draws a = rand(j, j + 0.5) and b = rand(j + 0.5, j) (half-integer
+// arguments, exact for j < 2^22), a height z = 1 - 2 a and an angle phi = 2 pi b; the circle at
+// that height has radius sqrt(1 - z^2), correctly rounded. One fixed sequence of fp32 operations
+// (host only: the table OcclusionBufferParams.dirs is built here).
+inline f3 ambient_dir(uint32_t j) {
+    const float fj = static_cast<float>(j);
+    const float a = rand2(fj, fj + 0.5f), b = rand2(fj + 0.5f, fj);
+    const float zc = 1.0f - 2.0f * a;
+    const float rest = 1.0f - zc * zc;
+    const float rr = __builtin_sqrtf(rest > 0.0f ? rest : 0.0f), phi = kLensTwoPi * b;
+    return f3{rr * sin_canonical(phi + kLensHalfPi), rr * sin_canonical(phi), zc};
+}
 #endif
 
 }  // namespace vcrt

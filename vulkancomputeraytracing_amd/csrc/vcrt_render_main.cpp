@@ -2,7 +2,9 @@
 // (VulkanComputeRayTracing.cpp:17-42): Begin -> DrawNextFrame x N -> End, then optionally writes
 // the frame as PFM (linear rgba32f, as the compute image holds it) or PPM (sRGB8 encoded on the
 // GPU, as the B8G8R8A8_SRGB swapchain shows it: Frontend.cpp:43). --features PREFIX adds the
-// frame's guide buffers (vcrt_draw_features) as PREFIX_albedo.ppm and PREFIX_normal.ppm.
+// frame's guide buffers (vcrt_draw_features) as PREFIX_albedo.ppm and PREFIX_normal.ppm, --ao
+// PREFIX its ambient visibility buffer (vcrt_draw_occlusion) as PREFIX_ao.ppm, sRGB8 as a frame.
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -20,7 +22,7 @@ int usage() {
                  "usage: vcrt_render [--width W] [--height H] [--spp N] [--depth D] "
                  "[--scene final|three|red|stress4096] [--frames F] [--progressive 0|1] [--device I] "
                  "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm] "
-                 "[--features PREFIX] [--feature-samples N]\n");
+                 "[--features PREFIX] [--feature-samples N] [--ao PREFIX] [--ao-rays M]\n");
     return 2;
 }
 
@@ -51,15 +53,16 @@ int main(int argc, char** argv) {
     vcrt_default_desc(&desc);
     int scene = VCRT_SCENE_FINAL, frames = 1;
     double orbit = 0.0;  // degrees about the world y axis through lookat, per frame
-    std::string out, features;
+    std::string out, features, ao;
     int feature_samples = 0;  // 0: the description's spp
+    int ao_rays = 8;          // secondary rays per sample that hits
     bool configured = false;  // any option that changes the description or the scene
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (i + 1 >= argc) return usage();
         const char* v = argv[++i];
         configured = configured || (a != "--out" && a != "--frames" && a != "--features" &&
-                                    a != "--feature-samples");
+                                    a != "--feature-samples" && a != "--ao" && a != "--ao-rays");
         if (a == "--width") desc.width = std::atoi(v);
         else if (a == "--height") desc.height = std::atoi(v);
         else if (a == "--spp") desc.samples_per_pixel = std::atoi(v);
@@ -72,6 +75,8 @@ int main(int argc, char** argv) {
         else if (a == "--out") out = v;
         else if (a == "--features") features = v;
         else if (a == "--feature-samples") feature_samples = std::atoi(v);
+        else if (a == "--ao") ao = v;
+        else if (a == "--ao-rays") ao_rays = std::atoi(v);
         else if (a == "--scene") {
             const std::string s = v;
             scene = s == "final" ? VCRT_SCENE_FINAL : s == "three" ? VCRT_SCENE_THREE
@@ -153,6 +158,31 @@ int main(int argc, char** argv) {
             }
         } else {
             std::fprintf(stderr, "DrawFeatures: %s\n", vcrt_result_string(r));
+        }
+    }
+    if (r == VK_SUCCESS && !ao.empty()) {
+        // the ambient visibility of the last frame's camera, encoded as a frame's PPM is: byte =
+        // the number of sRGB8 thresholds the channel reaches (vcrt_srgb8_thresholds)
+        const size_t n = static_cast<size_t>(desc.width) * desc.height;
+        const uint32_t samples = static_cast<uint32_t>(
+            feature_samples > 0 ? feature_samples : desc.samples_per_pixel);
+        std::vector<float> plane(4 * n);
+        r = DrawOcclusion(0, samples, static_cast<uint32_t>(ao_rays > 0 ? ao_rays : 0), 1e5f,
+                          plane.data());
+        if (r == VK_SUCCESS) {
+            float th[255];
+            vcrt_srgb8_thresholds(th);
+            std::vector<uint8_t> v8(4 * n);
+            for (size_t i = 0; i < 4 * n; i++)
+                v8[i] = static_cast<uint8_t>(std::upper_bound(th, th + 255, plane[i]) - th);
+            const std::vector<float> none;
+            if (!write_image(ao + "_ao.ppm", desc.width, desc.height, false, none, v8)) {
+                std::fprintf(stderr, "cannot write %s_ao.ppm: %s\n", ao.c_str(),
+                             std::strerror(errno));
+                r = VK_ERROR_UNKNOWN;
+            }
+        } else {
+            std::fprintf(stderr, "DrawOcclusion: %s\n", vcrt_result_string(r));
         }
     }
     EndRenderingOperation();

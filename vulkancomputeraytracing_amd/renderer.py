@@ -155,6 +155,26 @@ def frame_rays(desc: RenderDesc, xy, first: int, n: int) -> tuple[np.ndarray, np
     return origins, dirs
 
 
+MAX_AMBIENT_RAYS = 4096      # samples * rays of one draw_occlusion (vcrt.h vcrt_draw_occlusion)
+MAX_AMBIENT_INDEX = 1 << 22  # ambient directions a renderer admits (vcrt.h vcrt_ambient_dirs)
+
+
+def ambient_dirs(first: int, count: int) -> np.ndarray:
+    """float32 [count, 3]: the unit vectors u_j of j = first .. first + count - 1 that
+    Renderer.draw_occlusion adds to a hit's normal (vcrt_ambient_dirs: host only, no GPU)."""
+    try:
+        first, count = int(first), int(count)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"first, count: integers expected ({e})") from None
+    if first < 0 or count < 0:
+        raise ValueError("first and count must be >= 0")
+    if first + count > MAX_AMBIENT_INDEX:
+        raise ValueError("first + count must not exceed 2^22")
+    out = np.zeros((count, 3), np.float32)
+    N.check_count("vcrt_ambient_dirs", N.lib().vcrt_ambient_dirs(first, count, out.ctypes.data))
+    return out
+
+
 def pixel_scale_log2(max_abs_quantum_sum: float) -> int:
     """s of a pixel's quantization scale 2^s from its largest |quantum sum| (vcrt_pixel_scale_log2:
     host only, no GPU): 32 below 2^12, else the largest s with max * 2^s < 2^44. The oracle
@@ -641,6 +661,61 @@ class Renderer:
                             "group_tests": st.group_tests, "bound_tests": st.bound_tests,
                             "kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
                             "kernel": st.kernel.decode()}
+        return out
+
+    def draw_occlusion(self, samples: int | None = None, first: int = 0, rays: int = 8,
+                       reach: float | None = None, stats: bool = False, device: bool = False):
+        """The ambient visibility buffer of the frame's own camera rays (vcrt_draw_occlusion):
+        float32 [..., 4] in the rank-local framebuffer's shape ([height, width, 4] at world 1, else
+        the packed tiles [tiles, 64, 4], slots outside the frame 0). Over the sample indices
+        first .. first + samples - 1 (samples=None: the description's spp), every sample that hits
+        sends `rays` any-hit rays of reach `reach` (None: the reference's infinity, 1e5; +inf is
+        allowed; <= 0.001 leaves every ray open) from the hit point along normal + unit vector
+        (ambient_dirs); rgb is the share of open rays, a sky sample counting as fully open, and a
+        the share of samples that hit -- draw_features' coverage. Albedo x visibility is a
+        readable preview frame.
+
+        numpy through the host call; with device=True a torch tensor on the renderer's device,
+        filled through the device call after the caller's current stream is synchronised. With
+        stats=True the result is (plane, stats dict): rays, hit_rays, secondary_rays, occluded,
+        listed_rays, group_tests, bound_tests, kernel_ms, host_ms, kernel. Argument errors raise
+        ValueError before any native call. The framebuffer, the accumulation and the frame
+        statistics are left alone."""
+        first, n = _check_sample_range(first, self.desc.samples_per_pixel if samples is None
+                                       else samples)
+        try:
+            m = int(rays)
+            reach = 1e5 if reach is None else float(reach)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"rays: an integer, reach: a float expected ({e})") from None
+        if not 1 <= m <= 256:
+            raise ValueError("rays must be 1 .. 256")
+        if n * m > MAX_AMBIENT_RAYS:
+            raise ValueError("samples * rays must not exceed 4096")
+        if (first + n) * m > MAX_AMBIENT_INDEX:
+            raise ValueError("(first + samples) * rays must not exceed 2^22")
+        if reach != reach:
+            raise ValueError("reach must not be NaN")
+        lib = self._L()
+        elems, tiles = self.local_layout()
+        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
+                else (tiles, 64))
+        st = N.vcrt_occlusion_buffer_stats()
+        if device:
+            import torch
+            dev = torch.device("cuda", self.desc.device if self.desc.device >= 0
+                               else torch.cuda.current_device())
+            out = torch.zeros(lead + (4,), device=dev, dtype=torch.float32)
+            torch.cuda.current_stream(dev).synchronize()
+            N.check("vcrt_draw_occlusion_device", lib.vcrt_draw_occlusion_device(
+                first, n, m, reach, out.data_ptr(), ctypes.byref(st)))
+        else:
+            out = np.zeros(lead + (4,), dtype=np.float32)
+            N.check("vcrt_draw_occlusion", lib.vcrt_draw_occlusion(
+                first, n, m, reach, out.ctypes.data, ctypes.byref(st)))
+        if stats:
+            names = [f for f, _ in N.vcrt_occlusion_buffer_stats._fields_ if f != "kernel"]
+            return out, {**{f: getattr(st, f) for f in names}, "kernel": st.kernel.decode()}
         return out
 
     def occluded(self, origins, dirs, tmax=None, stats: bool = False):
