@@ -36,5 +36,11 @@ VkResult DrawFeatures(IN uint32_t first, IN uint32_t n, OUT float* albedo, OUT f
 // `reach` per sample that hits; a host pointer in the framebuffer's layout).
 VkResult DrawOcclusion(IN uint32_t first, IN uint32_t n, IN uint32_t m, IN float reach,
                        OUT float* visibility);
+// The denoised frame (vcrt_denoise: the edge-avoiding a-trous filter over a colour plane and
+// DrawFeatures' albedo and normal_depth, host pointers, [height][width] float4 each; a guide may
+// be NULL, which switches its terms off; params NULL takes vcrt_default_denoise_params).
+VkResult Denoise(IN const float* colour, IN const float* albedo, IN const float* normal_depth,
+                 IN int32_t width, IN int32_t height, IN const vcrt_denoise_params* params,
+                 OUT float* out);
 
 #endif

@@ -29,7 +29,8 @@
  * a frame for a denoiser (vcrt_draw_features: first-hit albedo, normal, depth, coverage and
  * sphere id of the frame's own camera rays; vcrt_frame_rays) and its ambient visibility buffer
  * (vcrt_draw_occlusion: the open share of short rays sent from those first hits;
- * vcrt_ambient_dirs).
+ * vcrt_ambient_dirs); and the denoiser those guides are for (vcrt_denoise: an edge-avoiding
+ * a-trous filter over a frame and its guide planes; vcrt_denoise_host, vcrt_denoise_scales).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -667,6 +668,106 @@ vcrt_result vcrt_draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, f
  * out [count][3]. Returns count, or a negative VkResult: VCRT_ERROR_FORMAT_NOT_SUPPORTED for
  * first + count > 2^22, VCRT_ERROR_INITIALIZATION_FAILED for a NULL out with count > 0. */
 int32_t vcrt_ambient_dirs(uint32_t first, uint32_t count, float* out /* [count][3] */);
+
+/* The denoiser those guide buffers are for: an edge-avoiding a-trous wavelet filter (Dammertz,
+ * Sewtz, Hanika, Lensch 2010) over a frame, albedo-demodulated, steered by vcrt_draw_features'
+ * planes. A pure image function of the caller's planes: a one-GPU framebuffer, or rank 0's
+ * assembled frame with guides put through vcrt_assemble_tiles. Added.
+ *
+ * Inputs, each [height][width] float4, row 0 at the top: colour, a frame (its alpha is carried
+ * through untouched); albedo and normal_depth exactly as vcrt_draw_features writes them, either
+ * may be NULL, which switches off the terms that use it. Output: one float4 plane of that shape.
+ *
+ * Scales, computed once on the host in fp32 (vcrt_denoise_scales is this as code):
+ *   k_X  = 1.0f / (sigma_X * sigma_X)   the product, then a correctly rounded division;
+ *          0 when sigma_X == 0
+ *   kl_l = k_colour * 4^l                exact: sigma_colour halves every pass
+ * A term is ON when its k is not 0 and its plane is there (normal and depth: normal_depth;
+ * albedo: albedo; colour: always there). A term that is off is the constant +0 and is not
+ * evaluated, so "off" and "k = 0" give the same bits.
+ *
+ * Pass 0 input, eps = 0x1p-10f: with demodulate != 0 and a non-NULL albedo
+ *   s_0.c = colour.c / fmaxf(albedo.c, eps)    per rgb channel, correctly rounded
+ * otherwise s_0 = colour.
+ * Pass l = 0 .. levels - 1, for pixel p = (x, y), step = 1 << l: the taps q = (x + step dx,
+ * y + step dy) for dx, dy in -2 .. 2 are visited with dy outer and dx inner, both ascending; a
+ * tap outside the frame is skipped (not clamped, not mirrored). Every fp32 operation is rounded on
+ * its own, no contraction:
+ *   h   = k5[dx + 2] * k5[dy + 2]          k5 = {1/16, 1/4, 3/8, 1/4, 1/16} (products exact)
+ *   dn  = sum over x, y, z    of (n_p - n_q)^2   left to right     (normal_depth.xyz)
+ *   rz  = (z_p - z_q) / ((fabsf(z_p) + fabsf(z_q)) + 0x1p-20f)     (normal_depth.w)
+ *   da  = sum over r, g, b, a of (a_p - a_q)^2   left to right     (albedo, coverage included)
+ *   dl  = sum over r, g, b    of (s_p - s_q)^2   left to right     (this pass's input)
+ *   X   = ((dn * k_normal + (rz * rz) * k_depth) + da * k_albedo) + dl * kl_l
+ *         (each product an ON term, else +0)
+ *   e   = 1.0f - fminf(X, 1.0f)
+ *   w   = h * (e * e)
+ *   acc.c += w * s_q.c   (rgb),   wsum += w          both start at +0
+ *   s_{l+1}(p).c = acc.c / wsum                      correctly rounded
+ * The centre tap has X = 0 and w = 9/64, so wsum > 0. The weight is a compact polynomial on
+ * purpose: no exp, so every bit is reproducible on the host.
+ * Final: out.c = s_levels.c * fmaxf(albedo.c, eps) when pass 0 demodulated, else s_levels.c;
+ * out.a = colour.a.
+ * One lane owns one output pixel and runs its 25 taps in that order, so the bits depend on the
+ * planes and the parameters only -- not on the launch shape, and not on which passes stage
+ * their footprint in LDS (VCRT_DENOISE_LDS below). The contract holds for finite planes whose
+ * s_0 is finite; anything else is filtered without a fault, deterministic, otherwise unspecified
+ * (a tap whose guide terms alone reach 1 has w = 0 and its colour is not read).
+ *
+ * vcrt_denoise_host is the definition as code (host only, no GPU; csrc/denoise.cpp).
+ * vcrt_denoise takes host pointers, staged through device planes that are kept, only grown, and
+ * freed by vcrt_end; vcrt_denoise_device device pointers, 16-B aligned, readable on the
+ * renderer's device. Both need vcrt_begin for the device, the stream and the code object, run one
+ * launch of vcrt_denoise_pass per pass on the render stream -- pass 0 fuses the demodulation, the
+ * last pass the re-modulation, the passes between go through two scratch planes kept likewise --
+ * and return when done. They leave alone the framebuffer, the accumulation, vcrt_stats and the
+ * cost order: a frame drawn after a denoise has the bits it would have had without it. The
+ * planes' size need not be the renderer's.
+ * VCRT_DENOISE_LDS=N in the environment (read at every call): the first N passes, at most the two
+ * of step 1 and 2, stage their workgroup's footprint with its halo of 2 step in LDS; unset = 2,
+ * the measured choice (profiles/denoise.json); 0 = every pass reads its taps directly. Same bits.
+ * Errors: VCRT_ERROR_FORMAT_NOT_SUPPORTED, checked first, so it reads the same before vcrt_begin:
+ * a struct_size that is not sizeof(vcrt_denoise_params), levels outside 1 .. 8, a NaN, negative
+ * or infinite sigma, a sigma so small that its k (kl_l of the last pass for the colour) is not
+ * finite, width or height outside 1 .. 65535, more than 2^26 pixels.
+ * VCRT_ERROR_INITIALIZATION_FAILED, before anything touches the GPU: a NULL colour or out, out
+ * equal to an input pointer, a misaligned device plane, and (not vcrt_denoise_host) before
+ * vcrt_begin. demodulate or sigma_albedo > 0 with a NULL albedo is not an error: those terms are
+ * off. VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object has no vcrt_denoise_pass kernel
+ * (an A/B build of an older tree). A NULL params takes vcrt_default_denoise_params. */
+typedef struct vcrt_denoise_params {
+    uint32_t struct_size;   /* sizeof(vcrt_denoise_params) */
+    int32_t  levels;        /* 1..8: passes, pass l = 0..levels-1 has tap spacing 2^l */
+    float    sigma_normal;  /* 0 = term off, for each sigma */
+    float    sigma_depth;   /* relative depth */
+    float    sigma_albedo;
+    float    sigma_colour;  /* on the filtered signal itself; halves every pass */
+    int32_t  demodulate;    /* 1: filter colour / albedo, multiply back at the end */
+} vcrt_denoise_params;
+/* The defaults: the sigmas that minimise the error of the denoised 4-spp final scene against its
+ * 256-spp frame over a small grid (profiles/denoise_defaults.json). */
+vcrt_result vcrt_default_denoise_params(vcrt_denoise_params* params);
+/* k4 = {k_normal, k_depth, k_albedo, k_colour} of params (host only); the parameter errors
+ * above. */
+vcrt_result vcrt_denoise_scales(const vcrt_denoise_params* params, float k4[4]);
+typedef struct vcrt_denoise_stats {
+    double   kernel_ms;     /* all passes, HIP events on the render stream */
+    double   host_ms;       /* wall time of the call */
+    double   pass_ms[8];    /* each pass, between the events around it */
+    int32_t  passes;        /* launches = levels */
+    int32_t  lds_passes;    /* of them, the passes that staged their footprint in LDS */
+    char     kernel[48];    /* "vcrt_denoise_pass" */
+} vcrt_denoise_stats;
+vcrt_result vcrt_denoise_host(const float* colour, const float* albedo, const float* normal_depth,
+                              int32_t width, int32_t height, const vcrt_denoise_params* params,
+                              float* out);
+vcrt_result vcrt_denoise(const float* colour, const float* albedo, const float* normal_depth,
+                         int32_t width, int32_t height, const vcrt_denoise_params* params,
+                         float* out, vcrt_denoise_stats* stats);
+vcrt_result vcrt_denoise_device(const float* colour, const float* albedo,
+                                const float* normal_depth, int32_t width, int32_t height,
+                                const vcrt_denoise_params* params, float* out,
+                                vcrt_denoise_stats* stats);
 
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file

@@ -164,6 +164,29 @@ class vcrt_occlusion_buffer_stats(ctypes.Structure):
     ]
 
 
+class vcrt_denoise_params(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("levels", ctypes.c_int32),
+        ("sigma_normal", ctypes.c_float),
+        ("sigma_depth", ctypes.c_float),
+        ("sigma_albedo", ctypes.c_float),
+        ("sigma_colour", ctypes.c_float),
+        ("demodulate", ctypes.c_int32),
+    ]
+
+
+class vcrt_denoise_stats(ctypes.Structure):
+    _fields_ = [
+        ("kernel_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("pass_ms", ctypes.c_double * 8),
+        ("passes", ctypes.c_int32),
+        ("lds_passes", ctypes.c_int32),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
 class vcrt_camera_stats(ctypes.Structure):
     _fields_ = [
         ("host_ms", ctypes.c_double),
@@ -308,6 +331,20 @@ SIGNATURES = {
                                                     ctypes.c_void_p,
                                                     ctypes.POINTER(vcrt_occlusion_buffer_stats)]),
     "vcrt_ambient_dirs": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]),
+    "vcrt_default_denoise_params": (ctypes.c_int32, [ctypes.POINTER(vcrt_denoise_params)]),
+    "vcrt_denoise_scales": (ctypes.c_int32, [ctypes.POINTER(vcrt_denoise_params),
+                                             ctypes.c_void_p]),
+    "vcrt_denoise_host": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p]),
+    "vcrt_denoise": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int32, ctypes.c_int32,
+                                      ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p,
+                                      ctypes.POINTER(vcrt_denoise_stats)]),
+    "vcrt_denoise_device": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p,
+                                             ctypes.POINTER(vcrt_denoise_stats)]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

@@ -74,3 +74,10 @@ VkResult DrawOcclusion(IN uint32_t first, IN uint32_t n, IN uint32_t m, IN float
                        OUT float* visibility) {
     return static_cast<VkResult>(vcrt_draw_occlusion(first, n, m, reach, visibility, nullptr));
 }
+
+VkResult Denoise(IN const float* colour, IN const float* albedo, IN const float* normal_depth,
+                 IN int32_t width, IN int32_t height, IN const vcrt_denoise_params* params,
+                 OUT float* out) {
+    return static_cast<VkResult>(
+        vcrt_denoise(colour, albedo, normal_depth, width, height, params, out, nullptr));
+}

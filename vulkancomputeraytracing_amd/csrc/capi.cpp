@@ -26,6 +26,7 @@
 #include "camera_lists_abi.h"
 #include "cluster.hpp"
 #include "comm_wait.hpp"
+#include "denoise_abi.h"
 #include "hip_status.hpp"
 #include "scene.hpp"
 #include "scene_update_abi.h"
@@ -111,6 +112,14 @@ struct RendererState {
     float4* d_ao_plane = nullptr;
     size_t ao_dirs_cap = 0, ao_plane_cap = 0;  // in directions, in elements
     std::vector<float4> h_ao_dirs;
+    // the denoiser (vcrt_denoise; null: the code object predates it): the two scratch planes the
+    // passes between the first and the last go through, the host call's four staging planes and
+    // the events around the passes; kept and grown only
+    hipFunction_t k_denoise_pass = nullptr, k_denoise_pass_lds = nullptr;
+    float4* d_dn_scratch[2] = {nullptr, nullptr};
+    float4* d_dn_stage[4] = {nullptr, nullptr, nullptr, nullptr};  // colour, albedo, guides, out
+    size_t dn_scratch_cap[2] = {0, 0}, dn_stage_cap[4] = {0, 0, 0, 0};  // in pixels
+    hipEvent_t ev_dn[9] = {};
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -713,6 +722,12 @@ VkResult bind_kernels() {
     if (hipModuleGetFunction(&g.k_frame_occlusion, m, "vcrt_frame_occlusion") != hipSuccess) {
         (void)hipGetLastError();
         g.k_frame_occlusion = nullptr;
+    }
+    // optional: the denoise kernels (vcrt_denoise answers the same), both or neither
+    if (hipModuleGetFunction(&g.k_denoise_pass, m, "vcrt_denoise_pass") != hipSuccess ||
+        hipModuleGetFunction(&g.k_denoise_pass_lds, m, "vcrt_denoise_pass_lds") != hipSuccess) {
+        (void)hipGetLastError();
+        g.k_denoise_pass = g.k_denoise_pass_lds = nullptr;
     }
     // optional: the camera-list kernels (vcrt_set_camera then runs the host builders)
     const std::pair<hipFunction_t*, const char*> list_kernels[] = {
@@ -2239,6 +2254,12 @@ vcrt_result vcrt_end(void) {
     if (g.d_ft_counters) (void)hipFree(g.d_ft_counters);
     if (g.d_ao_dirs) (void)hipFree(g.d_ao_dirs);
     if (g.d_ao_plane) (void)hipFree(g.d_ao_plane);
+    for (float4* b : g.d_dn_scratch)
+        if (b) (void)hipFree(b);
+    for (float4* b : g.d_dn_stage)
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : g.ev_dn)
+        if (e) (void)hipEventDestroy(e);
     if (g.d_cl_boxes) (void)hipFree(g.d_cl_boxes);
     if (g.d_cl_spheres) (void)hipFree(g.d_cl_spheres);
     if (g.d_cl_counts) (void)hipFree(g.d_cl_counts);
@@ -2785,6 +2806,155 @@ vcrt_result vcrt_draw_occlusion(uint32_t first, uint32_t n, uint32_t m, float re
                                 hipMemcpyDeviceToHost, g.stream));
         VCRT_TRY(hipStreamSynchronize(g.stream));
     }
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+// ---- the denoiser -----------------------------------------------------------------------------
+
+namespace {
+
+// VCRT_DENOISE_LDS: how many leading passes stage their footprint in LDS (at most the passes of
+// step 1 and 2). Unset: both -- see tools/denoise_bench.py and profiles/denoise.json for the A/B.
+int32_t denoise_lds_passes() {
+    static_assert(vcrt::kDenoiseLdsMaxStep == 2, "the LDS kernel takes passes 0 and 1");
+    int32_t n = 2;
+    if (const char* e = std::getenv("VCRT_DENOISE_LDS")) n = std::atoi(e);
+    return std::min(std::max(n, 0), 2);
+}
+
+// The passes on device planes (checked by the callers); returns when the last is done.
+VkResult denoise_device(const float* colour, const float* albedo, const float* normal_depth,
+                        int32_t width, int32_t height, const vcrt_denoise_params& pr,
+                        const float k4[4], float* out, vcrt_denoise_stats* stats) {
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const int32_t levels = pr.levels;
+    // pass l reads the plane pass l - 1 wrote: the colour, the scratch planes in turn, the output
+    for (int32_t b = 0; b < std::min(levels - 1, 2); b++)
+        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_dn_scratch[b]), &g.dn_scratch_cap[b], pixels,
+                      sizeof(float4)));
+    for (int32_t l = 0; l <= levels; l++)
+        if (!g.ev_dn[l]) VCRT_TRY(hipEventCreate(&g.ev_dn[l]));
+    const bool demod = pr.demodulate != 0 && albedo;
+    uint32_t terms = 0;
+    if (normal_depth && k4[0] != 0.0f) terms |= vcrt::kDenoiseNormal;
+    if (normal_depth && k4[1] != 0.0f) terms |= vcrt::kDenoiseDepth;
+    if (albedo && k4[2] != 0.0f) terms |= vcrt::kDenoiseAlbedo;
+    const int32_t lds_passes = std::min(denoise_lds_passes(), levels);
+    float kl = k4[3];
+    const float* in = colour;
+    VCRT_TRY(hipEventRecord(g.ev_dn[0], g.stream));
+    for (int32_t l = 0; l < levels; l++) {
+        vcrt::DenoiseParams p{};
+        p.in = in;
+        p.colour = colour;
+        p.albedo = albedo;
+        p.normal_depth = normal_depth;
+        p.out = l == levels - 1 ? out : reinterpret_cast<float*>(g.d_dn_scratch[l & 1]);
+        p.width = static_cast<uint32_t>(width);
+        p.height = static_cast<uint32_t>(height);
+        p.step = 1u << l;
+        p.flags = terms | (kl != 0.0f ? vcrt::kDenoiseColour : 0u) |
+                  (demod && l == 0 ? vcrt::kDenoiseDemodIn : 0u) |
+                  (demod && l == levels - 1 ? vcrt::kDenoiseModOut : 0u) |
+                  (l == levels - 1 ? vcrt::kDenoiseLast : 0u);
+        p.k_normal = k4[0];
+        p.k_depth = k4[1];
+        p.k_albedo = k4[2];
+        p.kl = kl;
+        VkResult r;
+        if (l < lds_passes) {
+            const uint32_t halo = 2u * p.step;
+            const uint32_t entries =
+                (vcrt::kDenoiseTileW + 2u * halo) * (vcrt::kDenoiseTileH + 2u * halo);
+            const bool guides = (terms & (vcrt::kDenoiseNormal | vcrt::kDenoiseDepth)) != 0;
+            const uint32_t planes =
+                1u + ((terms & vcrt::kDenoiseAlbedo) ? 1u : 0u) + (guides ? 1u : 0u);
+            p.tiles_x = (p.width + vcrt::kDenoiseTileW - 1u) / vcrt::kDenoiseTileW;
+            const uint32_t tiles_y = (p.height + vcrt::kDenoiseTileH - 1u) / vcrt::kDenoiseTileH;
+            r = launch(g.k_denoise_pass_lds, p.tiles_x * tiles_y, vcrt::kDenoiseThreads,
+                       entries * planes * static_cast<uint32_t>(sizeof(float4)), p);
+        } else {
+            p.tiles_x = (p.width + vcrt::kDenoiseRowW - 1u) / vcrt::kDenoiseRowW;
+            const uint32_t tiles_y = (p.height + vcrt::kDenoiseRowH - 1u) / vcrt::kDenoiseRowH;
+            r = launch(g.k_denoise_pass, p.tiles_x * tiles_y, vcrt::kDenoiseThreads, 0, p);
+        }
+        if (r != VK_SUCCESS) return r;
+        VCRT_TRY(hipEventRecord(g.ev_dn[l + 1], g.stream));
+        in = p.out;
+        kl = kl * 4.0f;
+    }
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) {
+        *stats = vcrt_denoise_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_denoise_pass");
+        stats->passes = levels;
+        stats->lds_passes = lds_passes;
+        float ms = 0.f;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[0], g.ev_dn[levels]));
+        stats->kernel_ms = ms;
+        for (int32_t l = 0; l < levels; l++) {
+            VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[l], g.ev_dn[l + 1]));
+            stats->pass_ms[l] = ms;
+        }
+    }
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_denoise_device(const float* colour, const float* albedo,
+                                const float* normal_depth, int32_t width, int32_t height,
+                                const vcrt_denoise_params* params, float* out,
+                                vcrt_denoise_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_denoise_params pr;
+    float k4[4];
+    const vcrt_result a = vcrt::denoise_args(colour, albedo, normal_depth, width, height, params,
+                                             out, &pr, k4);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernels' 16-byte loads and stores
+    if ((reinterpret_cast<uintptr_t>(colour) | reinterpret_cast<uintptr_t>(albedo) |
+         reinterpret_cast<uintptr_t>(normal_depth) | reinterpret_cast<uintptr_t>(out)) & 15u)
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_denoise_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = denoise_device(colour, albedo, normal_depth, width, height, pr, k4, out,
+                                      stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_denoise(const float* colour, const float* albedo, const float* normal_depth,
+                         int32_t width, int32_t height, const vcrt_denoise_params* params,
+                         float* out, vcrt_denoise_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_denoise_params pr;
+    float k4[4];
+    const vcrt_result a = vcrt::denoise_args(colour, albedo, normal_depth, width, height, params,
+                                             out, &pr, k4);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_denoise_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const float* host[3] = {colour, albedo, normal_depth};
+    const float* dev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++)  // the three inputs that are there, and the output
+        if (k == 3 || host[k])
+            VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_dn_stage[k]), &g.dn_stage_cap[k], pixels,
+                          sizeof(float4)));
+    for (int k = 0; k < 3; k++) {
+        if (!host[k]) continue;
+        VCRT_TRY(hipMemcpyAsync(g.d_dn_stage[k], host[k], sizeof(float4) * pixels,
+                                hipMemcpyHostToDevice, g.stream));
+        dev[k] = reinterpret_cast<const float*>(g.d_dn_stage[k]);
+    }
+    const VkResult r = denoise_device(dev[0], dev[1], dev[2], width, height, pr, k4,
+                                      reinterpret_cast<float*>(g.d_dn_stage[3]), stats);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(out, g.d_dn_stage[3], sizeof(float4) * pixels, hipMemcpyDeviceToHost,
+                            g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;
 }

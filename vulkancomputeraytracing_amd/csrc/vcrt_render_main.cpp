@@ -4,6 +4,8 @@
 // GPU, as the B8G8R8A8_SRGB swapchain shows it: Frontend.cpp:43). --features PREFIX adds the
 // frame's guide buffers (vcrt_draw_features) as PREFIX_albedo.ppm and PREFIX_normal.ppm, --ao
 // PREFIX its ambient visibility buffer (vcrt_draw_occlusion) as PREFIX_ao.ppm, sRGB8 as a frame.
+// --denoise FILE writes the last frame put through the denoiser (vcrt_denoise over the framebuffer
+// and the guide buffers of --feature-samples samples), PFM or PPM by FILE's suffix as --out.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -22,7 +24,8 @@ int usage() {
                  "usage: vcrt_render [--width W] [--height H] [--spp N] [--depth D] "
                  "[--scene final|three|red|stress4096] [--frames F] [--progressive 0|1] [--device I] "
                  "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm] "
-                 "[--features PREFIX] [--feature-samples N] [--ao PREFIX] [--ao-rays M]\n");
+                 "[--features PREFIX] [--feature-samples N] [--ao PREFIX] [--ao-rays M] "
+                 "[--denoise file.ppm|file.pfm] [--denoise-levels L]\n");
     return 2;
 }
 
@@ -53,7 +56,8 @@ int main(int argc, char** argv) {
     vcrt_default_desc(&desc);
     int scene = VCRT_SCENE_FINAL, frames = 1;
     double orbit = 0.0;  // degrees about the world y axis through lookat, per frame
-    std::string out, features, ao;
+    std::string out, features, ao, denoise;
+    int denoise_levels = 0;   // 0: vcrt_default_denoise_params'
     int feature_samples = 0;  // 0: the description's spp
     int ao_rays = 8;          // secondary rays per sample that hits
     bool configured = false;  // any option that changes the description or the scene
@@ -62,7 +66,8 @@ int main(int argc, char** argv) {
         if (i + 1 >= argc) return usage();
         const char* v = argv[++i];
         configured = configured || (a != "--out" && a != "--frames" && a != "--features" &&
-                                    a != "--feature-samples" && a != "--ao" && a != "--ao-rays");
+                                    a != "--feature-samples" && a != "--ao" && a != "--ao-rays" &&
+                                    a != "--denoise" && a != "--denoise-levels");
         if (a == "--width") desc.width = std::atoi(v);
         else if (a == "--height") desc.height = std::atoi(v);
         else if (a == "--spp") desc.samples_per_pixel = std::atoi(v);
@@ -77,6 +82,8 @@ int main(int argc, char** argv) {
         else if (a == "--feature-samples") feature_samples = std::atoi(v);
         else if (a == "--ao") ao = v;
         else if (a == "--ao-rays") ao_rays = std::atoi(v);
+        else if (a == "--denoise") denoise = v;
+        else if (a == "--denoise-levels") denoise_levels = std::atoi(v);
         else if (a == "--scene") {
             const std::string s = v;
             scene = s == "final" ? VCRT_SCENE_FINAL : s == "three" ? VCRT_SCENE_THREE
@@ -183,6 +190,39 @@ int main(int argc, char** argv) {
             }
         } else {
             std::fprintf(stderr, "DrawOcclusion: %s\n", vcrt_result_string(r));
+        }
+    }
+    if (r == VK_SUCCESS && !denoise.empty()) {
+        // the last frame through the a-trous filter, steered by its own guide buffers; a PPM is
+        // encoded as a frame's is: byte = the number of sRGB8 thresholds the channel reaches
+        const bool pfm = denoise.size() > 4 && denoise.compare(denoise.size() - 4, 4, ".pfm") == 0;
+        const size_t n = static_cast<size_t>(desc.width) * desc.height;
+        const uint32_t samples = static_cast<uint32_t>(
+            feature_samples > 0 ? feature_samples : desc.samples_per_pixel);
+        std::vector<float> frame(4 * n), albedo(4 * n), normal(4 * n), clean(4 * n);
+        vcrt_denoise_params dp;
+        vcrt_default_denoise_params(&dp);
+        if (denoise_levels != 0) dp.levels = denoise_levels;
+        r = ReadFramebuffer(frame.data(), frame.size());
+        if (r == VK_SUCCESS) r = DrawFeatures(0, samples, albedo.data(), normal.data(), nullptr);
+        if (r == VK_SUCCESS)
+            r = Denoise(frame.data(), albedo.data(), normal.data(), desc.width, desc.height, &dp,
+                        clean.data());
+        if (r == VK_SUCCESS) {
+            std::vector<uint8_t> c8(pfm ? 0 : 4 * n);
+            if (!pfm) {
+                float th[255];
+                vcrt_srgb8_thresholds(th);
+                for (size_t i = 0; i < 4 * n; i++)
+                    c8[i] = static_cast<uint8_t>(std::upper_bound(th, th + 255, clean[i]) - th);
+            }
+            if (!write_image(denoise, desc.width, desc.height, pfm, clean, c8)) {
+                std::fprintf(stderr, "cannot write %s: %s\n", denoise.c_str(),
+                             std::strerror(errno));
+                r = VK_ERROR_UNKNOWN;
+            }
+        } else {
+            std::fprintf(stderr, "Denoise: %s\n", vcrt_result_string(r));
         }
     }
     EndRenderingOperation();

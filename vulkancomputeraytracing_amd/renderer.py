@@ -175,6 +175,93 @@ def ambient_dirs(first: int, count: int) -> np.ndarray:
     return out
 
 
+DENOISE_FIELDS = ("levels", "sigma_normal", "sigma_depth", "sigma_albedo", "sigma_colour",
+                  "demodulate")
+
+
+def default_denoise_params() -> dict:
+    """vcrt_default_denoise_params as a dict: levels, the four sigmas and demodulate."""
+    p = N.vcrt_denoise_params()
+    N.check("vcrt_default_denoise_params", N.lib().vcrt_default_denoise_params(ctypes.byref(p)))
+    return {f: getattr(p, f) for f in DENOISE_FIELDS}
+
+
+def _denoise_params(given: dict) -> N.vcrt_denoise_params:
+    """The C parameter block: the defaults with the fields `given` names (None: the default)."""
+    unknown = set(given) - set(DENOISE_FIELDS)
+    if unknown:
+        raise TypeError(f"denoise: unexpected parameters {sorted(unknown)}")
+    p = N.vcrt_denoise_params()
+    N.check("vcrt_default_denoise_params", N.lib().vcrt_default_denoise_params(ctypes.byref(p)))
+    for name, v in given.items():
+        if v is None:
+            continue
+        try:
+            setattr(p, name, int(v) if name in ("levels", "demodulate") else float(v))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"denoise: {name}: a number expected ({e})") from None
+    return p
+
+
+def denoise_scales(**params) -> np.ndarray:
+    """float32 [4]: k_normal, k_depth, k_albedo, k_colour = 1 / sigma^2 (0 for sigma 0) of the
+    denoiser's parameters (vcrt_denoise_scales: host only, no GPU)."""
+    k = np.zeros(4, np.float32)
+    p = _denoise_params(params)
+    N.check("vcrt_denoise_scales", N.lib().vcrt_denoise_scales(ctypes.byref(p), k.ctypes.data))
+    return k
+
+
+def _check_planes(colour, albedo, normal_depth):
+    """The planes of a denoise call, validated before any native call: numpy float32
+    C-contiguous [height, width, 4] (converted), or torch float32 contiguous tensors of that shape
+    on one CUDA device (as they are); the guides may be None. Raises ValueError."""
+    planes = {"colour": colour, "albedo": albedo, "normal_depth": normal_depth}
+    if colour is None:
+        raise ValueError("colour: a plane expected")
+    torch_in = _is_torch(colour)
+    out = {}
+    for name, a in planes.items():
+        if a is None:
+            out[name] = None
+            continue
+        if _is_torch(a) != torch_in:
+            raise ValueError("the planes must all be numpy arrays or all torch tensors")
+        if torch_in:
+            import torch
+            if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous():
+                raise ValueError(f"{name}: a contiguous float32 CUDA tensor expected")
+            if a.device != colour.device:
+                raise ValueError(f"{name}: torch tensors must be on one CUDA device")
+        else:
+            try:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{name}: not convertible to a float32 array ({e})") from None
+        if a.ndim != 3 or a.shape[2] != 4 or tuple(a.shape) != tuple(out.get("colour", a).shape):
+            raise ValueError(f"{name}: shape [height, width, 4] of the colour plane expected, "
+                             f"got {tuple(a.shape)}")
+        out[name] = a
+    return out["colour"], out["albedo"], out["normal_depth"]
+
+
+def denoise_host(colour, albedo=None, normal_depth=None, **params) -> np.ndarray:
+    """The denoiser's definition on the host (vcrt_denoise_host: no GPU): the edge-avoiding
+    a-trous filter of vcrt.h over numpy planes [height, width, 4]; Renderer.denoise computes the
+    same bits on the GPU. params: levels, sigma_normal, sigma_depth, sigma_albedo, sigma_colour,
+    demodulate (omitted: default_denoise_params)."""
+    if _is_torch(colour):
+        raise ValueError("denoise_host takes numpy planes")
+    colour, albedo, normal_depth = _check_planes(colour, albedo, normal_depth)
+    p = _denoise_params(params)
+    out = np.empty_like(colour)
+    N.check("vcrt_denoise_host", N.lib().vcrt_denoise_host(
+        colour.ctypes.data, None if albedo is None else albedo.ctypes.data,
+        None if normal_depth is None else normal_depth.ctypes.data,
+        colour.shape[1], colour.shape[0], ctypes.byref(p), out.ctypes.data))
+    return out
+
+
 def pixel_scale_log2(max_abs_quantum_sum: float) -> int:
     """s of a pixel's quantization scale 2^s from its largest |quantum sum| (vcrt_pixel_scale_log2:
     host only, no GPU): 32 below 2^12, else the largest s with max * 2^s < 2^44. The oracle
@@ -716,6 +803,77 @@ class Renderer:
         if stats:
             names = [f for f, _ in N.vcrt_occlusion_buffer_stats._fields_ if f != "kernel"]
             return out, {**{f: getattr(st, f) for f in names}, "kernel": st.kernel.decode()}
+        return out
+
+    def denoise(self, frame=None, guides=None, *, levels=None, sigma_normal=None,
+                sigma_depth=None, sigma_albedo=None, sigma_colour=None, demodulate=None,
+                stats: bool = False, device: bool = False):
+        """The frame through the denoiser (vcrt_denoise): the edge-avoiding a-trous filter of
+        vcrt.h, albedo-demodulated, steered by draw_features' planes -- on the GPU the bits
+        denoise_host computes.
+
+        frame: a plane [height, width, 4]; None takes the renderer's own framebuffer. guides: a
+        dict with "albedo" and "normal_depth" as draw_features returns them (either may be
+        missing or None: its terms are off); None calls draw_features(samples=spp). Both defaults
+        need the whole frame on this renderer, so they work at world size 1 only: a shard puts
+        its gathered frame and guide planes through assemble_tiles and passes them in. params:
+        the keyword parameters (None: default_denoise_params').
+
+        numpy planes go through the host call and give a numpy plane. torch tensors on the
+        renderer's device go through the device call on their data_ptr(), after the caller's
+        current stream is synchronised, and give a torch tensor: no host round trip. device=True
+        makes the defaults torch tensors (the framebuffer is filtered where it lies). With
+        stats=True the result is (plane, stats dict): kernel_ms, host_ms, pass_ms, passes,
+        lds_passes, kernel. Shape and dtype errors raise ValueError before any native call. The
+        framebuffer, the accumulation and the frame statistics are left alone."""
+        lib = self._L()
+        p = _denoise_params(dict(levels=levels, sigma_normal=sigma_normal, sigma_depth=sigma_depth,
+                                 sigma_albedo=sigma_albedo, sigma_colour=sigma_colour,
+                                 demodulate=demodulate))
+        if (frame is None or guides is None) and self.desc.world_size != 1:
+            raise ValueError(
+                "denoise: at world size > 1 a rank holds packed tiles; gather the frame and the "
+                "guide planes, rebuild them with assemble_tiles and pass frame= and guides=")
+        given = [frame] + [v for v in (guides or {}).values()]
+        if any(v is not None and _is_torch(v) for v in given):
+            device = True
+        if guides is None:
+            guides = self.draw_features(sphere=False, device=device)
+        own = None  # the renderer's framebuffer on the device: filtered where it lies
+        if frame is None and device:
+            import torch
+            own, _ = self.framebuffer_device()
+            frame = torch.empty((self.desc.height, self.desc.width, 4), dtype=torch.float32,
+                                device=torch.device(
+                                    "cuda", self.desc.device if self.desc.device >= 0
+                                    else torch.cuda.current_device()))  # receives the result
+        elif frame is None:
+            frame = self.read_framebuffer()
+        colour, albedo, nd = _check_planes(frame, guides.get("albedo"),
+                                           guides.get("normal_depth"))
+        st = N.vcrt_denoise_stats()
+        h, w = int(colour.shape[0]), int(colour.shape[1])
+        if _is_torch(colour):
+            import torch
+            if self.desc.device >= 0 and colour.device.index != self.desc.device:
+                raise ValueError(f"planes on {colour.device}, the renderer on device "
+                                 f"{self.desc.device}")
+            out = colour if own else torch.empty_like(colour)
+            torch.cuda.current_stream(colour.device).synchronize()
+            N.check("vcrt_denoise_device", lib.vcrt_denoise_device(
+                own or colour.data_ptr(), None if albedo is None else albedo.data_ptr(),
+                None if nd is None else nd.data_ptr(), w, h, ctypes.byref(p), out.data_ptr(),
+                ctypes.byref(st)))
+        else:
+            out = np.empty_like(colour)
+            N.check("vcrt_denoise", lib.vcrt_denoise(
+                colour.ctypes.data, None if albedo is None else albedo.ctypes.data,
+                None if nd is None else nd.ctypes.data, w, h, ctypes.byref(p), out.ctypes.data,
+                ctypes.byref(st)))
+        if stats:
+            return out, {"kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
+                         "pass_ms": list(st.pass_ms)[:st.passes], "passes": st.passes,
+                         "lds_passes": st.lds_passes, "kernel": st.kernel.decode()}
         return out
 
     def occluded(self, origins, dirs, tmax=None, stats: bool = False):
