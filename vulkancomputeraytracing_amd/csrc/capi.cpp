@@ -3,8 +3,10 @@
 // Replaces the compute half of the reference's Renderer.cpp: the rgba32f storage image
 // (Renderer.cpp:433-468) becomes a device float4 buffer, the compute pipeline
 // (:532-543) a HIP module, and the per-frame vkCmdDispatch(W/16,H/16,1) + vkQueueSubmit
-// (:204-225, :673-686) one persistent-kernel launch on a HIP stream. All state is file-static,
-// as in the reference (Renderer.cpp:13-33): one renderer per process.
+// (:204-225, :673-686) one persistent-kernel launch on a HIP stream. All state is one file-level
+// object, as in the reference (Renderer.cpp:13-33): one renderer per process. Its device buffers,
+// pinned buffers and events are owners (device_resources.hpp) that free themselves, so teardown
+// is an assignment of a fresh state (vcrt_end) and there is no list of frees to maintain.
 #include <dlfcn.h>
 #include <unistd.h>
 
@@ -27,6 +29,7 @@
 #include "cluster.hpp"
 #include "comm_wait.hpp"
 #include "denoise_abi.h"
+#include "device_resources.hpp"
 #include "hip_status.hpp"
 #include "scene.hpp"
 #include "scene_update_abi.h"
@@ -36,6 +39,9 @@
 
 namespace {
 
+using vcrt::DeviceBuffer;
+using vcrt::Event;
+using vcrt::PinnedBuffer;
 using vcrt::to_vk;
 
 // segments (u64 at 8), work_done[2] (u64 at 16), then the work-queue counters from 256
@@ -53,7 +59,7 @@ struct RendererState {
     int num_cus = 0;
     size_t max_lds = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_resolve = nullptr;
+    Event ev_start, ev_stop, ev_resolve;
     VkPipelineShaderStageCreateInfo stage{};
     hipFunction_t k_trace_lds = nullptr, k_trace_smem = nullptr, k_assemble = nullptr,
                   k_fill = nullptr, k_trace_lds_stats = nullptr, k_trace_smem_stats = nullptr,
@@ -77,49 +83,40 @@ struct RendererState {
     hipFunction_t k_smem_lens = nullptr, k_flat_lens = nullptr, k_flat_lens_cost = nullptr,
                   k_flat_global_lens = nullptr, k_flat_global_lens_cost = nullptr,
                   k_flat_boxes_lens = nullptr, k_flat_boxes_lens_cost = nullptr;
-    float* d_rq_rays = nullptr;  // [cap][6]: the origins, then the directions
-    float4* d_rq_radiance = nullptr;
-    uint4* d_rq_hits = nullptr;
-    size_t rq_rays_cap = 0, rq_radiance_cap = 0, rq_hits_cap = 0;  // in rays
-    void* d_rq_counters = nullptr;
+    DeviceBuffer<float> d_rq_rays;  // [n][3] the origins, then [n][3] the directions
+    DeviceBuffer<float4> d_rq_radiance;
+    DeviceBuffer<vcrt_ray_hit> d_rq_hits;
+    DeviceBuffer<unsigned long long> d_rq_counters;
     // occlusion queries (vcrt_occlude_rays; null: the code object predates them): the host call
     // stages its rays in d_rq_rays and the reaches and answers here; tallies in d_rq_counters
     hipFunction_t k_occlude_rays = nullptr;
-    float* d_oq_tmax = nullptr;
-    uint8_t* d_oq_occluded = nullptr;
-    size_t oq_tmax_cap = 0, oq_occluded_cap = 0;  // in rays
+    DeviceBuffer<float> d_oq_tmax;
+    DeviceBuffer<uint8_t> d_oq_occluded;
     // feature buffers (vcrt_draw_features; null: the code object predates them): the jitter
     // terms and lens origins of the call's own sample indices (the frame's tables are left
     // alone), the host call's staging planes and the tallies' slots; kept and grown only
     hipFunction_t k_frame_features = nullptr;
     bool feature_lists = true;  // VCRT_FEATURE_LISTS=0: no ray takes the camera-ray lists
-    float2* d_ft_jitter_in = nullptr;
-    float4* d_ft_jitter = nullptr;
-    float4* d_ft_lens = nullptr;
-    size_t ft_jitter_in_cap = 0, ft_jitter_cap = 0, ft_lens_cap = 0;  // in samples
+    DeviceBuffer<float2> d_ft_jitter_in;
+    DeviceBuffer<float4> d_ft_jitter, d_ft_lens;
     std::vector<float2> h_ft_jitter;
     std::vector<float4> h_ft_lens;
-    float4* d_ft_albedo = nullptr;
-    float4* d_ft_normal_depth = nullptr;
-    int32_t* d_ft_sphere = nullptr;
-    size_t ft_albedo_cap = 0, ft_normal_depth_cap = 0, ft_sphere_cap = 0;  // in elements
-    void* d_ft_counters = nullptr;
+    DeviceBuffer<float4> d_ft_albedo, d_ft_normal_depth;
+    DeviceBuffer<int32_t> d_ft_sphere;
+    DeviceBuffer<unsigned long long> d_ft_counters;
     // the ambient visibility buffer (vcrt_draw_occlusion; null: the code object predates it): the
     // u_j table of the call and the host call's staging plane, kept and grown only; the jitter and
     // lens tables and the tallies' slots are the feature buffers'
     hipFunction_t k_frame_occlusion = nullptr;
-    float4* d_ao_dirs = nullptr;
-    float4* d_ao_plane = nullptr;
-    size_t ao_dirs_cap = 0, ao_plane_cap = 0;  // in directions, in elements
+    DeviceBuffer<float4> d_ao_dirs, d_ao_plane;
     std::vector<float4> h_ao_dirs;
     // the denoiser (vcrt_denoise; null: the code object predates it): the two scratch planes the
     // passes between the first and the last go through, the host call's four staging planes and
     // the events around the passes; kept and grown only
     hipFunction_t k_denoise_pass = nullptr, k_denoise_pass_lds = nullptr;
-    float4* d_dn_scratch[2] = {nullptr, nullptr};
-    float4* d_dn_stage[4] = {nullptr, nullptr, nullptr, nullptr};  // colour, albedo, guides, out
-    size_t dn_scratch_cap[2] = {0, 0}, dn_stage_cap[4] = {0, 0, 0, 0};  // in pixels
-    hipEvent_t ev_dn[9] = {};
+    DeviceBuffer<float4> d_dn_scratch[2];
+    DeviceBuffer<float4> d_dn_stage[4];  // colour, albedo, guides, out
+    Event ev_dn[9];
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -131,9 +128,8 @@ struct RendererState {
     // segments, later frames hand out the blocks most expensive first
     int cost_order = -1;
     bool cost_partition = false;  // the partition is the cost partition (default_chunk)
-    uint32_t* d_pixel_cost = nullptr;   // [total_pixels] segments (TraceParams.pixel_cost)
-    uint32_t* d_block_order = nullptr;  // [blocks] TraceParams.block_order
-    size_t cost_words = 0, order_words = 0;
+    DeviceBuffer<uint32_t> d_pixel_cost;   // [total_pixels] segments (TraceParams.pixel_cost)
+    DeviceBuffer<uint32_t> d_block_order;  // [blocks] TraceParams.block_order
     uint64_t order_key = 0;  // the configuration the order was measured for (0: none)
     uint32_t nch_magic[2] = {0u, 0u};  // TraceParams.nch_magic of the partition
     // deferred fetches (TraceParams.fetch_min / fetch_wait; VCRT_FETCH_MIN, VCRT_FETCH_WAIT;
@@ -145,46 +141,40 @@ struct RendererState {
     int debug_stats = 0;  // 1: the stats kernels; 2: the product kernels with a debug buffer
                           //    (builds with VCRT_WAVE_END_TIMES record wave start/end times)
     uint32_t work_flags = 0;
-    void* d_debug = nullptr;
-    uint32_t* d_region = nullptr;  // stats kernels: [waves][kRegionCount] region entry counts
-    size_t region_words = 0;
+    DeviceBuffer<unsigned long long> d_debug;  // vcrt_stats.debug's image
+    DeviceBuffer<uint32_t> d_region;  // stats kernels: [waves][kRegionCount] region entry counts
     // scene
     int32_t nspheres = 0;
     bool scene_bounded = false;  // every |center|, radius <= 2^30: discriminants stay finite
     bool radii_safe = false;     // every |radius| in [2^-40, 2^30] (kFlagRadiiSafe)
     int32_t accum_log2 = vcrt::kAccumMaxScaleLog2;  // the scale s pixels start at (flags)
-    float4* d_geom = nullptr;  // pair-SoA groups of four (+1 padding group)
-    float4* d_center_radius = nullptr;
-    float4* d_shade = nullptr;
-    float4* d_material = nullptr;  // (material id, 1 / param, Schlick r0^2, 0) per sphere
+    DeviceBuffer<float4> d_geom;  // pair-SoA groups of four (+1 padding group)
+    DeviceBuffer<float4> d_center_radius, d_shade;
+    DeviceBuffer<float4> d_material;  // (material id, 1 / param, Schlick r0^2, 0) per sphere
     // culled-scan tables (cluster.hpp); ncgroups == 0 when culling does not apply
     int32_t ncgroups = 0, ncbig = 0;
     float cmargin[4] = {0, 0, 0, 0};  // box margin constants (CullTables::margin)
     bool cslab_on = false;            // the shared y slab (CullTables::slab, slab_lohi)
     float cslab[2] = {0, 0};
-    float4* d_cgroup = nullptr;
-    float4* d_cbound = nullptr;
-    float4* d_cbound_nf = nullptr;
-    float4* d_cnode = nullptr;
-    float4* d_cnode_nf = nullptr;  // node-pair boxes, near/far layout, padded to whole chunks
-    float4* d_ctop = nullptr;
+    DeviceBuffer<float4> d_cgroup, d_cbound, d_cbound_nf, d_cnode;
+    DeviceBuffer<float4> d_cnode_nf;  // node-pair boxes, near/far layout, padded to whole chunks
+    DeviceBuffer<float4> d_ctop;
     // the footprint tables of the LDS-table flat scan (CullTables::fp_*), packed to their width
-    uint32_t* d_fp_tab = nullptr;
+    DeviceBuffer<uint32_t> d_fp_tab;
     float cfp_x[2] = {1, 0}, cfp_z[2] = {1, 0}, cfp_y[2] = {0, 0}, cfp_k2 = 0;
     uint32_t cfp_always = 0xffffffffu;
     // the group-level footprint tables (CullTables::gf_*) and whether a frame may use them
-    uint4* d_gf_tab = nullptr;
+    DeviceBuffer<uint4> d_gf_tab;
     float cgf_x[2] = {1, 0}, cgf_z[2] = {1, 0}, cgf_k2 = 0;
     uint32_t cgf_n = 0, cgf_always[4] = {0, 0, 0, 0};
     bool cgf_ok = false;
-    uint32_t* d_prim_info = nullptr;  // camera-ray tile lists (primary.cpp), flat scan only
-    uint16_t* d_prim_ids = nullptr;
-    float4* d_cam_rec = nullptr;  // camera-relative records: big groups, sphere lists
-    bool primary_lists = true;        // VCRT_PRIMARY_LISTS=0 turns them off
-    // the installed lists' sizes and their buffers' capacities (vcrt_set_camera reuses the
-    // buffers and grows them only): ids, pair records; info words, ids, floats of d_cam_rec
-    size_t prim_nids = 0, prim_npairs = 0;
-    size_t prim_info_cap = 0, prim_ids_cap = 0, cam_rec_cap = 0;
+    // camera-ray tile lists (primary.cpp), flat scan only; vcrt_set_camera reuses the buffers
+    // and grows them only
+    DeviceBuffer<uint32_t> d_prim_info;
+    DeviceBuffer<uint16_t> d_prim_ids;
+    DeviceBuffer<float> d_cam_rec;  // camera-relative records: big groups, sphere lists
+    bool primary_lists = true;      // VCRT_PRIMARY_LISTS=0 turns them off
+    size_t prim_nids = 0, prim_npairs = 0;  // the installed lists' sizes: ids, pair records
     // the scene as vcrt_set_scene got it and its culling tables: vcrt_set_camera's host builders
     // (VCRT_CAMERA_LISTS=host, or a code object without the list kernels) and sizes
     std::vector<vcrt_sphere> h_spheres;
@@ -193,22 +183,19 @@ struct RendererState {
     // scratch: grown boxes and sphere entries, counts + offsets + totals; kept and grown only
     hipFunction_t k_cl_prepare = nullptr, k_cl_count = nullptr, k_cl_scan = nullptr,
                   k_cl_fill = nullptr;
-    double* d_cl_boxes = nullptr;
-    double* d_cl_spheres = nullptr;
-    uint32_t* d_cl_counts = nullptr;
-    size_t cl_boxes_cap = 0, cl_spheres_cap = 0, cl_counts_cap = 0;  // elements
-    uint32_t* h_cl_totals = nullptr;  // pinned [2]
-    hipEvent_t ev_cl[2] = {nullptr, nullptr};
+    DeviceBuffer<double> d_cl_boxes, d_cl_spheres;
+    DeviceBuffer<uint32_t> d_cl_counts;
+    PinnedBuffer<uint32_t> h_cl_totals;  // [2]
+    Event ev_cl[2];
     vcrt_camera_stats cam_stats{};
     // vcrt_update_spheres: the refit kernels (scene_update.hip; null: the code object predates
     // them), the staged spheres, the summary and its pinned copy; kept and grown only
     hipFunction_t k_su_rows = nullptr, k_su_groups = nullptr, k_su_levels = nullptr,
                   k_su_footprint = nullptr;
-    float* d_su_spheres = nullptr;
-    size_t su_spheres_cap = 0;  // floats
-    vcrt::SceneSummary* d_su_summary = nullptr;
-    vcrt::SceneSummary* h_su_summary = nullptr;  // pinned
-    hipEvent_t ev_su[2] = {nullptr, nullptr};
+    DeviceBuffer<float> d_su_spheres;
+    DeviceBuffer<vcrt::SceneSummary> d_su_summary;
+    PinnedBuffer<vcrt::SceneSummary> h_su_summary;
+    Event ev_su[2];
     vcrt_scene_update_stats su_stats{};
     // h_ct holds the grouping but not yet the tables of h_spheres: the device refit leaves them
     // on the device, and current_tables() restates them when the host needs them
@@ -219,41 +206,41 @@ struct RendererState {
     int32_t tail_start = 0, tail_chunk = 1, tail_nchunks = 0;  // TraceParams' tail
     uint32_t total_pixels = 0, total_items = 0;
     bool direct = false;  // one item per pixel, not progressive: lanes write pixels (kFlagDirect)
-    double* d_accum = nullptr;  // [total_pixels][4] exact sums of the quantized chunk sums
+    DeviceBuffer<double> d_accum;  // [total_pixels][4] exact sums of the quantized chunk sums
     // d_accum holds zeros: a memset, or the last resolve wrote them back (vcrt_resolve
     // zero_accum), so a non-progressive frame needs no memset of its own
     bool accum_clean = false;
     // Outlier quanta (vcrt_math.h "Accumulation"): [total_pixels] the float bits of each pixel's
     // largest |quantum sum| that passed 2^12 (0: none); once one has, every frame of the
     // configuration quantizes each pixel at its own scale (pixel_scale, kFlagPixelScale)
-    uint32_t* d_pixel_emax = nullptr;
+    DeviceBuffer<uint32_t> d_pixel_emax;
     bool pixel_scale = false;
     int32_t min_scale = vcrt::kAccumMaxScaleLog2;  // the smallest pixel scale so far
     uint64_t accumulated = 0;               // samples per pixel accumulated (progressive)
     // the host's jitter (jx, jy) of a frame's sample indices: two pinned buffers used in turn,
     // each reused only once the copy recorded by its event is done (progressive frames set up
     // their jitter without waiting for the stream)
-    float2* h_jitter[2] = {nullptr, nullptr};
+    PinnedBuffer<float2> h_jitter[2];
     // the lens origins of the same sample indices (desc.lens_radius > 0, else null), built on
     // the host (vcrt_math.h lens_offset) in the same two turns and under the same events
-    float4* h_lens[2] = {nullptr, nullptr};
-    float4* d_lens = nullptr;  // TraceParams.lens
-    hipEvent_t ev_jitter[2] = {nullptr, nullptr};
+    PinnedBuffer<float4> h_lens[2];
+    DeviceBuffer<float4> d_lens;  // TraceParams.lens
+    Event ev_jitter[2];
     int jitter_slot = 0;
-    float* d_srgb_thresholds = nullptr;
-    uchar4* d_srgb = nullptr;
+    DeviceBuffer<float> d_srgb_thresholds;
+    DeviceBuffer<uchar4> d_srgb;  // vcrt_read_framebuffer_srgb8's staging, kept and grown only
     // per-frame inputs / outputs
-    float2* d_jitter_in = nullptr;  // the host's jitter (jx, jy) of the frame's sample indices
-    float4* d_jitter = nullptr;     // TraceParams.jitter (vcrt_setup_jitter)
-    float4* d_corner = nullptr;     // TraceParams.corner (vcrt_setup_jitter, at vcrt_begin)
-    float4* d_fb_own = nullptr;
-    float4* d_fb = nullptr;  // current render target (own or caller-provided)
+    DeviceBuffer<float2> d_jitter_in;  // the host's jitter (jx, jy) of the frame's sample indices
+    DeviceBuffer<float4> d_jitter;     // TraceParams.jitter (vcrt_setup_jitter)
+    DeviceBuffer<float4> d_corner;     // TraceParams.corner (vcrt_setup_jitter, at vcrt_begin)
+    DeviceBuffer<float4> d_fb_own;
+    float4* d_fb = nullptr;  // current render target (own, the gather's or caller-provided)
     size_t fb_bytes = 0;
-    void* d_counters = nullptr;
+    DeviceBuffer<unsigned long long> d_counters;  // kCounterBytes
     // the counters' first four u64 (outlier max, segments, work tallies), read back each frame:
     // host-pinned, written by vcrt_resolve (which then zeroes d_counters: counters_clean) or
     // copied when no resolve runs
-    unsigned long long* h_counters = nullptr;
+    PinnedBuffer<unsigned long long> h_counters;
     bool counters_clean = false;
     uint32_t tiles_x = 0, local_tiles = 0;
     uint32_t local_elems = 0;   // float4 elements of the rank-local framebuffer
@@ -264,14 +251,19 @@ struct RendererState {
     ncclComm_t comm = nullptr;  // non-blocking (comm_wait.hpp): every wait has a deadline
     bool comm_lost = false;     // the communicator failed or timed out and was aborted: every
                                 // later draw returns VK_ERROR_DEVICE_LOST (until vcrt_begin)
-    float4* d_gather = nullptr;  // rank 0: [world][pad_tiles][64], its own tiles in slot 0
-    float4* d_frame = nullptr;   // rank 0: the assembled frame [height][width]
-    hipEvent_t ev_gather_start = nullptr, ev_gather = nullptr;
+    DeviceBuffer<float4> d_gather;  // rank 0: [world][pad_tiles][64], its own tiles in slot 0
+    DeviceBuffer<float4> d_frame;   // rank 0: the assembled frame [height][width]
+    Event ev_gather_start, ev_gather;
     vcrt::Camera cam{};
     vcrt_stats stats{};
 };
 
-RendererState g;
+// The state lives on the heap and is never deleted: a file-static RendererState would run its
+// members' destructors at process exit, and a process that ends without vcrt_end would then call
+// hipFree and hipEventDestroy from a static destructor, possibly after the HIP runtime has torn
+// itself down. As it is, such a process makes no HIP call at exit; the resources are released in
+// vcrt_end alone, by move-assigning a fresh state.
+RendererState& g = *new RendererState;
 
 #define VCRT_TRY(expr)                          \
     do {                                        \
@@ -498,41 +490,29 @@ std::array<float, 12> camera_array() {
     return c;
 }
 
+// Whether a frame of camera `cam` (camera_array) gets the camera-ray lists. The camera phase of
+// the flat scans traces a fresh camera ray from its quarter's list when the ray is in the guarded
+// range. Its origin is the camera centre, a frame constant, so that half of the guard (every
+// |component| <= 2^30, in a bounded scene; also rejects NaN) is decided here: a frame that fails
+// it gets no lists, and its camera rays take the main scan, which tests their origin itself.
+bool lists_allowed(const std::array<float, 12>& cam) {
+    return g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
+           std::fabs(cam[11]) <= 0x1p30f;
+}
+
 void free_scene() {
-    if (g.d_geom) (void)hipFree(g.d_geom);
-    if (g.d_center_radius) (void)hipFree(g.d_center_radius);
-    if (g.d_shade) (void)hipFree(g.d_shade);
-    if (g.d_material) (void)hipFree(g.d_material);
-    g.d_geom = nullptr;
-    g.d_center_radius = nullptr;
-    g.d_shade = nullptr;
-    g.d_material = nullptr;
-    if (g.d_cgroup) (void)hipFree(g.d_cgroup);
-    if (g.d_cbound) (void)hipFree(g.d_cbound);
-    if (g.d_cbound_nf) (void)hipFree(g.d_cbound_nf);
-    if (g.d_cnode) (void)hipFree(g.d_cnode);
-    if (g.d_cnode_nf) (void)hipFree(g.d_cnode_nf);
-    if (g.d_ctop) (void)hipFree(g.d_ctop);
-    if (g.d_fp_tab) (void)hipFree(g.d_fp_tab);
-    g.d_fp_tab = nullptr;
-    if (g.d_gf_tab) (void)hipFree(g.d_gf_tab);
-    g.d_gf_tab = nullptr;
+    for (DeviceBuffer<float4>* b : {&g.d_geom, &g.d_center_radius, &g.d_shade, &g.d_material,
+                                    &g.d_cgroup, &g.d_cbound, &g.d_cbound_nf, &g.d_cnode,
+                                    &g.d_cnode_nf, &g.d_ctop})
+        b->reset();
+    g.d_fp_tab.reset();
+    g.d_gf_tab.reset();
     g.cgf_ok = false;
     g.cgf_n = 0;
-    if (g.d_prim_info) (void)hipFree(g.d_prim_info);
-    if (g.d_prim_ids) (void)hipFree(g.d_prim_ids);
-    if (g.d_cam_rec) (void)hipFree(g.d_cam_rec);
-    g.d_cam_rec = nullptr;
-    g.d_prim_info = nullptr;
-    g.d_prim_ids = nullptr;
+    g.d_prim_info.reset();
+    g.d_prim_ids.reset();
+    g.d_cam_rec.reset();
     g.prim_nids = g.prim_npairs = 0;
-    g.prim_info_cap = g.prim_ids_cap = g.cam_rec_cap = 0;
-    g.d_cgroup = nullptr;
-    g.d_cbound = nullptr;
-    g.d_cbound_nf = nullptr;
-    g.d_cnode = nullptr;
-    g.d_cnode_nf = nullptr;
-    g.d_ctop = nullptr;
     g.ncgroups = 0;
     g.ncbig = 0;
     g.nspheres = 0;
@@ -579,10 +559,29 @@ std::vector<float> node_near_far(const vcrt::CullTables& ct) {
     return near_far(nodes);
 }
 
-hipError_t upload_near_far(const std::vector<float>& nf, float4** out) {
-    hipError_t e = hipMalloc(out, sizeof(float) * nf.size());
+// A host table into an (empty) scene buffer of its size, on the null stream.
+template <typename T, typename H>
+hipError_t upload(DeviceBuffer<T>& out, const std::vector<H>& table) {
+    const size_t bytes = sizeof(H) * table.size();
+    const hipError_t e = out.reserve((bytes + sizeof(T) - 1) / sizeof(T));
     if (e != hipSuccess) return e;
-    return hipMemcpy(*out, nf.data(), sizeof(float) * nf.size(), hipMemcpyHostToDevice);
+    return hipMemcpy(out.data(), table.data(), bytes, hipMemcpyHostToDevice);
+}
+
+// Every |center component| and |radius| <= 2^30: discriminants stay finite (scene_bounded).
+bool values_bounded(const vcrt_sphere* s, int32_t count) {
+    for (int32_t i = 0; i < count; i++)
+        for (float v : {s[i].center[0], s[i].center[1], s[i].center[2], s[i].radius})
+            if (!(std::fabs(v) <= 0x1p30f)) return false;  // also rejects NaN
+    return true;
+}
+
+// Every |radius| in [2^-40, 2^30] (kFlagRadiiSafe).
+bool values_radii_safe(const vcrt_sphere* s, int32_t count) {
+    for (int32_t i = 0; i < count; i++)
+        if (!(std::fabs(s[i].radius) >= 0x1p-40f && std::fabs(s[i].radius) <= 0x1p30f))
+            return false;
+    return true;
 }
 
 // The linear scan table of a scene (vcrt_set_scene): count / 4 groups rounded up, one more for
@@ -640,124 +639,96 @@ std::vector<float> group_records(const vcrt::CullTables& ct) {
     return rec;
 }
 
-// hipModuleGetFunction of a required entry point: a code object without it (e.g. an A/B build of
-// an older tree) is an incompatible shader binary, not an unknown error (hipErrorNotFound used to
-// map to VK_ERROR_UNKNOWN: profiles/r04_ab_log.md, run 7)
-#define VCRT_BIND(fn, m, name)                                                   \
-    do {                                                                         \
-        const hipError_t e_ = hipModuleGetFunction(fn, m, name);                 \
-        if (e_ == hipErrorNotFound) return VK_ERROR_INCOMPATIBLE_SHADER_BINARY_EXT; \
-        if (e_ != hipSuccess) return to_vk(e_);                                  \
-    } while (0)
+// Every entry point the library binds. Group 0 is required: a code object without one (e.g. an
+// A/B build of an older tree) is an incompatible shader binary, not an unknown error
+// (hipErrorNotFound used to map to VK_ERROR_UNKNOWN: profiles/r04_ab_log.md, run 7). Every other
+// group is optional (code objects built before the feature lack it, and the call that needs it
+// answers VK_ERROR_FEATURE_NOT_PRESENT or takes its host path) and all or nothing: a group with
+// a miss has none of its kernels.
+struct KernelRow {
+    hipFunction_t RendererState::*field;
+    const char* name;
+    int group;
+};
+using RS = RendererState;
+constexpr KernelRow kKernels[] = {
+    {&RS::k_trace_lds, "vcrt_trace_lds", 0},
+    {&RS::k_trace_smem, "vcrt_trace_smem", 0},
+    {&RS::k_assemble, "vcrt_assemble", 0},
+    {&RS::k_fill, "vcrt_fill", 0},
+    {&RS::k_resolve, "vcrt_resolve", 0},
+    {&RS::k_encode, "vcrt_encode_srgb8", 0},
+    {&RS::k_setup_jitter, "vcrt_setup_jitter", 0},
+    {&RS::k_trace_lds_stats, "vcrt_trace_lds_stats", 0},
+    {&RS::k_trace_smem_stats, "vcrt_trace_smem_stats", 0},
+    {&RS::k_trace_cull, "vcrt_trace_cull", 0},
+    {&RS::k_trace_cull_stats, "vcrt_trace_cull_stats", 0},
+    {&RS::k_trace_cull_lane_lds, "vcrt_trace_cull_lane_lds", 0},
+    {&RS::k_trace_cull_lane_lds_stats, "vcrt_trace_cull_lane_lds_stats", 0},
+    {&RS::k_trace_cull_lane, "vcrt_trace_cull_lane", 0},
+    {&RS::k_trace_cull_lane_stats, "vcrt_trace_cull_lane_stats", 0},
+    {&RS::k_trace_cull_lane_lds_wide, "vcrt_trace_cull_lane_lds_wide", 0},
+    {&RS::k_trace_cull_lane_lds_wide_stats, "vcrt_trace_cull_lane_lds_wide_stats", 0},
+    {&RS::k_trace_cull_flat, "vcrt_trace_cull_flat", 0},
+    {&RS::k_trace_cull_flat_stats, "vcrt_trace_cull_flat_stats", 0},
+    {&RS::k_trace_cull_flat_global, "vcrt_trace_cull_flat_global", 0},
+    {&RS::k_trace_cull_flat_global_stats, "vcrt_trace_cull_flat_global_stats", 0},
+    // the boxes-in-LDS flat scan and its stats build, both or neither
+    {&RS::k_trace_cull_flat_boxes, "vcrt_trace_cull_flat_boxes", 1},
+    {&RS::k_trace_cull_flat_boxes_stats, "vcrt_trace_cull_flat_boxes_stats", 1},
+    // the flat scans' cost-order builds, each on its own
+    {&RS::k_trace_cull_flat_cost, "vcrt_trace_cull_flat_cost", 2},
+    {&RS::k_trace_cull_flat_global_cost, "vcrt_trace_cull_flat_global_cost", 3},
+    {&RS::k_trace_cull_flat_boxes_cost, "vcrt_trace_cull_flat_boxes_cost", 4},
+    {&RS::k_trace_rays, "vcrt_trace_rays", 5},
+    // the thin-lens frame kernels, each on its own (lens_kernels_bound asks for all seven)
+    {&RS::k_smem_lens, "vcrt_trace_smem_lens", 6},
+    {&RS::k_flat_lens, "vcrt_trace_cull_flat_lens", 7},
+    {&RS::k_flat_lens_cost, "vcrt_trace_cull_flat_lens_cost", 8},
+    {&RS::k_flat_global_lens, "vcrt_trace_cull_flat_global_lens", 9},
+    {&RS::k_flat_global_lens_cost, "vcrt_trace_cull_flat_global_lens_cost", 10},
+    {&RS::k_flat_boxes_lens, "vcrt_trace_cull_flat_boxes_lens", 11},
+    {&RS::k_flat_boxes_lens_cost, "vcrt_trace_cull_flat_boxes_lens_cost", 12},
+    {&RS::k_occlude_rays, "vcrt_occlude_rays", 13},
+    {&RS::k_frame_features, "vcrt_frame_features", 14},
+    {&RS::k_frame_occlusion, "vcrt_frame_occlusion", 15},
+    // the denoise kernels, both or neither
+    {&RS::k_denoise_pass, "vcrt_denoise_pass", 16},
+    {&RS::k_denoise_pass_lds, "vcrt_denoise_pass_lds", 16},
+    // the camera-list kernels, each on its own (vcrt_set_camera asks for all four, else it runs
+    // the host builders)
+    {&RS::k_cl_prepare, "vcrt_camlist_prepare", 17},
+    {&RS::k_cl_count, "vcrt_camlist_count", 18},
+    {&RS::k_cl_scan, "vcrt_camlist_scan", 19},
+    {&RS::k_cl_fill, "vcrt_camlist_fill", 20},
+    // the scene-refit kernels, likewise (vcrt_update_spheres else rebuilds as vcrt_set_scene)
+    {&RS::k_su_rows, "vcrt_scene_rows", 21},
+    {&RS::k_su_groups, "vcrt_scene_groups", 22},
+    {&RS::k_su_levels, "vcrt_scene_levels", 23},
+    {&RS::k_su_footprint, "vcrt_scene_footprint", 24},
+};
+constexpr size_t kKernelCount = sizeof(kKernels) / sizeof(kKernels[0]);
 
-VkResult bind_kernels() {
-    hipModule_t m = static_cast<hipModule_t>(g.stage.module);
-    VCRT_BIND(&g.k_trace_lds, m, "vcrt_trace_lds");
-    VCRT_BIND(&g.k_trace_smem, m, "vcrt_trace_smem");
-    VCRT_BIND(&g.k_assemble, m, "vcrt_assemble");
-    VCRT_BIND(&g.k_fill, m, "vcrt_fill");
-    VCRT_BIND(&g.k_resolve, m, "vcrt_resolve");
-    VCRT_BIND(&g.k_encode, m, "vcrt_encode_srgb8");
-    VCRT_BIND(&g.k_setup_jitter, m, "vcrt_setup_jitter");
-    VCRT_BIND(&g.k_trace_lds_stats, m, "vcrt_trace_lds_stats");
-    VCRT_BIND(&g.k_trace_smem_stats, m, "vcrt_trace_smem_stats");
-    VCRT_BIND(&g.k_trace_cull, m, "vcrt_trace_cull");
-    VCRT_BIND(&g.k_trace_cull_stats, m, "vcrt_trace_cull_stats");
-    VCRT_BIND(&g.k_trace_cull_lane_lds, m, "vcrt_trace_cull_lane_lds");
-    VCRT_BIND(&g.k_trace_cull_lane_lds_stats, m, "vcrt_trace_cull_lane_lds_stats");
-    VCRT_BIND(&g.k_trace_cull_lane, m, "vcrt_trace_cull_lane");
-    VCRT_BIND(&g.k_trace_cull_lane_stats, m, "vcrt_trace_cull_lane_stats");
-    VCRT_BIND(&g.k_trace_cull_flat, m, "vcrt_trace_cull_flat");
-    VCRT_BIND(&g.k_trace_cull_flat_stats, m, "vcrt_trace_cull_flat_stats");
-    VCRT_BIND(&g.k_trace_cull_flat_global, m, "vcrt_trace_cull_flat_global");
-    VCRT_BIND(&g.k_trace_cull_flat_global_stats, m, "vcrt_trace_cull_flat_global_stats");
-    // optional: code objects built before the boxes-in-LDS flat scan lack it (A/B builds)
-    if (hipModuleGetFunction(&g.k_trace_cull_flat_boxes, m, "vcrt_trace_cull_flat_boxes") !=
-            hipSuccess ||
-        hipModuleGetFunction(&g.k_trace_cull_flat_boxes_stats, m,
-                             "vcrt_trace_cull_flat_boxes_stats") != hipSuccess) {
+// The table's entry points of module m into fn (parallel to kKernels); the state is not touched.
+VkResult bind_kernels(hipModule_t m, hipFunction_t (&fn)[kKernelCount]) {
+    for (size_t i = 0; i < kKernelCount; i++) {
+        const hipError_t e = hipModuleGetFunction(&fn[i], m, kKernels[i].name);
+        if (e == hipSuccess) continue;
+        fn[i] = nullptr;
+        if (kKernels[i].group == 0)
+            return e == hipErrorNotFound ? VK_ERROR_INCOMPATIBLE_SHADER_BINARY_EXT : to_vk(e);
         (void)hipGetLastError();
-        g.k_trace_cull_flat_boxes = g.k_trace_cull_flat_boxes_stats = nullptr;
     }
-    // optional as well (A/B builds of earlier trees): the flat scans' cost-order builds
-    const std::pair<hipFunction_t*, const char*> cost_kernels[] = {
-        {&g.k_trace_cull_flat_cost, "vcrt_trace_cull_flat_cost"},
-        {&g.k_trace_cull_flat_global_cost, "vcrt_trace_cull_flat_global_cost"},
-        {&g.k_trace_cull_flat_boxes_cost, "vcrt_trace_cull_flat_boxes_cost"}};
-    for (const auto& [fp, name] : cost_kernels)
-        if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
-            (void)hipGetLastError();
-            *fp = nullptr;
-        }
-    // optional: the ray-query kernel (vcrt_trace_rays answers VK_ERROR_FEATURE_NOT_PRESENT)
-    if (hipModuleGetFunction(&g.k_trace_rays, m, "vcrt_trace_rays") != hipSuccess) {
-        (void)hipGetLastError();
-        g.k_trace_rays = nullptr;
-    }
-    // optional: the thin-lens frame kernels (a lens renderer answers the same without them)
-    const std::pair<hipFunction_t*, const char*> lens_kernels[] = {
-        {&g.k_smem_lens, "vcrt_trace_smem_lens"},
-        {&g.k_flat_lens, "vcrt_trace_cull_flat_lens"},
-        {&g.k_flat_lens_cost, "vcrt_trace_cull_flat_lens_cost"},
-        {&g.k_flat_global_lens, "vcrt_trace_cull_flat_global_lens"},
-        {&g.k_flat_global_lens_cost, "vcrt_trace_cull_flat_global_lens_cost"},
-        {&g.k_flat_boxes_lens, "vcrt_trace_cull_flat_boxes_lens"},
-        {&g.k_flat_boxes_lens_cost, "vcrt_trace_cull_flat_boxes_lens_cost"}};
-    for (const auto& [fp, name] : lens_kernels)
-        if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
-            (void)hipGetLastError();
-            *fp = nullptr;
-        }
-    // optional: the occlusion-query kernel (vcrt_occlude_rays answers the same)
-    if (hipModuleGetFunction(&g.k_occlude_rays, m, "vcrt_occlude_rays") != hipSuccess) {
-        (void)hipGetLastError();
-        g.k_occlude_rays = nullptr;
-    }
-    // optional: the feature-buffer kernel (vcrt_draw_features answers the same)
-    if (hipModuleGetFunction(&g.k_frame_features, m, "vcrt_frame_features") != hipSuccess) {
-        (void)hipGetLastError();
-        g.k_frame_features = nullptr;
-    }
-    // optional: the ambient-visibility kernel (vcrt_draw_occlusion answers the same)
-    if (hipModuleGetFunction(&g.k_frame_occlusion, m, "vcrt_frame_occlusion") != hipSuccess) {
-        (void)hipGetLastError();
-        g.k_frame_occlusion = nullptr;
-    }
-    // optional: the denoise kernels (vcrt_denoise answers the same), both or neither
-    if (hipModuleGetFunction(&g.k_denoise_pass, m, "vcrt_denoise_pass") != hipSuccess ||
-        hipModuleGetFunction(&g.k_denoise_pass_lds, m, "vcrt_denoise_pass_lds") != hipSuccess) {
-        (void)hipGetLastError();
-        g.k_denoise_pass = g.k_denoise_pass_lds = nullptr;
-    }
-    // optional: the camera-list kernels (vcrt_set_camera then runs the host builders)
-    const std::pair<hipFunction_t*, const char*> list_kernels[] = {
-        {&g.k_cl_prepare, "vcrt_camlist_prepare"},
-        {&g.k_cl_count, "vcrt_camlist_count"},
-        {&g.k_cl_scan, "vcrt_camlist_scan"},
-        {&g.k_cl_fill, "vcrt_camlist_fill"}};
-    for (const auto& [fp, name] : list_kernels)
-        if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
-            (void)hipGetLastError();
-            *fp = nullptr;
-        }
-    // optional: the scene-refit kernels (vcrt_update_spheres then rebuilds as vcrt_set_scene)
-    const std::pair<hipFunction_t*, const char*> refit_kernels[] = {
-        {&g.k_su_rows, "vcrt_scene_rows"},
-        {&g.k_su_groups, "vcrt_scene_groups"},
-        {&g.k_su_levels, "vcrt_scene_levels"},
-        {&g.k_su_footprint, "vcrt_scene_footprint"}};
-    for (const auto& [fp, name] : refit_kernels)
-        if (hipModuleGetFunction(fp, m, name) != hipSuccess) {
-            (void)hipGetLastError();
-            *fp = nullptr;
-        }
-    VCRT_TRY(hipModuleGetFunction(&g.k_trace_cull_lane_lds_wide, m,
-                                  "vcrt_trace_cull_lane_lds_wide"));
-    VCRT_TRY(hipModuleGetFunction(&g.k_trace_cull_lane_lds_wide_stats, m,
-                                  "vcrt_trace_cull_lane_lds_wide_stats"));
+    for (size_t i = 0; i < kKernelCount; i++)
+        if (fn[i] == nullptr)
+            for (size_t j = 0; j < kKernelCount; j++)
+                if (kKernels[j].group == kKernels[i].group) fn[j] = nullptr;
     return VK_SUCCESS;
 }
 
+// Loads a code object (path; null: the one beside the library, else the embedded copy) and binds
+// its kernels, then commits: only when every required kernel is there does the new module take
+// the old one's place. A failed load leaves the stage and every kernel as they were.
 VkResult load_code_object(const char* path) {
     VkPipelineShaderStageCreateInfo stage{};
     VkResult r;
@@ -772,9 +743,16 @@ VkResult load_code_object(const char* path) {
             r = CreateShaderStageFromFile(nullptr, VK_SHADER_STAGE_COMPUTE_BIT, &stage);
     }
     if (r != VK_SUCCESS) return r;
+    hipFunction_t fn[kKernelCount];
+    r = bind_kernels(static_cast<hipModule_t>(stage.module), fn);
+    if (r != VK_SUCCESS) {
+        DestroyShaderStage(&stage);
+        return r;
+    }
     DestroyShaderStage(&g.stage);
     g.stage = stage;
-    return bind_kernels();
+    for (size_t i = 0; i < kKernelCount; i++) g.*kKernels[i].field = fn[i];
+    return VK_SUCCESS;
 }
 
 // The caller's description as this library's struct. struct_size is sizeof(vcrt_render_desc), or
@@ -827,8 +805,9 @@ struct FbView {
     uint32_t elems;
 };
 FbView fb_view() {
-    if (g.d_frame)
-        return {g.d_frame, static_cast<uint32_t>(g.desc.width) * static_cast<uint32_t>(g.desc.height)};
+    if (g.d_frame.data())
+        return {g.d_frame.data(),
+                static_cast<uint32_t>(g.desc.width) * static_cast<uint32_t>(g.desc.height)};
     return {g.d_fb, g.local_elems};
 }
 
@@ -846,21 +825,62 @@ VkResult launch(hipFunction_t f, uint32_t grid, uint32_t block, uint32_t lds, Pa
     return VK_SUCCESS;
 }
 
+// One timed launch of a query or guide kernel with tallies of its own, waited for: `counters`
+// (words u64, allocated on first use) is zeroed and handed to `bind`, which points the params at
+// it; the launch runs between ev_start and ev_stop. With a host destination the counters come
+// back into it and *ms is the kernel time; without one neither is read.
+template <typename Params, typename Bind>
+VkResult timed_launch(hipFunction_t f, uint32_t grid, uint32_t block, Params& params,
+                      DeviceBuffer<unsigned long long>& counters, size_t words, Bind&& bind,
+                      unsigned long long* host, float* ms) {
+    const size_t bytes = words * sizeof(unsigned long long);
+    VCRT_TRY(counters.reserve(words));
+    bind(counters.data());
+    VCRT_TRY(hipMemsetAsync(counters.data(), 0, bytes, g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_start.get(), g.stream));
+    const VkResult r = launch(f, grid, block, 0, params);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipEventRecord(g.ev_stop.get(), g.stream));
+    if (host)
+        VCRT_TRY(hipMemcpyAsync(host, counters.data(), bytes, hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (host) VCRT_TRY(hipEventElapsedTime(ms, g.ev_start.get(), g.ev_stop.get()));
+    return VK_SUCCESS;
+}
+
+// FeatureParams.tallies, OcclusionBufferParams.tallies: slots of 64 B, summed by the callers
+constexpr size_t kFeatureCounterWords = 8 * vcrt::kFeatureTallySlots;  // u64
+
+// The timed launch of a kernel that traces the frame's own camera rays (vcrt_draw_features,
+// vcrt_draw_occlusion): one wave per local tile, its tallies' slots in d_ft_counters. A rank
+// without tiles launches nothing, and *ms stays 0.
+template <typename Params>
+VkResult frame_ray_launch(hipFunction_t f, Params& p, unsigned long long* slots, float* ms) {
+    if (g.local_tiles == 0) {
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+        return VK_SUCCESS;
+    }
+    return timed_launch(f, (g.local_tiles + 3u) / 4u, 256, p, g.d_ft_counters,
+                        kFeatureCounterWords, [&p](unsigned long long* c) { p.tallies = c; },
+                        slots, ms);
+}
+
 // Zero the pixels' sums and their outlier record (a new scene, vcrt_begin, a reset): every
 // pixel starts again at the scale 2^32 (vcrt_math.h "Accumulation"). On the render stream, and
 // waited for: the render stream is non-blocking, so a memset on the null stream would not be
 // ordered before the next frame's kernels (a 2-GiB memset still running then zeroed the last
 // rows' sums of an 8192 x 8192 frame).
 hipError_t reset_sums() {
-    if (g.d_accum) {
-        const hipError_t e = hipMemsetAsync(g.d_accum, 0, 32u * static_cast<size_t>(g.total_pixels),
-                                            g.stream);
+    if (g.d_accum.data()) {
+        const hipError_t e = hipMemsetAsync(g.d_accum.data(), 0,
+                                            32u * static_cast<size_t>(g.total_pixels), g.stream);
         if (e != hipSuccess) return e;
         g.accum_clean = true;
     }
-    if (g.d_pixel_emax) {
-        const hipError_t e = hipMemsetAsync(
-            g.d_pixel_emax, 0, sizeof(uint32_t) * static_cast<size_t>(g.total_pixels), g.stream);
+    if (g.d_pixel_emax.data()) {
+        const hipError_t e =
+            hipMemsetAsync(g.d_pixel_emax.data(), 0,
+                           sizeof(uint32_t) * static_cast<size_t>(g.total_pixels), g.stream);
         if (e != hipSuccess) return e;
     }
     if (g.stream) {
@@ -880,28 +900,30 @@ VkResult setup_jitter(uint64_t base, bool corners = false) {
     const int spp = g.desc.samples_per_pixel;
     const int slot = g.jitter_slot;
     g.jitter_slot ^= 1;
-    VCRT_TRY(hipEventSynchronize(g.ev_jitter[slot]));  // its last copy (two frames ago) is done
-    make_jitter(base, spp, g.h_jitter[slot]);
-    VCRT_TRY(hipMemcpyAsync(g.d_jitter_in, g.h_jitter[slot], sizeof(float2) * spp,
+    // its last copy (two frames ago) is done
+    VCRT_TRY(hipEventSynchronize(g.ev_jitter[slot].get()));
+    make_jitter(base, spp, g.h_jitter[slot].data());
+    VCRT_TRY(hipMemcpyAsync(g.d_jitter_in.data(), g.h_jitter[slot].data(), sizeof(float2) * spp,
                             hipMemcpyHostToDevice, g.stream));
-    if (g.d_lens) {  // the lens origins of the same sample indices: centre + offset_i
+    if (g.d_lens.data()) {  // the lens origins of the same sample indices: centre + offset_i
+        float4* lens = g.h_lens[slot].data();
         for (int k = 0; k < spp; k++) {
             const vcrt::f3 o = vcrt::add(
                 g.cam.center, vcrt::lens_offset(static_cast<uint32_t>(base + k),
                                                 g.desc.lens_radius, g.cam.u, g.cam.v));
-            g.h_lens[slot][k] = make_float4(o.x, o.y, o.z, 0.0f);
+            lens[k] = make_float4(o.x, o.y, o.z, 0.0f);
         }
-        VCRT_TRY(hipMemcpyAsync(g.d_lens, g.h_lens[slot], sizeof(float4) * spp,
+        VCRT_TRY(hipMemcpyAsync(g.d_lens.data(), lens, sizeof(float4) * spp,
                                 hipMemcpyHostToDevice, g.stream));
     }
-    VCRT_TRY(hipEventRecord(g.ev_jitter[slot], g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_jitter[slot].get(), g.stream));
     vcrt::SetupJitterParams sp{};
-    sp.jitter_in = g.d_jitter_in;
-    sp.jitter = g.d_jitter;
+    sp.jitter_in = g.d_jitter_in.data();
+    sp.jitter = g.d_jitter.data();
     sp.nsamples = static_cast<uint32_t>(spp);
     const std::array<float, 12> cam = camera_array();
     for (int i = 0; i < 12; i++) sp.cam[i] = cam[i];
-    sp.corner = corners ? g.d_corner : nullptr;
+    sp.corner = corners ? g.d_corner.data() : nullptr;
     sp.slots = g.total_pixels;
     sp.tiles_x = g.tiles_x;
     sp.rank = static_cast<uint32_t>(g.desc.rank);
@@ -936,15 +958,11 @@ void comm_release(bool abort) {
         g.comm = nullptr;
     }
     if (g.stream) (void)hipStreamSynchronize(g.stream);
-    if (g.d_gather) (void)hipFree(g.d_gather);
-    if (g.d_frame) (void)hipFree(g.d_frame);
-    if (g.ev_gather) (void)hipEventDestroy(g.ev_gather);
-    if (g.ev_gather_start) (void)hipEventDestroy(g.ev_gather_start);
-    g.d_gather = nullptr;
-    g.d_frame = nullptr;
-    g.ev_gather = nullptr;
-    g.ev_gather_start = nullptr;
-    g.d_fb = g.d_fb_own;
+    g.d_gather.reset();
+    g.d_frame.reset();
+    g.ev_gather.reset();
+    g.ev_gather_start.reset();
+    g.d_fb = g.d_fb_own.data();
 }
 
 // A communicator failure inside a draw: abort it and report the device lost (the reference's
@@ -963,14 +981,14 @@ VkResult comm_fail() {
 // communicator is non-blocking: the group is enqueued when its state leaves ncclInProgress
 // (bounded wait), and the caller waits for ev_gather with a deadline (wait_gather).
 VkResult gather_frame() {
-    VCRT_TRY(hipEventRecord(g.ev_gather_start, g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_gather_start.get(), g.stream));
     const size_t n = static_cast<size_t>(g.pad_tiles) * 64 * 4;  // floats per rank
     auto ok = [](ncclResult_t e) { return e == ncclSuccess || e == ncclInProgress; };
     bool good = ok(ncclGroupStart());
     if (good) {
         if (g.desc.rank == 0) {
             for (int32_t peer = 1; peer < g.desc.world_size && good; peer++)
-                good = ok(ncclRecv(reinterpret_cast<float*>(g.d_gather) + n * peer, n,
+                good = ok(ncclRecv(reinterpret_cast<float*>(g.d_gather.data()) + n * peer, n,
                                    ncclFloat32, peer, g.comm, g.stream));
         } else {
             good = ok(ncclSend(g.d_fb, n, ncclFloat32, 0, g.comm, g.stream));
@@ -981,7 +999,7 @@ VkResult gather_frame() {
                                           vcrt::comm_timeout_ms()) != vcrt::WaitResult::kDone)
         return comm_fail();
     if (g.desc.rank == 0) {
-        vcrt::AssembleParams ap{g.d_gather,    g.d_frame,         g.desc.width,
+        vcrt::AssembleParams ap{g.d_gather.data(),    g.d_frame.data(),         g.desc.width,
                                 g.desc.height, g.desc.world_size, g.tiles_x,
                                 g.pad_tiles};
         const uint64_t total = static_cast<uint64_t>(g.desc.width) * g.desc.height;
@@ -990,7 +1008,7 @@ VkResult gather_frame() {
             256, 0, ap);
         if (r != VK_SUCCESS) return r;
     }
-    VCRT_TRY(hipEventRecord(g.ev_gather, g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_gather.get(), g.stream));
     return VK_SUCCESS;
 }
 
@@ -1001,7 +1019,7 @@ VkResult wait_gather() {
     hipError_t ev = hipSuccess;
     const vcrt::WaitResult w = vcrt::wait_with_deadline(
         [&ev] {
-            ev = hipEventQuery(g.ev_gather);
+            ev = hipEventQuery(g.ev_gather.get());
             if (ev == hipSuccess) return vcrt::PollState::kDone;
             if (ev != hipErrorNotReady) return vcrt::PollState::kFailed;
             return comm_state(g.comm) == vcrt::PollState::kFailed ? vcrt::PollState::kFailed
@@ -1165,18 +1183,6 @@ KernelChoice select_kernel() {
     return KernelChoice{f, fs, base, fc, fname, block, lds, variant};
 }
 
-// A device buffer of at least `rays` elements of `bytes_each`, kept between calls (the query
-// staging buffers, the camera lists): grown, its contents dropped, when too small.
-hipError_t grow(void** buf, size_t* cap, size_t rays, size_t bytes_each) {
-    if (rays <= *cap) return hipSuccess;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc(buf, rays * bytes_each);
-    if (e == hipSuccess) *cap = rays;
-    return e;
-}
-
 // The camera-ray lists of primary.cpp into the buffers a frame reads (TraceParams.prim_info,
 // prim_ids, cam_rec): the two infos interleaved; the big groups' camera-relative records, then the
 // sphere lists' pairs, then 12 zero floats. The buffers are kept and only grow (free_scene drops
@@ -1190,14 +1196,12 @@ VkResult install_camera_lists(const vcrt::CullTables& ct, const vcrt::PrimaryLis
         info[2 * e] = pl.info[e];
         info[2 * e + 1] = sl.info[e];
     }
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_info), &g.prim_info_cap, info.size(),
-                  sizeof(uint32_t)));
-    VCRT_TRY(hipMemcpy(g.d_prim_info, info.data(), sizeof(uint32_t) * info.size(),
+    VCRT_TRY(g.d_prim_info.reserve(info.size()));
+    VCRT_TRY(hipMemcpy(g.d_prim_info.data(), info.data(), sizeof(uint32_t) * info.size(),
                        hipMemcpyHostToDevice));
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_ids), &g.prim_ids_cap,
-                  pl.ids.size() + 1, sizeof(uint16_t)));
+    VCRT_TRY(g.d_prim_ids.reserve(pl.ids.size() + 1));
     if (!pl.ids.empty())
-        VCRT_TRY(hipMemcpy(g.d_prim_ids, pl.ids.data(), sizeof(uint16_t) * pl.ids.size(),
+        VCRT_TRY(hipMemcpy(g.d_prim_ids.data(), pl.ids.data(), sizeof(uint16_t) * pl.ids.size(),
                            hipMemcpyHostToDevice));
     // the camera fast trace's records: the big groups', then the sphere lists' pairs
     std::vector<float> crec;
@@ -1205,9 +1209,8 @@ VkResult install_camera_lists(const vcrt::CullTables& ct, const vcrt::PrimaryLis
     crec.resize(static_cast<size_t>(ct.nbig) * 16);
     crec.insert(crec.end(), sl.rec.begin(), sl.rec.end());
     crec.resize(crec.size() + 12, 0.0f);  // never empty
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cam_rec), &g.cam_rec_cap, crec.size(),
-                  sizeof(float)));
-    VCRT_TRY(hipMemcpy(g.d_cam_rec, crec.data(), sizeof(float) * crec.size(),
+    VCRT_TRY(g.d_cam_rec.reserve(crec.size()));
+    VCRT_TRY(hipMemcpy(g.d_cam_rec.data(), crec.data(), sizeof(float) * crec.size(),
                        hipMemcpyHostToDevice));
     g.prim_nids = pl.ids.size();
     g.prim_npairs = sl.rec.size() / 12;
@@ -1269,30 +1272,25 @@ VkResult build_camera_lists_device() {
     p.world = static_cast<uint32_t>(g.desc.world_size);
     p.tiles_x = g.tiles_x;
     p.ids_ok = p.ngroups <= 0xFFFFu ? 1u : 0u;
-    p.ctop = reinterpret_cast<const float*>(g.d_ctop);
-    p.cnode = reinterpret_cast<const float*>(g.d_cnode);
-    p.cbound = reinterpret_cast<const float*>(g.d_cbound);
-    p.cgroup = reinterpret_cast<const float*>(g.d_cgroup);
-    p.center_radius = reinterpret_cast<const float*>(g.d_center_radius);
+    p.ctop = reinterpret_cast<const float*>(g.d_ctop.data());
+    p.cnode = reinterpret_cast<const float*>(g.d_cnode.data());
+    p.cbound = reinterpret_cast<const float*>(g.d_cbound.data());
+    p.cgroup = reinterpret_cast<const float*>(g.d_cgroup.data());
+    p.center_radius = reinterpret_cast<const float*>(g.d_center_radius.data());
     const size_t nbox = static_cast<size_t>(p.ngroups) + p.nnodes + p.ntops;
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cl_boxes), &g.cl_boxes_cap,
-                  nbox * vcrt::kCamListBox, sizeof(double)));
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cl_spheres), &g.cl_spheres_cap,
-                  static_cast<size_t>(p.nspheres) * vcrt::kCamListBox, sizeof(double)));
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cl_counts), &g.cl_counts_cap,
-                  4 * static_cast<size_t>(p.n) + 2, sizeof(uint32_t)));
-    if (!g.h_cl_totals) VCRT_TRY(hipHostMalloc(&g.h_cl_totals, 2 * sizeof(uint32_t)));
-    for (int k = 0; k < 2; k++)
-        if (!g.ev_cl[k]) VCRT_TRY(hipEventCreate(&g.ev_cl[k]));
-    p.boxes = g.d_cl_boxes;
-    p.spheres = g.d_cl_spheres;
-    p.counts = g.d_cl_counts;
+    VCRT_TRY(g.d_cl_boxes.reserve(nbox * vcrt::kCamListBox));
+    VCRT_TRY(g.d_cl_spheres.reserve(static_cast<size_t>(p.nspheres) * vcrt::kCamListBox));
+    VCRT_TRY(g.d_cl_counts.reserve(4 * static_cast<size_t>(p.n) + 2));
+    VCRT_TRY(g.h_cl_totals.reserve(2));
+    for (Event& e : g.ev_cl) VCRT_TRY(e.create());
+    p.boxes = g.d_cl_boxes.data();
+    p.spheres = g.d_cl_spheres.data();
+    p.counts = g.d_cl_counts.data();
     p.offsets = p.counts + 2 * static_cast<size_t>(p.n);
     p.totals = p.offsets + 2 * static_cast<size_t>(p.n);
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_info), &g.prim_info_cap,
-                  2 * static_cast<size_t>(p.n), sizeof(uint32_t)));
-    p.prim_info = g.d_prim_info;
-    VCRT_TRY(hipEventRecord(g.ev_cl[0], g.stream));
+    VCRT_TRY(g.d_prim_info.reserve(2 * static_cast<size_t>(p.n)));
+    p.prim_info = g.d_prim_info.data();
+    VCRT_TRY(hipEventRecord(g.ev_cl[0].get(), g.stream));
     const uint32_t quarter_blocks = (p.n + 255u) / 256u;
     VkResult r = launch(g.k_cl_prepare,
                         static_cast<uint32_t>(std::min<size_t>((nbox + p.nspheres + 255) / 256, 4096)),
@@ -1300,22 +1298,21 @@ VkResult build_camera_lists_device() {
     if (r != VK_SUCCESS) return r;
     if ((r = launch(g.k_cl_count, quarter_blocks, 256, 0, p)) != VK_SUCCESS) return r;
     if ((r = launch(g.k_cl_scan, 1, vcrt::kCamListScanThreads, 0, p)) != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(g.h_cl_totals, p.totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    uint32_t* totals = g.h_cl_totals.data();
+    VCRT_TRY(hipMemcpyAsync(totals, p.totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
                             g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
-    const size_t nids = g.h_cl_totals[0], npairs = g.h_cl_totals[1];
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_prim_ids), &g.prim_ids_cap, nids + 1,
-                  sizeof(uint16_t)));
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_cam_rec), &g.cam_rec_cap,
-                  static_cast<size_t>(p.nbig) * 16 + npairs * 12 + 12, sizeof(float)));
-    p.prim_ids = g.d_prim_ids;
-    p.cam_rec = reinterpret_cast<float*>(g.d_cam_rec);
+    const size_t nids = totals[0], npairs = totals[1];
+    VCRT_TRY(g.d_prim_ids.reserve(nids + 1));
+    VCRT_TRY(g.d_cam_rec.reserve(static_cast<size_t>(p.nbig) * 16 + npairs * 12 + 12));
+    p.prim_ids = g.d_prim_ids.data();
+    p.cam_rec = g.d_cam_rec.data();
     const uint32_t fill_threads = std::max(std::max(p.n, p.nbig), 12u);
     if ((r = launch(g.k_cl_fill, (fill_threads + 255u) / 256u, 256, 0, p)) != VK_SUCCESS) return r;
-    VCRT_TRY(hipEventRecord(g.ev_cl[1], g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_cl[1].get(), g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     float ms = 0.0f;
-    VCRT_TRY(hipEventElapsedTime(&ms, g.ev_cl[0], g.ev_cl[1]));
+    VCRT_TRY(hipEventElapsedTime(&ms, g.ev_cl[0].get(), g.ev_cl[1].get()));
     g.cam_stats.lists_ms = ms;
     g.prim_nids = nids;
     g.prim_npairs = npairs;
@@ -1413,9 +1410,8 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
     g.lds_per_cu = static_cast<uint32_t>(prop.maxSharedMemoryPerMultiProcessor);
     if ((r = to_vk(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking))) != VK_SUCCESS)
         return fail(r);
-    if ((r = to_vk(hipEventCreate(&g.ev_start))) != VK_SUCCESS) return fail(r);
-    if ((r = to_vk(hipEventCreate(&g.ev_stop))) != VK_SUCCESS) return fail(r);
-    if ((r = to_vk(hipEventCreate(&g.ev_resolve))) != VK_SUCCESS) return fail(r);
+    for (Event* e : {&g.ev_start, &g.ev_stop, &g.ev_resolve})
+        if ((r = to_vk(e->create())) != VK_SUCCESS) return fail(r);
     if ((r = load_code_object(g.desc.code_object_path)) != VK_SUCCESS) return fail(r);
     g.desc.code_object_path = nullptr;  // not owned
     if (lens_on() && !lens_kernels_bound()) return fail(VCRT_ERROR_FEATURE_NOT_PRESENT);
@@ -1429,28 +1425,23 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
                               [](double x) { return std::tan(x); });
     // Jitter (shader.comp:48) depends only on the sample index: one table per frame config.
     const int spp = g.desc.samples_per_pixel;
-    if ((r = to_vk(hipMalloc(&g.d_jitter_in, sizeof(float2) * spp))) != VK_SUCCESS) return fail(r);
+    // (the state is fresh, so every reserve here and below allocates exactly what it names)
+    if ((r = to_vk(g.d_jitter_in.reserve(spp))) != VK_SUCCESS) return fail(r);
     for (int k = 0; k < 2; k++) {
-        if ((r = to_vk(hipHostMalloc(&g.h_jitter[k], sizeof(float2) * spp))) != VK_SUCCESS)
-            return fail(r);
-        if ((r = to_vk(hipEventCreateWithFlags(&g.ev_jitter[k], hipEventDisableTiming))) !=
-            VK_SUCCESS)
+        if ((r = to_vk(g.h_jitter[k].reserve(spp))) != VK_SUCCESS) return fail(r);
+        if ((r = to_vk(g.ev_jitter[k].create(hipEventDisableTiming))) != VK_SUCCESS)
             return fail(r);
     }
-    if ((r = to_vk(hipMalloc(&g.d_jitter, sizeof(float4) * spp))) != VK_SUCCESS) return fail(r);
+    if ((r = to_vk(g.d_jitter.reserve(spp))) != VK_SUCCESS) return fail(r);
     if (lens_on()) {  // the lens origins, a table like the jitter's
         for (int k = 0; k < 2; k++)
-            if ((r = to_vk(hipHostMalloc(&g.h_lens[k], sizeof(float4) * spp))) != VK_SUCCESS)
-                return fail(r);
-        if ((r = to_vk(hipMalloc(&g.d_lens, sizeof(float4) * spp))) != VK_SUCCESS) return fail(r);
+            if ((r = to_vk(g.h_lens[k].reserve(spp))) != VK_SUCCESS) return fail(r);
+        if ((r = to_vk(g.d_lens.reserve(spp))) != VK_SUCCESS) return fail(r);
     }
     {
-        float th[255];
-        srgb_thresholds(th);
-        if ((r = to_vk(hipMalloc(&g.d_srgb_thresholds, sizeof(th)))) != VK_SUCCESS) return fail(r);
-        if ((r = to_vk(hipMemcpy(g.d_srgb_thresholds, th, sizeof(th), hipMemcpyHostToDevice))) !=
-            VK_SUCCESS)
-            return fail(r);
+        std::vector<float> th(255);
+        srgb_thresholds(th.data());
+        if ((r = to_vk(upload(g.d_srgb_thresholds, th))) != VK_SUCCESS) return fail(r);
     }
 
     // Frame sharding: 8x8 tiles, (tx, ty) to rank (tx + ty) % world (DESIGN.md "Multi-GPU").
@@ -1479,18 +1470,16 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
     const size_t own = g.desc.world_size == 1 ? g.fb_bytes
                                               : static_cast<size_t>(g.pad_tiles) * 64 * 16;
     if (own) {
-        if ((r = to_vk(hipMalloc(&g.d_fb_own, own))) != VK_SUCCESS) return fail(r);
-        if ((r = to_vk(hipMemsetAsync(g.d_fb_own, 0, own, g.stream))) != VK_SUCCESS)
+        if ((r = to_vk(g.d_fb_own.reserve(own / sizeof(float4)))) != VK_SUCCESS) return fail(r);
+        if ((r = to_vk(hipMemsetAsync(g.d_fb_own.data(), 0, own, g.stream))) != VK_SUCCESS)
             return fail(r);
     }
-    g.d_fb = g.d_fb_own;
+    g.d_fb = g.d_fb_own.data();
     // Work decomposition: (local tile, chunk of K samples) items holding whole quanta; a pixel's
     // quantum sums are combined exactly (vcrt_math.h "Accumulation"), at most kAccumMaxChunks.
     g.total_pixels = g.local_tiles * 64u;  // local element slots incl. partial-tile padding
     // the camera-ray tables: the jitter terms and the local slots' pixel corners
-    if (g.total_pixels &&
-        (r = to_vk(hipMalloc(&g.d_corner, sizeof(float4) * g.total_pixels))) != VK_SUCCESS)
-        return fail(r);
+    if ((r = to_vk(g.d_corner.reserve(g.total_pixels))) != VK_SUCCESS) return fail(r);
     if ((r = setup_jitter(0, g.total_pixels != 0)) != VK_SUCCESS) return fail(r);
     g.quantum = work_quantum(g.desc);
     if ((spp + g.quantum - 1) / g.quantum > vcrt::kAccumMaxChunks)
@@ -1517,18 +1506,17 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
     }
     if (!g.direct && g.total_pixels) {  // 32 B per pixel, whatever the spp
         const size_t bytes = 32u * static_cast<size_t>(g.total_pixels);
-        if ((r = to_vk(hipMalloc(&g.d_accum, bytes))) != VK_SUCCESS) return fail(r);
-        if ((r = to_vk(hipMemsetAsync(g.d_accum, 0, bytes, g.stream))) != VK_SUCCESS)
+        if ((r = to_vk(g.d_accum.reserve(bytes / sizeof(double)))) != VK_SUCCESS) return fail(r);
+        if ((r = to_vk(hipMemsetAsync(g.d_accum.data(), 0, bytes, g.stream))) != VK_SUCCESS)
             return fail(r);
         g.accum_clean = true;
         const size_t eb = sizeof(uint32_t) * static_cast<size_t>(g.total_pixels);
-        if ((r = to_vk(hipMalloc(&g.d_pixel_emax, eb))) != VK_SUCCESS) return fail(r);
-        if ((r = to_vk(hipMemsetAsync(g.d_pixel_emax, 0, eb, g.stream))) != VK_SUCCESS)
+        if ((r = to_vk(g.d_pixel_emax.reserve(g.total_pixels))) != VK_SUCCESS) return fail(r);
+        if ((r = to_vk(hipMemsetAsync(g.d_pixel_emax.data(), 0, eb, g.stream))) != VK_SUCCESS)
             return fail(r);
     }
-    if ((r = to_vk(hipMalloc(&g.d_counters, kCounterBytes))) != VK_SUCCESS) return fail(r);
-    if ((r = to_vk(hipHostMalloc(&g.h_counters, 4 * sizeof(unsigned long long)))) != VK_SUCCESS)
-        return fail(r);
+    if ((r = to_vk(g.d_counters.reserve(kCounterBytes / 8))) != VK_SUCCESS) return fail(r);
+    if ((r = to_vk(g.h_counters.reserve(4))) != VK_SUCCESS) return fail(r);
     if (const char* e = std::getenv("VCRT_DEBUG_STATS")) g.debug_stats = std::atoi(e);
     if (const char* e = std::getenv("VCRT_PRIMARY_LISTS")) g.primary_lists = std::atoi(e) != 0;
     if (const char* e = std::getenv("VCRT_FEATURE_LISTS")) g.feature_lists = std::atoi(e) != 0;
@@ -1570,7 +1558,9 @@ vcrt_result vcrt_begin(const vcrt_render_desc* desc) {
             g.ring_max = std::min<uint32_t>(static_cast<uint32_t>(std::atoi(e)),
                                             vcrt::kRingMaxEntries);
     }
-    if (g.debug_stats && (r = to_vk(hipMalloc(&g.d_debug, sizeof(g.stats.debug)))) != VK_SUCCESS)
+    if (g.debug_stats &&
+        (r = to_vk(g.d_debug.reserve(sizeof(g.stats.debug) / sizeof(g.stats.debug[0])))) !=
+            VK_SUCCESS)
         return fail(r);
 
     // The reference's world[] is compiled in; default to the same final scene.
@@ -1602,22 +1592,13 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
     (void)hipStreamSynchronize(g.stream);
     free_scene();
     if (ct.ngroups > 0) {
-        const std::vector<float> rec = group_records(ct);
-        VCRT_TRY(hipMalloc(&g.d_cgroup, sizeof(float) * rec.size()));
-        VCRT_TRY(hipMalloc(&g.d_cbound, sizeof(float) * ct.bound.size()));
-        VCRT_TRY(hipMalloc(&g.d_cnode, sizeof(float) * ct.node.size()));
-        VCRT_TRY(hipMalloc(&g.d_ctop, sizeof(float) * ct.top.size()));
-        VCRT_TRY(hipMemcpy(g.d_ctop, ct.top.data(), sizeof(float) * ct.top.size(),
-                           hipMemcpyHostToDevice));
-        VCRT_TRY(hipMemcpy(g.d_cgroup, rec.data(), sizeof(float) * rec.size(),
-                           hipMemcpyHostToDevice));
-        VCRT_TRY(hipMemcpy(g.d_cbound, ct.bound.data(), sizeof(float) * ct.bound.size(),
-                           hipMemcpyHostToDevice));
+        VCRT_TRY(upload(g.d_cgroup, group_records(ct)));
+        VCRT_TRY(upload(g.d_cbound, ct.bound));
+        VCRT_TRY(upload(g.d_cnode, ct.node));
+        VCRT_TRY(upload(g.d_ctop, ct.top));
         // near/far layout of the group boxes for the flat scan (vcrt_kernel_abi.h, cbound_nf)
-        VCRT_TRY(upload_near_far(near_far(ct.bound), &g.d_cbound_nf));
-        VCRT_TRY(upload_near_far(node_near_far(ct), &g.d_cnode_nf));
-        VCRT_TRY(hipMemcpy(g.d_cnode, ct.node.data(), sizeof(float) * ct.node.size(),
-                           hipMemcpyHostToDevice));
+        VCRT_TRY(upload(g.d_cbound_nf, near_far(ct.bound)));
+        VCRT_TRY(upload(g.d_cnode_nf, node_near_far(ct)));
         g.ncgroups = ct.ngroups;
         g.ncbig = ct.nbig;
         std::memcpy(g.cmargin, ct.margin, sizeof(ct.margin));
@@ -1626,10 +1607,7 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
         g.cslab[1] = ct.slab_lohi[1];
         {
             // footprint tables: 16-bit masks up to 16 nodes, as the kernel's LDS image holds them
-            const std::vector<uint32_t> packed = pack_footprint(ct);
-            VCRT_TRY(hipMalloc(&g.d_fp_tab, sizeof(uint32_t) * packed.size()));
-            VCRT_TRY(hipMemcpy(g.d_fp_tab, packed.data(), sizeof(uint32_t) * packed.size(),
-                               hipMemcpyHostToDevice));
+            VCRT_TRY(upload(g.d_fp_tab, pack_footprint(ct)));
             std::memcpy(g.cfp_x, ct.fp_x, sizeof(g.cfp_x));
             std::memcpy(g.cfp_z, ct.fp_z, sizeof(g.cfp_z));
             std::memcpy(g.cfp_y, ct.fp_y, sizeof(g.cfp_y));
@@ -1652,9 +1630,10 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
                                          vcrt::group_foot_zero_pad(ct.ngroups)) +
                                       vcrt::foot_lds_bytes(ct.ngroups))
                 return VCRT_ERROR_INITIALIZATION_FAILED;
-            VCRT_TRY(hipMalloc(&g.d_gf_tab, tab_bytes + 16u));
-            VCRT_TRY(hipMemcpy(g.d_gf_tab, ct.gf_tab.data(), tab_bytes, hipMemcpyHostToDevice));
-            VCRT_TRY(hipMemset(reinterpret_cast<char*>(g.d_gf_tab) + tab_bytes, 0, 16u));
+            VCRT_TRY(g.d_gf_tab.reserve(tab_bytes / sizeof(uint4) + 1));
+            VCRT_TRY(hipMemcpy(g.d_gf_tab.data(), ct.gf_tab.data(), tab_bytes,
+                               hipMemcpyHostToDevice));
+            VCRT_TRY(hipMemset(reinterpret_cast<char*>(g.d_gf_tab.data()) + tab_bytes, 0, 16u));
             std::memcpy(g.cgf_x, ct.gf_x, sizeof(g.cgf_x));
             std::memcpy(g.cgf_z, ct.gf_z, sizeof(g.cgf_z));
             std::memcpy(g.cgf_always, ct.gf_always, sizeof(g.cgf_always));
@@ -1677,19 +1656,11 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
             if (ru != VK_SUCCESS) return ru;
         }
     }
-    VCRT_TRY(hipMalloc(&g.d_geom, sizeof(float) * table.size()));
-    VCRT_TRY(hipMemcpy(g.d_geom, table.data(), sizeof(float) * table.size(),
-                       hipMemcpyHostToDevice));
+    VCRT_TRY(upload(g.d_geom, table));
     if (count > 0) {
-        VCRT_TRY(hipMalloc(&g.d_center_radius, sizeof(float4) * count));
-        VCRT_TRY(hipMalloc(&g.d_shade, sizeof(float4) * count));
-        VCRT_TRY(hipMalloc(&g.d_material, sizeof(float4) * count));
-        VCRT_TRY(hipMemcpy(g.d_center_radius, cr.data(), sizeof(float4) * count,
-                           hipMemcpyHostToDevice));
-        VCRT_TRY(
-            hipMemcpy(g.d_shade, shade.data(), sizeof(float4) * count, hipMemcpyHostToDevice));
-        VCRT_TRY(
-            hipMemcpy(g.d_material, mat.data(), sizeof(float4) * count, hipMemcpyHostToDevice));
+        VCRT_TRY(upload(g.d_center_radius, cr));
+        VCRT_TRY(upload(g.d_shade, shade));
+        VCRT_TRY(upload(g.d_material, mat));
     }
     // (the uploads above ran on the null stream; the render stream does not wait for it)
     VCRT_TRY(hipStreamSynchronize(nullptr));
@@ -1707,15 +1678,8 @@ vcrt_result vcrt_set_scene(const vcrt_sphere* spheres, int32_t count) {
     g.accumulated = 0;
     g.order_key = 0;    // and its cost order is measured again
     VCRT_TRY(reset_sums());
-    g.scene_bounded = true;
-    g.radii_safe = true;
-    for (int32_t i = 0; i < count; i++) {
-        const vcrt_sphere& sp = spheres[i];
-        for (float v : {sp.center[0], sp.center[1], sp.center[2], sp.radius})
-            if (!(std::fabs(v) <= 0x1p30f)) g.scene_bounded = false;  // also rejects NaN
-        if (!(std::fabs(sp.radius) >= 0x1p-40f && std::fabs(sp.radius) <= 0x1p30f))
-            g.radii_safe = false;
-    }
+    g.scene_bounded = values_bounded(spheres, count);
+    g.radii_safe = values_radii_safe(spheres, count);
     g.stage.pName = select_kernel().name;  // the entry point draws of this scene dispatch
     return VCRT_SUCCESS;
 }
@@ -1749,7 +1713,7 @@ uint64_t order_key_of(hipFunction_t f, uint32_t grid, uint32_t total_blocks) {
 // item; ties in the static order (head, then tail, each bottom-up: the highest block first).
 VkResult build_block_order(uint32_t total_blocks) {
     std::vector<uint32_t> cost(g.total_pixels);
-    VCRT_TRY(hipMemcpy(cost.data(), g.d_pixel_cost, cost.size() * sizeof(uint32_t),
+    VCRT_TRY(hipMemcpy(cost.data(), g.d_pixel_cost.data(), cost.size() * sizeof(uint32_t),
                        hipMemcpyDeviceToHost));
     std::vector<uint32_t> order(total_blocks);
     std::vector<uint64_t> bc(total_blocks, 0);
@@ -1777,14 +1741,8 @@ VkResult build_block_order(uint32_t total_blocks) {
     for (uint32_t b = total_blocks; b-- > head;) order[k++] = b;
     std::stable_sort(order.begin(), order.end(),
                      [&bc](uint32_t x, uint32_t y) { return bc[x] > bc[y]; });
-    if (total_blocks > g.order_words) {
-        if (g.d_block_order) (void)hipFree(g.d_block_order);
-        g.d_block_order = nullptr;
-        g.order_words = 0;
-        VCRT_TRY(hipMalloc(&g.d_block_order, total_blocks * sizeof(uint32_t)));
-        g.order_words = total_blocks;
-    }
-    VCRT_TRY(hipMemcpy(g.d_block_order, order.data(), total_blocks * sizeof(uint32_t),
+    VCRT_TRY(g.d_block_order.reserve(total_blocks));
+    VCRT_TRY(hipMemcpy(g.d_block_order.data(), order.data(), total_blocks * sizeof(uint32_t),
                        hipMemcpyHostToDevice));
     VCRT_TRY(hipStreamSynchronize(nullptr));  // before the render stream's next frame reads it
     return VK_SUCCESS;
@@ -1797,22 +1755,22 @@ VkResult build_block_order(uint32_t total_blocks) {
 // The scene's part of a kernel's argument block: the scan tables, the shading rows, the margins
 // and the flags' scene bits (frames and ray queries).
 static void scene_params(vcrt::TraceParams& p) {
-    p.geom = g.d_geom;
-    p.center_radius = g.d_center_radius;
-    p.shade = g.d_shade;
-    p.material = g.d_material;
-    p.cgroup = g.d_cgroup;
-    p.cbound = g.d_cbound;
-    p.cbound_nf = g.d_cbound_nf;
-    p.cnode = g.d_cnode;
-    p.cnode_nf = g.d_cnode_nf;
-    p.ctop = g.d_ctop;
+    p.geom = g.d_geom.data();
+    p.center_radius = g.d_center_radius.data();
+    p.shade = g.d_shade.data();
+    p.material = g.d_material.data();
+    p.cgroup = g.d_cgroup.data();
+    p.cbound = g.d_cbound.data();
+    p.cbound_nf = g.d_cbound_nf.data();
+    p.cnode = g.d_cnode.data();
+    p.cnode_nf = g.d_cnode_nf.data();
+    p.ctop = g.d_ctop.data();
     p.ncgroups = g.ncgroups;
     p.nbig = g.ncbig;
     for (int k = 0; k < 4; k++) p.box_margin[k] = g.cmargin[k];
     p.slab[0] = g.cslab[0];
     p.slab[1] = g.cslab[1];
-    p.fp_tab = g.d_fp_tab;
+    p.fp_tab = g.d_fp_tab.data();
     for (int k = 0; k < 2; k++) {
         p.fp_x[k] = g.cfp_x[k];
         p.fp_z[k] = g.cfp_z[k];
@@ -1820,7 +1778,7 @@ static void scene_params(vcrt::TraceParams& p) {
     }
     p.fp_k2 = g.cfp_k2;
     p.fp_always = g.cfp_always;
-    p.gf_tab = g.d_gf_tab;
+    p.gf_tab = g.d_gf_tab.data();
     for (int k = 0; k < 2; k++) {
         p.gf_x[k] = g.cgf_x[k];
         p.gf_z[k] = g.cgf_z[k];
@@ -1839,18 +1797,19 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     const uint32_t pixels = g.total_pixels;
     vcrt::TraceParams p{};
     scene_params(p);
-    p.jitter = g.d_jitter;
-    p.lens = g.d_lens;
-    p.corner = g.d_corner;
+    p.jitter = g.d_jitter.data();
+    p.lens = g.d_lens.data();
+    p.corner = g.d_corner.data();
     p.out = g.d_fb;
-    p.accum = g.d_accum;
-    p.work = reinterpret_cast<uint32_t*>(static_cast<char*>(g.d_counters) + 256);
-    p.segments = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_counters) + 8);
-    p.debug = static_cast<unsigned long long*>(g.d_debug);
-    p.work_done = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_counters) + 16);
-    p.prim_info = g.d_prim_info;
-    p.prim_ids = g.d_prim_ids;
-    p.cam_rec = g.d_cam_rec;
+    p.accum = g.d_accum.data();
+    unsigned long long* const counters64 = g.d_counters.data();  // (the layout: kCounterBytes)
+    p.work = reinterpret_cast<uint32_t*>(counters64 + 256 / 8);
+    p.segments = counters64 + 1;
+    p.debug = g.d_debug.data();
+    p.work_done = counters64 + 2;
+    p.prim_info = g.d_prim_info.data();
+    p.prim_ids = g.d_prim_ids.data();
+    p.cam_rec = reinterpret_cast<const float4*>(g.d_cam_rec.data());
     p.width = g.desc.width;
     p.height = g.desc.height;
     p.spp = g.desc.samples_per_pixel;
@@ -1874,12 +1833,12 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     // the group-level footprint (fact (5g)) takes the node level's place when the scene allows
     // it (CullTables::gf_ok) and the camera rays have their lists: without them camera rays
     // cross the scan on long grazing stretches, where a rectangle is loose
-    if (g.cgf_ok && g.d_gf_tab != nullptr && g.d_prim_info != nullptr)
+    if (g.cgf_ok && g.d_gf_tab.data() != nullptr && g.d_prim_info.data() != nullptr)
         p.flags |= vcrt::kFlagGroupFoot;
     // outlier quanta (vcrt_math.h "Accumulation"); the kernel's quantizing retire writes them
-    p.pixel_emax = g.d_pixel_emax;
-    p.outlier_max = static_cast<uint32_t*>(g.d_counters);  // u32 at 0 (zeroed every launch)
-    if (!g.direct && (p.pixel_emax == nullptr || g.d_accum == nullptr))
+    p.pixel_emax = g.d_pixel_emax.data();
+    p.outlier_max = reinterpret_cast<uint32_t*>(counters64);  // u32 at 0 (zeroed every launch)
+    if (!g.direct && (p.pixel_emax == nullptr || g.d_accum.data() == nullptr))
         return VK_ERROR_INITIALIZATION_FAILED;
     p.spp_total = static_cast<float>(spp_total);
     p.region = nullptr;
@@ -1887,15 +1846,9 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.nch_magic[1] = g.nch_magic[1];
     const std::array<float, 12> cam = camera_array();
     for (int i = 0; i < 12; i++) p.cam[i] = cam[i];
-    // The camera phase of the flat scans traces a fresh camera ray from its quarter's list when
-    // the ray is in the guarded range. Its origin is the camera centre, a frame constant, so that
-    // half of the guard (every |component| <= 2^30, in a bounded scene; also rejects NaN) is
-    // decided here: a frame that fails it gets no lists, and its camera rays take the main scan,
-    // which tests their origin itself. (The group footprint keeps to the lists the scene has:
-    // such a frame's camera rays never reach a culled scan.)
-    if (!(g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
-          std::fabs(cam[11]) <= 0x1p30f))
-        p.prim_info = nullptr;
+    // (The group footprint keeps to the lists the scene has: a frame without them sends no
+    // camera ray to a culled scan.)
+    if (!lists_allowed(cam)) p.prim_info = nullptr;
     const KernelChoice kc = select_kernel();
     hipFunction_t f = g.debug_stats == 1 ? kc.stats : kc.f;
     if (f == nullptr) return VK_ERROR_FEATURE_NOT_PRESENT;  // (a lens, no lens kernels loaded)
@@ -2011,51 +1964,39 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.pixel_cost = nullptr;
     p.block_order = nullptr;
     if (cost_mode && key == g.order_key) {
-        p.block_order = g.d_block_order;
+        p.block_order = g.d_block_order.data();
         p.flags &= ~vcrt::kFlagReverseOrder;  // the order is the whole hand-out sequence
     } else if (cost_mode) {
-        if (pixels > g.cost_words) {
-            if (g.d_pixel_cost) (void)hipFree(g.d_pixel_cost);
-            g.d_pixel_cost = nullptr;
-            g.cost_words = 0;
-            VCRT_TRY(hipMalloc(&g.d_pixel_cost, pixels * sizeof(uint32_t)));
-            g.cost_words = pixels;
-        }
-        VCRT_TRY(hipMemsetAsync(g.d_pixel_cost, 0, pixels * sizeof(uint32_t), g.stream));
-        p.pixel_cost = g.d_pixel_cost;
+        VCRT_TRY(g.d_pixel_cost.reserve(pixels));
+        VCRT_TRY(hipMemsetAsync(g.d_pixel_cost.data(), 0, pixels * sizeof(uint32_t), g.stream));
+        p.pixel_cost = g.d_pixel_cost.data();
         measure = true;
     }
     g.stats.cost_order = p.block_order != nullptr ? 1 : 0;
-    if (!g.counters_clean) VCRT_TRY(hipMemsetAsync(g.d_counters, 0, kCounterBytes, g.stream));
+    if (!g.counters_clean) VCRT_TRY(hipMemsetAsync(counters64, 0, kCounterBytes, g.stream));
     g.counters_clean = false;  // until this frame's resolve has read and zeroed them
     if (g.debug_stats == 1) {  // the stats kernels' region counters, one row per wave
         const size_t words = static_cast<size_t>(grid) * (block / 64u) * kRegionCount;
-        if (words > g.region_words) {
-            if (g.d_region) (void)hipFree(g.d_region);
-            g.d_region = nullptr;
-            g.region_words = 0;
-            VCRT_TRY(hipMalloc(&g.d_region, words * sizeof(uint32_t)));
-            g.region_words = words;
-        }
-        VCRT_TRY(hipMemsetAsync(g.d_region, 0, words * sizeof(uint32_t), g.stream));
-        p.region = g.d_region;
+        VCRT_TRY(g.d_region.reserve(words));
+        VCRT_TRY(hipMemsetAsync(g.d_region.data(), 0, words * sizeof(uint32_t), g.stream));
+        p.region = g.d_region.data();
     }
     if (!g.direct && !g.desc.progressive && !g.accum_clean)  // every frame sums from zero
-        VCRT_TRY(hipMemsetAsync(g.d_accum, 0, 32u * static_cast<size_t>(pixels), g.stream));
+        VCRT_TRY(hipMemsetAsync(g.d_accum.data(), 0, 32u * static_cast<size_t>(pixels), g.stream));
     if (!g.direct) g.accum_clean = false;  // until this frame's resolve zeroes it
     if (g.debug_stats) {
         unsigned long long init[128] = {0, 0, 0, 0, 0, ~0ull};
         if (g.debug_stats == 2) init[9] = init[10] = ~0ull;  // wave times: minima
-        VCRT_TRY(hipMemcpyAsync(g.d_debug, init, sizeof(init), hipMemcpyHostToDevice,
+        VCRT_TRY(hipMemcpyAsync(g.d_debug.data(), init, sizeof(init), hipMemcpyHostToDevice,
                                 g.stream));
     }
-    VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_start.get(), g.stream));
     VkResult r = launch(f, grid, block, lds_launch, p);
     if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_stop.get(), g.stream));
     bool resolved = false;
     if (!g.direct) {
-        vcrt::ResolveParams rp{g.d_accum,
+        vcrt::ResolveParams rp{g.d_accum.data(),
                                g.d_fb,
                                std::ldexp(1.0, -g.accum_log2),
                                static_cast<float>(spp_total),
@@ -2066,28 +2007,28 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
                                g.tiles_x,
                                g.local_tiles,
                                g.desc.progressive ? 0u : 1u,
-                               g.pixel_scale ? g.d_pixel_emax : nullptr,
-                               static_cast<unsigned long long*>(g.d_counters),
-                               g.h_counters,
+                               g.pixel_scale ? g.d_pixel_emax.data() : nullptr,
+                               counters64,
+                               g.h_counters.data(),
                                static_cast<uint32_t>(kCounterBytes / 4)};
         const uint32_t rgrid = std::min<uint32_t>((pixels + 255) / 256, 8192);
         r = launch(g.k_resolve, rgrid, 256, 0, rp);
         if (r != VK_SUCCESS) return r;
         resolved = true;
         g.accum_clean = !g.desc.progressive;
-        VCRT_TRY(hipEventRecord(g.ev_resolve, g.stream));
+        VCRT_TRY(hipEventRecord(g.ev_resolve.get(), g.stream));
     }
     if (!resolved)  // (one quantum per pixel: no resolve pass)
-        VCRT_TRY(hipMemcpyAsync(g.h_counters, g.d_counters, 4 * sizeof(unsigned long long),
+        VCRT_TRY(hipMemcpyAsync(g.h_counters.data(), counters64, 4 * sizeof(unsigned long long),
                                 hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     g.counters_clean = resolved;
-    const unsigned long long* counters = g.h_counters;
+    const unsigned long long* counters = g.h_counters.data();
     float ms = 0.f;
-    VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
+    VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start.get(), g.ev_stop.get()));
     g.stats.kernel_ms = ms;
     if (!g.direct) {
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_stop, g.ev_resolve));
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_stop.get(), g.ev_resolve.get()));
         g.stats.resolve_ms = ms;
     }
     g.stats.segments = counters[1];
@@ -2099,12 +2040,12 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
         g.order_key = key;
     }
     if (g.debug_stats)
-        VCRT_TRY(hipMemcpy(g.stats.debug, g.d_debug, sizeof(g.stats.debug),
+        VCRT_TRY(hipMemcpy(g.stats.debug, g.d_debug.data(), sizeof(g.stats.debug),
                            hipMemcpyDeviceToHost));
     if (g.debug_stats == 1 && p.region) {  // region counters summed over the waves
         const size_t words = static_cast<size_t>(grid) * (block / 64u) * kRegionCount;
         std::vector<uint32_t> rows(words);
-        VCRT_TRY(hipMemcpy(rows.data(), g.d_region, words * sizeof(uint32_t),
+        VCRT_TRY(hipMemcpy(rows.data(), g.d_region.data(), words * sizeof(uint32_t),
                            hipMemcpyDeviceToHost));
         for (size_t w = 0; w < words / kRegionCount; w++)
             for (uint32_t k = 0; k < kRegionCount; k++)
@@ -2143,7 +2084,7 @@ static VkResult rerender_scaled(uint64_t spp_total, uint32_t outlier_max) {
             if (r != VK_SUCCESS) return r;
             continue;
         }
-        VCRT_TRY(hipMemsetAsync(g.d_accum, 0, 32u * static_cast<size_t>(g.total_pixels),
+        VCRT_TRY(hipMemsetAsync(g.d_accum.data(), 0, 32u * static_cast<size_t>(g.total_pixels),
                                 g.stream));
         for (uint64_t f = 0; f * spp < spp_total; f++) {
             VkResult r = setup_jitter(f * spp);
@@ -2202,7 +2143,7 @@ vcrt_result vcrt_draw_next_frame(void) {
         if (r == VK_SUCCESS) r = wait_gather();
         if (r != VK_SUCCESS) return r;
         float ms = 0.f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_gather_start, g.ev_gather));
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_gather_start.get(), g.ev_gather.get()));
         g.stats.gather_ms = ms;
     }
     VCRT_TRY(hipStreamSynchronize(g.stream));
@@ -2222,66 +2163,11 @@ vcrt_result vcrt_draw_next_frame(void) {
 vcrt_result vcrt_end(void) {
     if (!g.begun) return VCRT_SUCCESS;  // idempotent
     if (g.stream) (void)hipStreamSynchronize(g.stream);
-    free_scene();
-    if (g.d_jitter) (void)hipFree(g.d_jitter);
-    if (g.d_jitter_in) (void)hipFree(g.d_jitter_in);
-    for (int k = 0; k < 2; k++) {
-        if (g.h_jitter[k]) (void)hipHostFree(g.h_jitter[k]);
-        if (g.h_lens[k]) (void)hipHostFree(g.h_lens[k]);
-        if (g.ev_jitter[k]) (void)hipEventDestroy(g.ev_jitter[k]);
-    }
-    if (g.d_lens) (void)hipFree(g.d_lens);
-    if (g.d_corner) (void)hipFree(g.d_corner);
-    if (g.d_fb_own) (void)hipFree(g.d_fb_own);
-    if (g.d_counters) (void)hipFree(g.d_counters);
-    if (g.h_counters) (void)hipHostFree(g.h_counters);
-    if (g.d_debug) (void)hipFree(g.d_debug);
-    if (g.d_region) (void)hipFree(g.d_region);
-    if (g.d_pixel_cost) (void)hipFree(g.d_pixel_cost);
-    if (g.d_block_order) (void)hipFree(g.d_block_order);
-    if (g.d_rq_rays) (void)hipFree(g.d_rq_rays);
-    if (g.d_rq_radiance) (void)hipFree(g.d_rq_radiance);
-    if (g.d_rq_hits) (void)hipFree(g.d_rq_hits);
-    if (g.d_rq_counters) (void)hipFree(g.d_rq_counters);
-    if (g.d_oq_tmax) (void)hipFree(g.d_oq_tmax);
-    if (g.d_oq_occluded) (void)hipFree(g.d_oq_occluded);
-    if (g.d_ft_jitter_in) (void)hipFree(g.d_ft_jitter_in);
-    if (g.d_ft_jitter) (void)hipFree(g.d_ft_jitter);
-    if (g.d_ft_lens) (void)hipFree(g.d_ft_lens);
-    if (g.d_ft_albedo) (void)hipFree(g.d_ft_albedo);
-    if (g.d_ft_normal_depth) (void)hipFree(g.d_ft_normal_depth);
-    if (g.d_ft_sphere) (void)hipFree(g.d_ft_sphere);
-    if (g.d_ft_counters) (void)hipFree(g.d_ft_counters);
-    if (g.d_ao_dirs) (void)hipFree(g.d_ao_dirs);
-    if (g.d_ao_plane) (void)hipFree(g.d_ao_plane);
-    for (float4* b : g.d_dn_scratch)
-        if (b) (void)hipFree(b);
-    for (float4* b : g.d_dn_stage)
-        if (b) (void)hipFree(b);
-    for (hipEvent_t e : g.ev_dn)
-        if (e) (void)hipEventDestroy(e);
-    if (g.d_cl_boxes) (void)hipFree(g.d_cl_boxes);
-    if (g.d_cl_spheres) (void)hipFree(g.d_cl_spheres);
-    if (g.d_cl_counts) (void)hipFree(g.d_cl_counts);
-    if (g.h_cl_totals) (void)hipHostFree(g.h_cl_totals);
-    for (int k = 0; k < 2; k++)
-        if (g.ev_cl[k]) (void)hipEventDestroy(g.ev_cl[k]);
-    if (g.d_su_spheres) (void)hipFree(g.d_su_spheres);
-    if (g.d_su_summary) (void)hipFree(g.d_su_summary);
-    if (g.h_su_summary) (void)hipHostFree(g.h_su_summary);
-    for (int k = 0; k < 2; k++)
-        if (g.ev_su[k]) (void)hipEventDestroy(g.ev_su[k]);
-    DestroyShaderStage(&g.stage);
-    if (g.ev_start) (void)hipEventDestroy(g.ev_start);
-    if (g.ev_stop) (void)hipEventDestroy(g.ev_stop);
-    if (g.ev_resolve) (void)hipEventDestroy(g.ev_resolve);
-    if (g.d_accum) (void)hipFree(g.d_accum);
-    if (g.d_pixel_emax) (void)hipFree(g.d_pixel_emax);
-    if (g.d_srgb_thresholds) (void)hipFree(g.d_srgb_thresholds);
-    if (g.d_srgb) (void)hipFree(g.d_srgb);
     comm_release(false);
-    if (g.stream) (void)hipStreamDestroy(g.stream);
-    g = RendererState{};
+    DestroyShaderStage(&g.stage);
+    const hipStream_t stream = g.stream;
+    g = RendererState{};  // every buffer and event is released here (device_resources.hpp)
+    if (stream) (void)hipStreamDestroy(stream);
     return VCRT_SUCCESS;
 }
 
@@ -2290,7 +2176,7 @@ vcrt_result vcrt_end(void) {
 namespace {
 
 constexpr uint32_t kRayQueryMax = 1u << 30;
-constexpr size_t kRayCounterBytes = 32;  // u32 work index at 0, u64 tallies at 8, 16, 24
+constexpr size_t kRayCounterWords = 4;  // u64: the u32 work index in [0], tallies in [1..3]
 
 // The arguments every form of the call checks, in the order of the header's table.
 vcrt_result ray_query_args(const float* origins, const float* dirs, uint32_t count,
@@ -2326,7 +2212,6 @@ VkResult ray_query_device(const float* origins, const float* dirs, uint32_t coun
         std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_trace_rays");
     }
     if (count == 0) return VK_SUCCESS;
-    if (!g.d_rq_counters) VCRT_TRY(hipMalloc(&g.d_rq_counters, kRayCounterBytes));
     vcrt::RayQueryParams p{};
     scene_params(p.scene);
     p.scene.max_depth = max_depth;
@@ -2335,22 +2220,18 @@ VkResult ray_query_device(const float* origins, const float* dirs, uint32_t coun
     p.radiance = reinterpret_cast<float4*>(radiance);
     p.hits = reinterpret_cast<uint4*>(hits);
     p.count = count;
-    p.work = static_cast<uint32_t*>(g.d_rq_counters);
-    p.tallies = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_rq_counters) + 8);
-    const uint32_t grid = query_grid(g.k_trace_rays, count);
-    VCRT_TRY(hipMemsetAsync(g.d_rq_counters, 0, kRayCounterBytes, g.stream));
-    VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
-    const VkResult r = launch(g.k_trace_rays, grid, kQueryBlock, 0, p);
+    unsigned long long counters[kRayCounterWords] = {};
+    float ms = 0.f;
+    const VkResult r = timed_launch(
+        g.k_trace_rays, query_grid(g.k_trace_rays, count), kQueryBlock, p, g.d_rq_counters,
+        kRayCounterWords,
+        [&p](unsigned long long* c) {
+            p.work = reinterpret_cast<uint32_t*>(c);
+            p.tallies = c + 1;
+        },
+        stats ? counters : nullptr, &ms);
     if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
-    unsigned long long counters[4] = {0, 0, 0, 0};
-    if (stats)
-        VCRT_TRY(hipMemcpyAsync(counters, g.d_rq_counters, kRayCounterBytes,
-                                hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) {
-        float ms = 0.f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
         stats->kernel_ms = ms;
         stats->segments = counters[1];
         stats->group_tests = counters[2];
@@ -2379,25 +2260,25 @@ vcrt_result vcrt_trace_rays(const float* origins, const float* dirs, uint32_t co
     const vcrt_result a = ray_query_args(origins, dirs, count, max_depth, radiance, hits);
     if (a != VCRT_SUCCESS) return a;
     const size_t n = count, in_bytes = 3 * sizeof(float) * n;
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_rays), &g.rq_rays_cap, n, 6 * sizeof(float)));
-    if (radiance) VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_radiance), &g.rq_radiance_cap, n, sizeof(float4)));
-    if (hits) VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_hits), &g.rq_hits_cap, n, sizeof(vcrt_ray_hit)));
-    float* d_origins = g.d_rq_rays;
-    float* d_dirs = g.d_rq_rays + 3 * n;
+    VCRT_TRY(g.d_rq_rays.reserve(6 * n));
+    if (radiance) VCRT_TRY(g.d_rq_radiance.reserve(n));
+    if (hits) VCRT_TRY(g.d_rq_hits.reserve(n));
+    float* d_origins = g.d_rq_rays.data();
+    float* d_dirs = g.d_rq_rays.data() + 3 * n;
     if (n) {
         VCRT_TRY(hipMemcpyAsync(d_origins, origins, in_bytes, hipMemcpyHostToDevice, g.stream));
         VCRT_TRY(hipMemcpyAsync(d_dirs, dirs, in_bytes, hipMemcpyHostToDevice, g.stream));
     }
     const VkResult r = ray_query_device(
         d_origins, d_dirs, count, max_depth,
-        radiance ? reinterpret_cast<float*>(g.d_rq_radiance) : nullptr,
-        hits ? reinterpret_cast<vcrt_ray_hit*>(g.d_rq_hits) : nullptr, stats);
+        radiance ? reinterpret_cast<float*>(g.d_rq_radiance.data()) : nullptr,
+        hits ? g.d_rq_hits.data() : nullptr, stats);
     if (r != VK_SUCCESS || n == 0) return r;
     if (radiance)
-        VCRT_TRY(hipMemcpyAsync(radiance, g.d_rq_radiance, sizeof(float4) * n,
+        VCRT_TRY(hipMemcpyAsync(radiance, g.d_rq_radiance.data(), sizeof(float4) * n,
                                 hipMemcpyDeviceToHost, g.stream));
     if (hits)
-        VCRT_TRY(hipMemcpyAsync(hits, g.d_rq_hits, sizeof(vcrt_ray_hit) * n,
+        VCRT_TRY(hipMemcpyAsync(hits, g.d_rq_hits.data(), sizeof(vcrt_ray_hit) * n,
                                 hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     return VCRT_SUCCESS;
@@ -2426,7 +2307,6 @@ VkResult occlusion_device(const float* origins, const float* dirs, const float* 
         std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_occlude_rays");
     }
     if (count == 0) return VK_SUCCESS;
-    if (!g.d_rq_counters) VCRT_TRY(hipMalloc(&g.d_rq_counters, kRayCounterBytes));
     vcrt::OcclusionParams p{};
     scene_params(p.scene);
     p.origins = origins;
@@ -2434,21 +2314,14 @@ VkResult occlusion_device(const float* origins, const float* dirs, const float* 
     p.tmax = tmax;
     p.occluded = occluded;
     p.count = count;
-    p.tallies = reinterpret_cast<unsigned long long*>(static_cast<char*>(g.d_rq_counters) + 8);
-    const uint32_t grid = query_grid(g.k_occlude_rays, count);
-    VCRT_TRY(hipMemsetAsync(g.d_rq_counters, 0, kRayCounterBytes, g.stream));
-    VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
-    const VkResult r = launch(g.k_occlude_rays, grid, kQueryBlock, 0, p);
+    unsigned long long counters[kRayCounterWords] = {};
+    float ms = 0.f;
+    const VkResult r = timed_launch(
+        g.k_occlude_rays, query_grid(g.k_occlude_rays, count), kQueryBlock, p, g.d_rq_counters,
+        kRayCounterWords, [&p](unsigned long long* c) { p.tallies = c + 1; },
+        stats ? counters : nullptr, &ms);
     if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
-    unsigned long long counters[4] = {0, 0, 0, 0};
-    if (stats)
-        VCRT_TRY(hipMemcpyAsync(counters, g.d_rq_counters, kRayCounterBytes,
-                                hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) {
-        float ms = 0.f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
         stats->kernel_ms = ms;
         stats->segments = count;  // one scan per ray
         stats->group_tests = counters[1];
@@ -2471,23 +2344,22 @@ vcrt_result vcrt_occlude_rays(const float* origins, const float* dirs, const flo
     const vcrt_result a = occlusion_args(origins, dirs, count, occluded);
     if (a != VCRT_SUCCESS) return a;
     const size_t n = count, in_bytes = 3 * sizeof(float) * n;
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_rq_rays), &g.rq_rays_cap, n, 6 * sizeof(float)));
-    if (tmax)
-        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_oq_tmax), &g.oq_tmax_cap, n, sizeof(float)));
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_oq_occluded), &g.oq_occluded_cap, n, 1));
-    float* d_origins = g.d_rq_rays;
-    float* d_dirs = g.d_rq_rays + 3 * n;
+    VCRT_TRY(g.d_rq_rays.reserve(6 * n));
+    if (tmax) VCRT_TRY(g.d_oq_tmax.reserve(n));
+    VCRT_TRY(g.d_oq_occluded.reserve(n));
+    float* d_origins = g.d_rq_rays.data();
+    float* d_dirs = g.d_rq_rays.data() + 3 * n;
     if (n) {
         VCRT_TRY(hipMemcpyAsync(d_origins, origins, in_bytes, hipMemcpyHostToDevice, g.stream));
         VCRT_TRY(hipMemcpyAsync(d_dirs, dirs, in_bytes, hipMemcpyHostToDevice, g.stream));
         if (tmax)
-            VCRT_TRY(hipMemcpyAsync(g.d_oq_tmax, tmax, sizeof(float) * n, hipMemcpyHostToDevice,
-                                    g.stream));
+            VCRT_TRY(hipMemcpyAsync(g.d_oq_tmax.data(), tmax, sizeof(float) * n,
+                                    hipMemcpyHostToDevice, g.stream));
     }
-    const VkResult r = occlusion_device(d_origins, d_dirs, tmax ? g.d_oq_tmax : nullptr, count,
-                                        g.d_oq_occluded, stats);
+    const VkResult r = occlusion_device(d_origins, d_dirs, tmax ? g.d_oq_tmax.data() : nullptr,
+                                        count, g.d_oq_occluded.data(), stats);
     if (r != VK_SUCCESS || n == 0) return r;
-    VCRT_TRY(hipMemcpyAsync(occluded, g.d_oq_occluded, n, hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipMemcpyAsync(occluded, g.d_oq_occluded.data(), n, hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     return VCRT_SUCCESS;
 }
@@ -2497,8 +2369,6 @@ vcrt_result vcrt_occlude_rays(const float* origins, const float* dirs, const flo
 namespace {
 
 constexpr uint64_t kFeatureMaxIndex = uint64_t{1} << 19;  // vcrt_lens_offsets' index bound
-// FeatureParams.tallies: slots of 64 B (listed rays, group tests, box tests), summed here
-constexpr size_t kFeatureCounterBytes = 64 * vcrt::kFeatureTallySlots;
 
 // The arguments both forms of the call check, before anything touches the GPU. The arguments'
 // own faults come first, so that they read the same with and without a renderer.
@@ -2515,27 +2385,26 @@ vcrt_result feature_args(uint32_t first, uint32_t n, const void* albedo, const v
 // origins (the frame's host operations: setup_jitter above) of sample indices first .. first +
 // n - 1 in the call's own tables.
 VkResult feature_tables(uint32_t first, uint32_t n) {
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_jitter_in), &g.ft_jitter_in_cap, n,
-                  sizeof(float2)));
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_jitter), &g.ft_jitter_cap, n, sizeof(float4)));
+    VCRT_TRY(g.d_ft_jitter_in.reserve(n));
+    VCRT_TRY(g.d_ft_jitter.reserve(n));
     g.h_ft_jitter.resize(n);
     make_jitter(first, static_cast<int>(n), g.h_ft_jitter.data());
-    VCRT_TRY(hipMemcpyAsync(g.d_ft_jitter_in, g.h_ft_jitter.data(), sizeof(float2) * n,
+    VCRT_TRY(hipMemcpyAsync(g.d_ft_jitter_in.data(), g.h_ft_jitter.data(), sizeof(float2) * n,
                             hipMemcpyHostToDevice, g.stream));
     if (lens_on()) {
-        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_lens), &g.ft_lens_cap, n, sizeof(float4)));
+        VCRT_TRY(g.d_ft_lens.reserve(n));
         g.h_ft_lens.resize(n);
         for (uint32_t k = 0; k < n; k++) {
             const vcrt::f3 o = vcrt::add(
                 g.cam.center, vcrt::lens_offset(first + k, g.desc.lens_radius, g.cam.u, g.cam.v));
             g.h_ft_lens[k] = make_float4(o.x, o.y, o.z, 0.0f);
         }
-        VCRT_TRY(hipMemcpyAsync(g.d_ft_lens, g.h_ft_lens.data(), sizeof(float4) * n,
+        VCRT_TRY(hipMemcpyAsync(g.d_ft_lens.data(), g.h_ft_lens.data(), sizeof(float4) * n,
                                 hipMemcpyHostToDevice, g.stream));
     }
     vcrt::SetupJitterParams sp{};
-    sp.jitter_in = g.d_ft_jitter_in;
-    sp.jitter = g.d_ft_jitter;
+    sp.jitter_in = g.d_ft_jitter_in.data();
+    sp.jitter = g.d_ft_jitter.data();
     sp.nsamples = n;
     const std::array<float, 12> cam = camera_array();
     for (int i = 0; i < 12; i++) sp.cam[i] = cam[i];
@@ -2551,12 +2420,12 @@ VkResult feature_tables(uint32_t first, uint32_t n) {
 // OcclusionBufferParams): a frame's, with the call's own jitter and lens tables of n samples.
 void frame_ray_scene(vcrt::TraceParams& s, uint32_t n) {
     scene_params(s);
-    s.jitter = g.d_ft_jitter;
-    s.lens = lens_on() ? g.d_ft_lens : nullptr;
-    s.corner = g.d_corner;
-    s.prim_info = g.d_prim_info;
-    s.prim_ids = g.d_prim_ids;
-    s.cam_rec = g.d_cam_rec;
+    s.jitter = g.d_ft_jitter.data();
+    s.lens = lens_on() ? g.d_ft_lens.data() : nullptr;
+    s.corner = g.d_corner.data();
+    s.prim_info = g.d_prim_info.data();
+    s.prim_ids = g.d_prim_ids.data();
+    s.cam_rec = reinterpret_cast<const float4*>(g.d_cam_rec.data());
     s.width = g.desc.width;
     s.height = g.desc.height;
     s.spp = static_cast<int32_t>(n);
@@ -2568,9 +2437,7 @@ void frame_ray_scene(vcrt::TraceParams& s, uint32_t n) {
     const std::array<float, 12> cam = camera_array();
     for (int i = 0; i < 12; i++) s.cam[i] = cam[i];
     // the lists go to a frame whose camera centre passes the range guard (trace_frame)
-    if (!(g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
-          std::fabs(cam[11]) <= 0x1p30f))
-        s.prim_info = nullptr;
+    if (!lists_allowed(cam)) s.prim_info = nullptr;
 }
 
 // The launch on device pointers (checked by the callers): one wave per local tile; returns when
@@ -2581,7 +2448,6 @@ VkResult draw_features_device(uint32_t first, uint32_t n, float* albedo, float* 
         *stats = vcrt_feature_stats{};
         std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_features");
     }
-    if (!g.d_ft_counters) VCRT_TRY(hipMalloc(&g.d_ft_counters, kFeatureCounterBytes));
     const VkResult t = feature_tables(first, n);
     if (t != VK_SUCCESS) return t;
     vcrt::FeatureParams p{};
@@ -2591,25 +2457,14 @@ VkResult draw_features_device(uint32_t first, uint32_t n, float* albedo, float* 
     p.sphere = sphere;
     p.n = n;
     p.use_lists = g.feature_lists ? 1u : 0u;
-    p.tallies = static_cast<unsigned long long*>(g.d_ft_counters);
-    std::vector<unsigned long long> slots(kFeatureCounterBytes / 8, 0ull);
-    if (g.local_tiles > 0) {
-        VCRT_TRY(hipMemsetAsync(g.d_ft_counters, 0, kFeatureCounterBytes, g.stream));
-        VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
-        const VkResult r = launch(g.k_frame_features, (g.local_tiles + 3u) / 4u, 256, 0, p);
-        if (r != VK_SUCCESS) return r;
-        VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
-        if (stats)
-            VCRT_TRY(hipMemcpyAsync(slots.data(), g.d_ft_counters, kFeatureCounterBytes,
-                                    hipMemcpyDeviceToHost, g.stream));
-    }
-    VCRT_TRY(hipStreamSynchronize(g.stream));
+    unsigned long long slots[kFeatureCounterWords] = {};
+    float ms = 0.f;
+    const VkResult r = frame_ray_launch(g.k_frame_features, p, stats ? slots : nullptr, &ms);
+    if (r != VK_SUCCESS) return r;
     if (stats) {
         unsigned long long counters[3] = {0, 0, 0};
-        for (size_t s = 0; s < slots.size(); s += 8)
+        for (size_t s = 0; s < kFeatureCounterWords; s += 8)
             for (int c = 0; c < 3; c++) counters[c] += slots[s + c];
-        float ms = 0.f;
-        if (g.local_tiles > 0) VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
         stats->kernel_ms = ms;
         stats->rays = g.local_pixels * n;
         stats->listed_rays = counters[0];
@@ -2648,41 +2503,35 @@ vcrt_result vcrt_draw_features(uint32_t first, uint32_t n, float* albedo, float*
     if (a != VCRT_SUCCESS) return a;
     if (!g.k_frame_features) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     const size_t elems = g.local_elems;
-    if (albedo)
-        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_albedo), &g.ft_albedo_cap, elems,
-                      sizeof(float4)));
-    if (normal_depth)
-        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_normal_depth), &g.ft_normal_depth_cap,
-                      elems, sizeof(float4)));
-    if (sphere)
-        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ft_sphere), &g.ft_sphere_cap, elems,
-                      sizeof(int32_t)));
+    if (albedo) VCRT_TRY(g.d_ft_albedo.reserve(elems));
+    if (normal_depth) VCRT_TRY(g.d_ft_normal_depth.reserve(elems));
+    if (sphere) VCRT_TRY(g.d_ft_sphere.reserve(elems));
     // packed tiles: the slots outside the frame keep what the caller's planes hold
     if (g.desc.world_size > 1 && elems) {
         if (albedo)
-            VCRT_TRY(hipMemcpyAsync(g.d_ft_albedo, albedo, sizeof(float4) * elems,
+            VCRT_TRY(hipMemcpyAsync(g.d_ft_albedo.data(), albedo, sizeof(float4) * elems,
                                     hipMemcpyHostToDevice, g.stream));
         if (normal_depth)
-            VCRT_TRY(hipMemcpyAsync(g.d_ft_normal_depth, normal_depth, sizeof(float4) * elems,
-                                    hipMemcpyHostToDevice, g.stream));
+            VCRT_TRY(hipMemcpyAsync(g.d_ft_normal_depth.data(), normal_depth,
+                                    sizeof(float4) * elems, hipMemcpyHostToDevice, g.stream));
         if (sphere)
-            VCRT_TRY(hipMemcpyAsync(g.d_ft_sphere, sphere, sizeof(int32_t) * elems,
+            VCRT_TRY(hipMemcpyAsync(g.d_ft_sphere.data(), sphere, sizeof(int32_t) * elems,
                                     hipMemcpyHostToDevice, g.stream));
     }
     const VkResult r = draw_features_device(
-        first, n, albedo ? reinterpret_cast<float*>(g.d_ft_albedo) : nullptr,
-        normal_depth ? reinterpret_cast<float*>(g.d_ft_normal_depth) : nullptr,
-        sphere ? g.d_ft_sphere : nullptr, stats);
+        first, n, albedo ? reinterpret_cast<float*>(g.d_ft_albedo.data()) : nullptr,
+        normal_depth ? reinterpret_cast<float*>(g.d_ft_normal_depth.data()) : nullptr,
+        sphere ? g.d_ft_sphere.data() : nullptr, stats);
     if (r != VK_SUCCESS) return r;
     if (elems) {
         if (albedo)
-            VCRT_TRY(hipMemcpyAsync(albedo, g.d_ft_albedo, sizeof(float4) * elems,
+            VCRT_TRY(hipMemcpyAsync(albedo, g.d_ft_albedo.data(), sizeof(float4) * elems,
                                     hipMemcpyDeviceToHost, g.stream));
         if (normal_depth)
-            VCRT_TRY(hipMemcpyAsync(normal_depth, g.d_ft_normal_depth, sizeof(float4) * elems,
-                                    hipMemcpyDeviceToHost, g.stream));
+            VCRT_TRY(hipMemcpyAsync(normal_depth, g.d_ft_normal_depth.data(),
+                                    sizeof(float4) * elems, hipMemcpyDeviceToHost, g.stream));
         if (sphere)
-            VCRT_TRY(hipMemcpyAsync(sphere, g.d_ft_sphere, sizeof(int32_t) * elems,
+            VCRT_TRY(hipMemcpyAsync(sphere, g.d_ft_sphere.data(), sizeof(int32_t) * elems,
                                     hipMemcpyDeviceToHost, g.stream));
         VCRT_TRY(hipStreamSynchronize(g.stream));
     }
@@ -2718,46 +2567,34 @@ VkResult draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, float rea
         *stats = vcrt_occlusion_buffer_stats{};
         std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_occlusion");
     }
-    if (!g.d_ft_counters) VCRT_TRY(hipMalloc(&g.d_ft_counters, kFeatureCounterBytes));
     const VkResult t = feature_tables(first, n);
     if (t != VK_SUCCESS) return t;
     // u_j of j = first m .. (first + n) m - 1, sample-major (vcrt_ambient_dirs' values)
     const uint32_t ndirs = n * m;
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ao_dirs), &g.ao_dirs_cap, ndirs, sizeof(float4)));
+    VCRT_TRY(g.d_ao_dirs.reserve(ndirs));
     g.h_ao_dirs.resize(ndirs);
     for (uint32_t k = 0; k < ndirs; k++) {
         const vcrt::f3 u = vcrt::ambient_dir(first * m + k);
         g.h_ao_dirs[k] = make_float4(u.x, u.y, u.z, 0.0f);
     }
-    VCRT_TRY(hipMemcpyAsync(g.d_ao_dirs, g.h_ao_dirs.data(), sizeof(float4) * ndirs,
+    VCRT_TRY(hipMemcpyAsync(g.d_ao_dirs.data(), g.h_ao_dirs.data(), sizeof(float4) * ndirs,
                             hipMemcpyHostToDevice, g.stream));
     vcrt::OcclusionBufferParams p{};
     frame_ray_scene(p.scene, n);
     p.visibility = reinterpret_cast<float4*>(visibility);
-    p.dirs = g.d_ao_dirs;
+    p.dirs = g.d_ao_dirs.data();
     p.n = n;
     p.m = m;
     p.reach = reach;
     p.use_lists = g.feature_lists ? 1u : 0u;
-    p.tallies = static_cast<unsigned long long*>(g.d_ft_counters);
-    std::vector<unsigned long long> slots(kFeatureCounterBytes / 8, 0ull);
-    if (g.local_tiles > 0) {
-        VCRT_TRY(hipMemsetAsync(g.d_ft_counters, 0, kFeatureCounterBytes, g.stream));
-        VCRT_TRY(hipEventRecord(g.ev_start, g.stream));
-        const VkResult r = launch(g.k_frame_occlusion, (g.local_tiles + 3u) / 4u, 256, 0, p);
-        if (r != VK_SUCCESS) return r;
-        VCRT_TRY(hipEventRecord(g.ev_stop, g.stream));
-        if (stats)
-            VCRT_TRY(hipMemcpyAsync(slots.data(), g.d_ft_counters, kFeatureCounterBytes,
-                                    hipMemcpyDeviceToHost, g.stream));
-    }
-    VCRT_TRY(hipStreamSynchronize(g.stream));
+    unsigned long long slots[kFeatureCounterWords] = {};
+    float ms = 0.f;
+    const VkResult r = frame_ray_launch(g.k_frame_occlusion, p, stats ? slots : nullptr, &ms);
+    if (r != VK_SUCCESS) return r;
     if (stats) {
         unsigned long long counters[5] = {0, 0, 0, 0, 0};
-        for (size_t s = 0; s < slots.size(); s += 8)
+        for (size_t s = 0; s < kFeatureCounterWords; s += 8)
             for (int c = 0; c < 5; c++) counters[c] += slots[s + c];
-        float ms = 0.f;
-        if (g.local_tiles > 0) VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start, g.ev_stop));
         stats->kernel_ms = ms;
         stats->rays = g.local_pixels * n;
         stats->hit_rays = counters[3];
@@ -2792,17 +2629,16 @@ vcrt_result vcrt_draw_occlusion(uint32_t first, uint32_t n, uint32_t m, float re
     if (a != VCRT_SUCCESS) return a;
     if (!g.k_frame_occlusion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     const size_t elems = g.local_elems;
-    VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_ao_plane), &g.ao_plane_cap, elems,
-                  sizeof(float4)));
+    VCRT_TRY(g.d_ao_plane.reserve(elems));
     // packed tiles: the slots outside the frame keep what the caller's plane holds
     if (g.desc.world_size > 1 && elems)
-        VCRT_TRY(hipMemcpyAsync(g.d_ao_plane, visibility, sizeof(float4) * elems,
+        VCRT_TRY(hipMemcpyAsync(g.d_ao_plane.data(), visibility, sizeof(float4) * elems,
                                 hipMemcpyHostToDevice, g.stream));
     const VkResult r = draw_occlusion_device(first, n, m, reach,
-                                             reinterpret_cast<float*>(g.d_ao_plane), stats);
+                                             reinterpret_cast<float*>(g.d_ao_plane.data()), stats);
     if (r != VK_SUCCESS) return r;
     if (elems) {
-        VCRT_TRY(hipMemcpyAsync(visibility, g.d_ao_plane, sizeof(float4) * elems,
+        VCRT_TRY(hipMemcpyAsync(visibility, g.d_ao_plane.data(), sizeof(float4) * elems,
                                 hipMemcpyDeviceToHost, g.stream));
         VCRT_TRY(hipStreamSynchronize(g.stream));
     }
@@ -2831,10 +2667,8 @@ VkResult denoise_device(const float* colour, const float* albedo, const float* n
     const int32_t levels = pr.levels;
     // pass l reads the plane pass l - 1 wrote: the colour, the scratch planes in turn, the output
     for (int32_t b = 0; b < std::min(levels - 1, 2); b++)
-        VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_dn_scratch[b]), &g.dn_scratch_cap[b], pixels,
-                      sizeof(float4)));
-    for (int32_t l = 0; l <= levels; l++)
-        if (!g.ev_dn[l]) VCRT_TRY(hipEventCreate(&g.ev_dn[l]));
+        VCRT_TRY(g.d_dn_scratch[b].reserve(pixels));
+    for (int32_t l = 0; l <= levels; l++) VCRT_TRY(g.ev_dn[l].create());
     const bool demod = pr.demodulate != 0 && albedo;
     uint32_t terms = 0;
     if (normal_depth && k4[0] != 0.0f) terms |= vcrt::kDenoiseNormal;
@@ -2843,14 +2677,14 @@ VkResult denoise_device(const float* colour, const float* albedo, const float* n
     const int32_t lds_passes = std::min(denoise_lds_passes(), levels);
     float kl = k4[3];
     const float* in = colour;
-    VCRT_TRY(hipEventRecord(g.ev_dn[0], g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_dn[0].get(), g.stream));
     for (int32_t l = 0; l < levels; l++) {
         vcrt::DenoiseParams p{};
         p.in = in;
         p.colour = colour;
         p.albedo = albedo;
         p.normal_depth = normal_depth;
-        p.out = l == levels - 1 ? out : reinterpret_cast<float*>(g.d_dn_scratch[l & 1]);
+        p.out = l == levels - 1 ? out : reinterpret_cast<float*>(g.d_dn_scratch[l & 1].data());
         p.width = static_cast<uint32_t>(width);
         p.height = static_cast<uint32_t>(height);
         p.step = 1u << l;
@@ -2880,7 +2714,7 @@ VkResult denoise_device(const float* colour, const float* albedo, const float* n
             r = launch(g.k_denoise_pass, p.tiles_x * tiles_y, vcrt::kDenoiseThreads, 0, p);
         }
         if (r != VK_SUCCESS) return r;
-        VCRT_TRY(hipEventRecord(g.ev_dn[l + 1], g.stream));
+        VCRT_TRY(hipEventRecord(g.ev_dn[l + 1].get(), g.stream));
         in = p.out;
         kl = kl * 4.0f;
     }
@@ -2891,10 +2725,10 @@ VkResult denoise_device(const float* colour, const float* albedo, const float* n
         stats->passes = levels;
         stats->lds_passes = lds_passes;
         float ms = 0.f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[0], g.ev_dn[levels]));
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[0].get(), g.ev_dn[levels].get()));
         stats->kernel_ms = ms;
         for (int32_t l = 0; l < levels; l++) {
-            VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[l], g.ev_dn[l + 1]));
+            VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[l].get(), g.ev_dn[l + 1].get()));
             stats->pass_ms[l] = ms;
         }
     }
@@ -2941,19 +2775,18 @@ vcrt_result vcrt_denoise(const float* colour, const float* albedo, const float* 
     const float* dev[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 4; k++)  // the three inputs that are there, and the output
         if (k == 3 || host[k])
-            VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_dn_stage[k]), &g.dn_stage_cap[k], pixels,
-                          sizeof(float4)));
+            VCRT_TRY(g.d_dn_stage[k].reserve(pixels));
     for (int k = 0; k < 3; k++) {
         if (!host[k]) continue;
-        VCRT_TRY(hipMemcpyAsync(g.d_dn_stage[k], host[k], sizeof(float4) * pixels,
+        VCRT_TRY(hipMemcpyAsync(g.d_dn_stage[k].data(), host[k], sizeof(float4) * pixels,
                                 hipMemcpyHostToDevice, g.stream));
-        dev[k] = reinterpret_cast<const float*>(g.d_dn_stage[k]);
+        dev[k] = reinterpret_cast<const float*>(g.d_dn_stage[k].data());
     }
     const VkResult r = denoise_device(dev[0], dev[1], dev[2], width, height, pr, k4,
-                                      reinterpret_cast<float*>(g.d_dn_stage[3]), stats);
+                                      reinterpret_cast<float*>(g.d_dn_stage[3].data()), stats);
     if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(out, g.d_dn_stage[3], sizeof(float4) * pixels, hipMemcpyDeviceToHost,
-                            g.stream));
+    VCRT_TRY(hipMemcpyAsync(out, g.d_dn_stage[3].data(), sizeof(float4) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;
@@ -2998,20 +2831,25 @@ vcrt_result vcrt_comm_init(const vcrt_comm_id* id) {
         return to_vk(err);
     };
     hipError_t err;
-    if ((err = hipEventCreate(&g.ev_gather_start)) != hipSuccess) return fail(err);
-    if ((err = hipEventCreate(&g.ev_gather)) != hipSuccess) return fail(err);
+    if ((err = g.ev_gather_start.create()) != hipSuccess) return fail(err);
+    if ((err = g.ev_gather.create()) != hipSuccess) return fail(err);
     if (g.desc.world_size > 1 && g.desc.rank == 0) {
-        const size_t slab = static_cast<size_t>(g.pad_tiles) * 64 * sizeof(float4);
-        const size_t all = slab * static_cast<size_t>(g.desc.world_size);
-        if ((err = hipMalloc(&g.d_gather, all)) != hipSuccess) return fail(err);
-        if ((err = hipMemsetAsync(g.d_gather, 0, all, g.stream)) != hipSuccess) return fail(err);
-        const size_t frame = static_cast<size_t>(g.desc.width) * g.desc.height * sizeof(float4);
-        if ((err = hipMalloc(&g.d_frame, frame)) != hipSuccess) return fail(err);
-        if ((err = hipMemsetAsync(g.d_frame, 0, frame, g.stream)) != hipSuccess) return fail(err);
+        // (once per vcrt_begin: both buffers are empty here)
+        const size_t all = static_cast<size_t>(g.pad_tiles) * 64 *
+                           static_cast<size_t>(g.desc.world_size);  // float4 elements
+        if ((err = g.d_gather.reserve(all)) != hipSuccess) return fail(err);
+        if ((err = hipMemsetAsync(g.d_gather.data(), 0, all * sizeof(float4), g.stream)) !=
+            hipSuccess)
+            return fail(err);
+        const size_t frame = static_cast<size_t>(g.desc.width) * g.desc.height;
+        if ((err = g.d_frame.reserve(frame)) != hipSuccess) return fail(err);
+        if ((err = hipMemsetAsync(g.d_frame.data(), 0, frame * sizeof(float4), g.stream)) !=
+            hipSuccess)
+            return fail(err);
         if ((err = hipStreamSynchronize(g.stream)) != hipSuccess) return fail(err);
-        g.d_fb = g.d_gather;  // rank 0 renders straight into its slot of the gather buffer
+        g.d_fb = g.d_gather.data();  // rank 0 renders straight into its slot of the gather buffer
     } else {
-        g.d_fb = g.d_fb_own;
+        g.d_fb = g.d_fb_own.data();
     }
     return VCRT_SUCCESS;
 }
@@ -3044,7 +2882,7 @@ vcrt_result vcrt_set_framebuffer_device(void* device_ptr, size_t bytes) {
     if (!g.begun) return VCRT_ERROR_INITIALIZATION_FAILED;
     if (g.comm) return VCRT_ERROR_FEATURE_NOT_PRESENT;  // the gather owns the buffers
     if (device_ptr == nullptr) {
-        g.d_fb = g.d_fb_own;
+        g.d_fb = g.d_fb_own.data();
         return VCRT_SUCCESS;
     }
     if (bytes < g.fb_bytes || (reinterpret_cast<uintptr_t>(device_ptr) & 15u))
@@ -3098,7 +2936,7 @@ vcrt_result vcrt_set_camera(const vcrt_camera* camera) {
     // the pixel corners, and the jitter and lens tables of sample 0 (accumulation restarts)
     VkResult r = setup_jitter(0, g.total_pixels != 0);
     if (r != VK_SUCCESS) return r;
-    if (g.d_prim_info != nullptr && g.ncgroups > 0) {  // the renderer has lists (vcrt_set_scene)
+    if (g.d_prim_info.data() && g.ncgroups > 0) {  // the renderer has lists (vcrt_set_scene)
         const char* how = std::getenv("VCRT_CAMERA_LISTS");
         const bool device = !(how && std::strcmp(how, "host") == 0) && g.k_cl_prepare &&
                             g.k_cl_count && g.k_cl_scan && g.k_cl_fill;
@@ -3132,14 +2970,14 @@ int32_t vcrt_camera_lists_read(uint32_t* group_info, uint32_t* sphere_info, int3
     if (!g.begun) return VCRT_ERROR_INITIALIZATION_FAILED;
     if (num_ids) *num_ids = 0;
     if (num_pairs) *num_pairs = 0;
-    if (g.d_prim_info == nullptr) return 0;  // no tables, a lens, or VCRT_PRIMARY_LISTS=0
+    if (g.d_prim_info.data() == nullptr) return 0;  // no tables, a lens, or VCRT_PRIMARY_LISTS=0
     VCRT_TRY(hipStreamSynchronize(g.stream));
     const size_t n = 4 * static_cast<size_t>(g.local_tiles);
     if (num_ids) *num_ids = static_cast<int32_t>(g.prim_nids);
     if (num_pairs) *num_pairs = static_cast<int32_t>(g.prim_npairs);
     if ((group_info || sphere_info) && cap_entries >= 0 && static_cast<size_t>(cap_entries) >= n) {
         std::vector<uint32_t> info(2 * n);
-        VCRT_TRY(hipMemcpy(info.data(), g.d_prim_info, sizeof(uint32_t) * info.size(),
+        VCRT_TRY(hipMemcpy(info.data(), g.d_prim_info.data(), sizeof(uint32_t) * info.size(),
                            hipMemcpyDeviceToHost));
         for (size_t e = 0; e < n; e++) {
             if (group_info) group_info[e] = info[2 * e];
@@ -3147,11 +2985,11 @@ int32_t vcrt_camera_lists_read(uint32_t* group_info, uint32_t* sphere_info, int3
         }
     }
     if (ids && g.prim_nids > 0 && cap_ids >= 0 && static_cast<size_t>(cap_ids) >= g.prim_nids)
-        VCRT_TRY(hipMemcpy(ids, g.d_prim_ids, sizeof(uint16_t) * g.prim_nids,
+        VCRT_TRY(hipMemcpy(ids, g.d_prim_ids.data(), sizeof(uint16_t) * g.prim_nids,
                            hipMemcpyDeviceToHost));
     const size_t floats = g.prim_npairs * 12;
     if (rec && floats > 0 && cap_floats >= 0 && static_cast<size_t>(cap_floats) >= floats)
-        VCRT_TRY(hipMemcpy(rec, reinterpret_cast<const float*>(g.d_cam_rec) +
+        VCRT_TRY(hipMemcpy(rec, reinterpret_cast<const float*>(g.d_cam_rec.data()) +
                                     static_cast<size_t>(g.ncbig) * 16,
                            sizeof(float) * floats, hipMemcpyDeviceToHost));
     return static_cast<int32_t>(n);
@@ -3160,20 +2998,6 @@ int32_t vcrt_camera_lists_read(uint32_t* group_info, uint32_t* sphere_info, int3
 // ---- scene updates ------------------------------------------------------------------------
 
 namespace {
-
-bool values_bounded(const vcrt_sphere* s, int32_t count) {
-    for (int32_t i = 0; i < count; i++)
-        for (float v : {s[i].center[0], s[i].center[1], s[i].center[2], s[i].radius})
-            if (!(std::fabs(v) <= 0x1p30f)) return false;  // also rejects NaN
-    return true;
-}
-
-bool values_radii_safe(const vcrt_sphere* s, int32_t count) {
-    for (int32_t i = 0; i < count; i++)
-        if (!(std::fabs(s[i].radius) >= 0x1p-40f && std::fabs(s[i].radius) <= 0x1p30f))
-            return false;
-    return true;
-}
 
 // The scalars of refitted tables into the renderer's state, as vcrt_set_scene takes them.
 void install_scalars(const vcrt::CullTables& ct, bool bounded, bool radii_safe) {
@@ -3186,7 +3010,7 @@ void install_scalars(const vcrt::CullTables& ct, bool bounded, bool radii_safe) 
     std::memcpy(g.cfp_y, ct.fp_y, sizeof(g.cfp_y));
     g.cfp_k2 = ct.fp_k2;
     g.cfp_always = ct.fp_always;
-    if (ct.gf_cells > 0 && g.d_gf_tab != nullptr) {
+    if (ct.gf_cells > 0 && g.d_gf_tab.data() != nullptr) {
         std::memcpy(g.cgf_x, ct.gf_x, sizeof(g.cgf_x));
         std::memcpy(g.cgf_z, ct.gf_z, sizeof(g.cgf_z));
         std::memcpy(g.cgf_always, ct.gf_always, sizeof(g.cgf_always));
@@ -3292,28 +3116,32 @@ const void* table_device(int32_t table, size_t* bytes) {
     *bytes = 0;
     if (table == VCRT_TABLE_LINEAR) {
         *bytes = ((n + 3) / 4 + 1) * 64;
-        return g.d_geom;
+        return g.d_geom.data();
     }
     if (table == VCRT_TABLE_CENTER_RADIUS || table == VCRT_TABLE_SHADE ||
         table == VCRT_TABLE_MATERIAL) {
         *bytes = n * 16;
-        return table == VCRT_TABLE_CENTER_RADIUS ? g.d_center_radius
-               : table == VCRT_TABLE_SHADE       ? g.d_shade
-                                                 : g.d_material;
+        return table == VCRT_TABLE_CENTER_RADIUS ? g.d_center_radius.data()
+               : table == VCRT_TABLE_SHADE       ? g.d_shade.data()
+                                                 : g.d_material.data();
     }
     if (ng == 0) return nullptr;
     const size_t node_pairs = ng / vcrt::kNodeGroups / 2, tops = (ng + 63) / 64;
     switch (table) {
-        case VCRT_TABLE_GROUPS: *bytes = (static_cast<size_t>(g.ncbig) + ng) * 80; return g.d_cgroup;
-        case VCRT_TABLE_BOUND: *bytes = ng / 2 * 64; return g.d_cbound;
-        case VCRT_TABLE_BOUND_NF: *bytes = ng / 2 * 80; return g.d_cbound_nf;
-        case VCRT_TABLE_NODE: *bytes = node_pairs * 64; return g.d_cnode;
-        case VCRT_TABLE_NODE_NF: *bytes = (node_pairs + 3) / 4 * 4 * 80; return g.d_cnode_nf;
-        case VCRT_TABLE_TOP: *bytes = (tops + (tops & 1)) / 2 * 64; return g.d_ctop;
+        case VCRT_TABLE_GROUPS:
+            *bytes = (static_cast<size_t>(g.ncbig) + ng) * 80;
+            return g.d_cgroup.data();
+        case VCRT_TABLE_BOUND: *bytes = ng / 2 * 64; return g.d_cbound.data();
+        case VCRT_TABLE_BOUND_NF: *bytes = ng / 2 * 80; return g.d_cbound_nf.data();
+        case VCRT_TABLE_NODE: *bytes = node_pairs * 64; return g.d_cnode.data();
+        case VCRT_TABLE_NODE_NF: *bytes = (node_pairs + 3) / 4 * 4 * 80; return g.d_cnode_nf.data();
+        case VCRT_TABLE_TOP: *bytes = (tops + (tops & 1)) / 2 * 64; return g.d_ctop.data();
         case VCRT_TABLE_FOOT:
             *bytes = sizeof(uint32_t) * vcrt::kFootCells * (ng > 128 ? 4 : 2);
-            return g.d_fp_tab;
-        case VCRT_TABLE_GROUP_FOOT: *bytes = sizeof(uint32_t) * 16 * g.cgf_n; return g.d_gf_tab;
+            return g.d_fp_tab.data();
+        case VCRT_TABLE_GROUP_FOOT:
+            *bytes = sizeof(uint32_t) * 16 * g.cgf_n;
+            return g.d_gf_tab.data();
         default: return nullptr;
     }
 }
@@ -3347,44 +3175,43 @@ VkResult refit_on_host() {
 // are then garbage and the caller rebuilds).
 VkResult refit_on_device(const float* d_values, vcrt_sphere* back, bool* unbounded) {
     *unbounded = false;
-    if (!g.d_su_summary) VCRT_TRY(hipMalloc(&g.d_su_summary, sizeof(vcrt::SceneSummary)));
-    if (!g.h_su_summary) VCRT_TRY(hipHostMalloc(&g.h_su_summary, sizeof(vcrt::SceneSummary)));
-    for (int k = 0; k < 2; k++)
-        if (!g.ev_su[k]) VCRT_TRY(hipEventCreate(&g.ev_su[k]));
+    VCRT_TRY(g.d_su_summary.reserve(1));
+    VCRT_TRY(g.h_su_summary.reserve(1));
+    for (Event& e : g.ev_su) VCRT_TRY(e.create());
     vcrt::SceneUpdateParams p{};
     p.spheres = d_values;
-    p.geom = reinterpret_cast<float*>(g.d_geom);
-    p.center_radius = reinterpret_cast<float*>(g.d_center_radius);
-    p.shade = reinterpret_cast<float*>(g.d_shade);
-    p.material = reinterpret_cast<float*>(g.d_material);
-    p.cgroup = reinterpret_cast<float*>(g.d_cgroup);
-    p.cbound = reinterpret_cast<float*>(g.d_cbound);
-    p.cbound_nf = reinterpret_cast<float*>(g.d_cbound_nf);
-    p.cnode = reinterpret_cast<float*>(g.d_cnode);
-    p.cnode_nf = reinterpret_cast<float*>(g.d_cnode_nf);
-    p.ctop = reinterpret_cast<float*>(g.d_ctop);
-    p.fp_tab = g.d_fp_tab;
-    p.gf_tab = reinterpret_cast<uint32_t*>(g.d_gf_tab);
-    p.summary = g.d_su_summary;
+    p.geom = reinterpret_cast<float*>(g.d_geom.data());
+    p.center_radius = reinterpret_cast<float*>(g.d_center_radius.data());
+    p.shade = reinterpret_cast<float*>(g.d_shade.data());
+    p.material = reinterpret_cast<float*>(g.d_material.data());
+    p.cgroup = reinterpret_cast<float*>(g.d_cgroup.data());
+    p.cbound = reinterpret_cast<float*>(g.d_cbound.data());
+    p.cbound_nf = reinterpret_cast<float*>(g.d_cbound_nf.data());
+    p.cnode = reinterpret_cast<float*>(g.d_cnode.data());
+    p.cnode_nf = reinterpret_cast<float*>(g.d_cnode_nf.data());
+    p.ctop = reinterpret_cast<float*>(g.d_ctop.data());
+    p.fp_tab = g.d_fp_tab.data();
+    p.gf_tab = reinterpret_cast<uint32_t*>(g.d_gf_tab.data());
+    p.summary = g.d_su_summary.data();
     p.nspheres = static_cast<uint32_t>(g.nspheres);
     p.nbig = static_cast<uint32_t>(g.ncbig);
     p.ngroups = static_cast<uint32_t>(g.ncgroups);
     p.nnodes = p.ngroups / static_cast<uint32_t>(vcrt::kNodeGroups);
     p.ntops = (p.ngroups + 63u) / 64u;
-    VCRT_TRY(hipEventRecord(g.ev_su[0], g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_su[0].get(), g.stream));
     const uint32_t entries = 4u * ((p.nspheres + 3u) / 4u + 1u);
     VkResult r = launch(g.k_su_rows, (entries + 255u) / 256u, 256, 0, p);
     if (r != VK_SUCCESS) return r;
     if ((r = launch(g.k_su_groups, (p.nbig + p.ngroups + 255u) / 256u, 256, 0, p)) != VK_SUCCESS)
         return r;
     if ((r = launch(g.k_su_levels, 1, vcrt::kSceneSummaryThreads, 0, p)) != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(g.h_su_summary, g.d_su_summary, sizeof(vcrt::SceneSummary),
-                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipMemcpyAsync(g.h_su_summary.data(), g.d_su_summary.data(),
+                            sizeof(vcrt::SceneSummary), hipMemcpyDeviceToHost, g.stream));
     if (back)
         VCRT_TRY(hipMemcpyAsync(back, d_values, sizeof(vcrt_sphere) * p.nspheres,
                                 hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
-    const vcrt::SceneSummary m = *g.h_su_summary;
+    const vcrt::SceneSummary m = *g.h_su_summary.data();
     if (!m.bounded) {
         *unbounded = true;
         return VK_SUCCESS;
@@ -3401,11 +3228,11 @@ VkResult refit_on_device(const float* d_values, vcrt_sphere* back, bool* unbound
         p.gf_z[k] = ct.gf_z[k];
     }
     p.fp_ok = ct.fp_ok ? 1u : 0u;
-    p.gf_n = g.d_gf_tab ? g.cgf_n : 0u;
+    p.gf_n = g.d_gf_tab.data() ? g.cgf_n : 0u;
     p.gf_keep_all = ct.gf_keep_all ? 1u : 0u;
     const uint32_t cells = vcrt::kFootCells * (p.ngroups > 128u ? 4u : 2u) + 4u * p.gf_n;
     if ((r = launch(g.k_su_footprint, (cells + 255u) / 256u, 256, 0, p)) != VK_SUCCESS) return r;
-    VCRT_TRY(hipEventRecord(g.ev_su[1], g.stream));
+    VCRT_TRY(hipEventRecord(g.ev_su[1].get(), g.stream));
     g.h_ct_stale = true;
     return VK_SUCCESS;
 }
@@ -3457,11 +3284,10 @@ vcrt_result update_spheres(const vcrt_sphere* spheres, int32_t count, bool on_de
         if (!on_device_ptr) {
             if (!values_bounded(spheres, count)) return rebuild(spheres);
             const size_t floats = static_cast<size_t>(count) * 10;
-            VCRT_TRY(grow(reinterpret_cast<void**>(&g.d_su_spheres), &g.su_spheres_cap, floats,
-                          sizeof(float)));
-            VCRT_TRY(hipMemcpyAsync(g.d_su_spheres, spheres, sizeof(float) * floats,
+            VCRT_TRY(g.d_su_spheres.reserve(floats));
+            VCRT_TRY(hipMemcpyAsync(g.d_su_spheres.data(), spheres, sizeof(float) * floats,
                                     hipMemcpyHostToDevice, g.stream));
-            d_values = g.d_su_spheres;
+            d_values = g.d_su_spheres.data();
             if (spheres != g.h_spheres.data()) g.h_spheres.assign(spheres, spheres + count);
         } else {
             fetched.resize(count);
@@ -3475,7 +3301,7 @@ vcrt_result update_spheres(const vcrt_sphere* spheres, int32_t count, bool on_de
         device = true;
     }
     // the camera-ray lists and camera-relative records of the refitted tables
-    if (g.d_prim_info != nullptr) {
+    if (g.d_prim_info.data() != nullptr) {
         const char* lists = std::getenv("VCRT_CAMERA_LISTS");
         const bool lists_device = !(lists && std::strcmp(lists, "host") == 0) && g.k_cl_prepare &&
                                   g.k_cl_count && g.k_cl_scan && g.k_cl_fill;
@@ -3497,14 +3323,15 @@ vcrt_result update_spheres(const vcrt_sphere* spheres, int32_t count, bool on_de
     g.stage.pName = select_kernel().name;
     if (device) {
         float ms = 0.0f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_su[0], g.ev_su[1]));
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_su[0].get(), g.ev_su[1].get()));
         g.su_stats.refit_ms = ms;
     }
     const uint64_t ng = static_cast<uint64_t>(g.ncgroups), tops = (ng + 63) / 64;
     g.su_stats.on_device = device ? 1 : 0;
     g.su_stats.groups = static_cast<uint64_t>(g.ncbig) + ng;
     g.su_stats.boxes = ng + ng / vcrt::kNodeGroups + tops + (tops & 1);
-    g.su_stats.footprint_cells = 4ull * vcrt::kFootCells + 4ull * (g.d_gf_tab ? g.cgf_n : 0u);
+    g.su_stats.footprint_cells =
+        4ull * vcrt::kFootCells + 4ull * (g.d_gf_tab.data() ? g.cgf_n : 0u);
     g.su_stats.host_ms = elapsed();
     return VCRT_SUCCESS;
 }
@@ -3564,24 +3391,19 @@ vcrt_result vcrt_selftest_sin(uint32_t first, uint32_t count, uint64_t* mismatch
         return VCRT_ERROR_INITIALIZATION_FAILED;
     hipFunction_t f = nullptr;
     VCRT_TRY(hipModuleGetFunction(&f, static_cast<hipModule_t>(g.stage.module), "vcrt_check_sin"));
-    void* buf = nullptr;  // [2] counters + first mismatch
-    VCRT_TRY(hipMalloc(&buf, 24));
+    DeviceBuffer<uint32_t> buf;  // [2] u64 counters + first mismatch; freed on every return
+    VCRT_TRY(buf.reserve(6));
     uint32_t init[6] = {0, 0, 0, 0, 0xFFFFFFFFu, 0};
-    hipError_t e = hipMemcpy(buf, init, sizeof(init), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the check runs on g.stream)
-    vcrt::SinCheckParams sp{static_cast<unsigned long long*>(buf),
-                            reinterpret_cast<uint32_t*>(static_cast<char*>(buf) + 16), first, count,
-                            {}};
+    VCRT_TRY(hipMemcpy(buf.data(), init, sizeof(init), hipMemcpyHostToDevice));
+    VCRT_TRY(hipStreamSynchronize(nullptr));  // (the check runs on g.stream)
+    vcrt::SinCheckParams sp{reinterpret_cast<unsigned long long*>(buf.data()), buf.data() + 4,
+                            first, count, {}};
     for (int j = 0; j < 13; j++) sp.sin_c[j] = vcrt::kSinC[j];
-    VkResult r = e == hipSuccess ? launch(f, 8 * 256 * 8, 256, 0, sp) : to_vk(e);
-    uint32_t out[6] = {0, 0, 0, 0, 0, 0};
-    if (r == VK_SUCCESS) {
-        e = hipMemcpyAsync(out, buf, sizeof(out), hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        r = to_vk(e);
-    }
-    (void)hipFree(buf);
+    const VkResult r = launch(f, 8 * 256 * 8, 256, 0, sp);
     if (r != VK_SUCCESS) return r;
+    uint32_t out[6] = {0, 0, 0, 0, 0, 0};
+    VCRT_TRY(hipMemcpyAsync(out, buf.data(), sizeof(out), hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
     std::memcpy(mismatches, &out[0], 8);
     std::memcpy(fallbacks, &out[2], 8);
     *first_mismatch = out[4];
@@ -3595,9 +3417,9 @@ vcrt_result vcrt_selftest_unit(const float* triples, uint32_t n, float* out) {
     hipFunction_t f = nullptr;
     VCRT_TRY(hipModuleGetFunction(&f, static_cast<hipModule_t>(g.stage.module), "vcrt_check_unit"));
     const size_t bytes = sizeof(float) * 3u * n;
-    void* buf = nullptr;  // the triples, then their unit vectors
-    VCRT_TRY(hipMalloc(&buf, 2 * bytes));
-    float* d_in = static_cast<float*>(buf);
+    DeviceBuffer<float> buf;  // the triples, then their unit vectors; freed on every return
+    VCRT_TRY(buf.reserve(6u * static_cast<size_t>(n)));
+    float* d_in = buf.data();
     float* d_out = d_in + 3u * static_cast<size_t>(n);
     hipError_t e = hipMemcpyAsync(d_in, triples, bytes, hipMemcpyHostToDevice, g.stream);
     vcrt::UnitCheckParams up{d_in, d_out, n};
@@ -3610,8 +3432,7 @@ vcrt_result vcrt_selftest_unit(const float* triples, uint32_t n, float* out) {
     } else {
         (void)hipStreamSynchronize(g.stream);
     }
-    (void)hipFree(buf);
-    return r == VK_SUCCESS ? VCRT_SUCCESS : r;
+    return r;
 }
 
 vcrt_result vcrt_read_framebuffer_srgb8(uint8_t* rgba8, size_t bytes) {
@@ -3619,14 +3440,12 @@ vcrt_result vcrt_read_framebuffer_srgb8(uint8_t* rgba8, size_t bytes) {
     if (!g.begun || (!rgba8 && v.elems)) return VCRT_ERROR_INITIALIZATION_FAILED;
     if (bytes < static_cast<size_t>(v.elems) * 4) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
     if (!v.elems) return VCRT_SUCCESS;
-    if (g.d_srgb) (void)hipFree(g.d_srgb);  // the view may have grown (vcrt_comm_init)
-    g.d_srgb = nullptr;
-    VCRT_TRY(hipMalloc(&g.d_srgb, sizeof(uchar4) * v.elems));
-    vcrt::EncodeParams ep{v.ptr, g.d_srgb, g.d_srgb_thresholds, v.elems};
+    VCRT_TRY(g.d_srgb.reserve(v.elems));  // the view may have grown (vcrt_comm_init)
+    vcrt::EncodeParams ep{v.ptr, g.d_srgb.data(), g.d_srgb_thresholds.data(), v.elems};
     const uint32_t grid = std::min<uint32_t>((v.elems + 255) / 256, 4096);
     VkResult r = launch(g.k_encode, grid, 256, 0, ep);
     if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(rgba8, g.d_srgb, sizeof(uchar4) * v.elems,
+    VCRT_TRY(hipMemcpyAsync(rgba8, g.d_srgb.data(), sizeof(uchar4) * v.elems,
                             hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     return VCRT_SUCCESS;
@@ -3647,7 +3466,7 @@ vcrt_result vcrt_shader_load(const char* filename) {
     if (!filename) return VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY;
     (void)hipStreamSynchronize(g.stream);
     const VkResult r = load_code_object(filename);
-    if (r == VK_SUCCESS && g.d_geom) g.stage.pName = select_kernel().name;
+    if (r == VK_SUCCESS && g.d_geom.data()) g.stage.pName = select_kernel().name;
     // a lens renderer cannot draw with a code object that has no lens kernels
     if (r == VK_SUCCESS && lens_on() && !lens_kernels_bound()) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     return r;
