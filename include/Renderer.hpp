@@ -42,5 +42,17 @@ VkResult DrawOcclusion(IN uint32_t first, IN uint32_t n, IN uint32_t m, IN float
 VkResult Denoise(IN const float* colour, IN const float* albedo, IN const float* normal_depth,
                  IN int32_t width, IN int32_t height, IN const vcrt_denoise_params* params,
                  OUT float* out);
+// The reprojection map of the frame's pixels (vcrt_draw_motion: where each pixel's surface lay in
+// the frame of prev_camera and prev_spheres, NULL for the current ones; host pointers in the
+// framebuffer's layout, float4 each; either plane may be NULL, not both).
+VkResult DrawMotion(IN const vcrt_camera* prev_camera, IN const vcrt_sphere* prev_spheres,
+                    IN int32_t count, OUT float* motion, OUT float* surface);
+// Temporal accumulation (vcrt_reproject: the previous output gathered through DrawMotion's map and
+// blended with the new frame; host pointers, [height][width] float4 each and float for the two
+// lengths; params NULL takes vcrt_default_reproject_params).
+VkResult Reproject(IN const float* colour, IN const float* motion, IN const float* history_colour,
+                   IN const float* history_surface, IN const float* history_length,
+                   IN int32_t width, IN int32_t height, IN const vcrt_reproject_params* params,
+                   OUT float* out, OUT float* out_length);
 
 #endif

@@ -29,8 +29,11 @@
  * a frame for a denoiser (vcrt_draw_features: first-hit albedo, normal, depth, coverage and
  * sphere id of the frame's own camera rays; vcrt_frame_rays) and its ambient visibility buffer
  * (vcrt_draw_occlusion: the open share of short rays sent from those first hits;
- * vcrt_ambient_dirs); and the denoiser those guides are for (vcrt_denoise: an edge-avoiding
- * a-trous filter over a frame and its guide planes; vcrt_denoise_host, vcrt_denoise_scales).
+ * vcrt_ambient_dirs); the denoiser those guides are for (vcrt_denoise: an edge-avoiding
+ * a-trous filter over a frame and its guide planes; vcrt_denoise_host, vcrt_denoise_scales); and
+ * temporal accumulation over a reprojection map (vcrt_draw_motion: where each pixel's surface
+ * was in the previous frame, vcrt_motion_project; vcrt_reproject: the previous output gathered
+ * there and blended with the new frame, vcrt_reproject_host).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -768,6 +771,164 @@ vcrt_result vcrt_denoise_device(const float* colour, const float* albedo,
                                 const float* normal_depth, int32_t width, int32_t height,
                                 const vcrt_denoise_params* params, float* out,
                                 vcrt_denoise_stats* stats);
+
+/* The reprojection map: where was each pixel's surface in the previous frame? vcrt_set_camera and
+ * vcrt_update_spheres restart the accumulation; this call and vcrt_reproject below carry the
+ * previous output across them. Added.
+ *
+ * For every valid local pixel (x, y) the call traces the pixel's centre ray, o = camera centre,
+ * d = corner(x, y) - centre with corner = pixel00 + x delta_u + y delta_v: no jitter, no lens
+ * offset (a jittered ray would shift a static scene's map by up to half a pixel; the map
+ * describes the pixel, not a sample; a lens renderer's map is the pinhole's). (t, s, normal) is
+ * the ray's first hit exactly as vcrt_ray_hit reports it: hit_sphere's strict <, the earliest
+ * index on ties, normal = (point - c) / r, not flipped.
+ * The previous camera, once on the host in fp32: cam' = the camera of prev_camera at the
+ * renderer's width and height, C' its centre, and
+ *   e = pixel00' - C'    nw = cross(delta_u', delta_v')    num = dot(e, nw)
+ *   nu = delta_u' / dot(delta_u', delta_u')    nv = delta_v' / dot(delta_v', delta_v')
+ * Per pixel, every fp32 operation rounded on its own, no contraction, divisions correctly
+ * rounded, dot products summed left to right (c', r': sphere s's previous centre and radius):
+ *   Q    = s >= 0 ? c' + r' * normal    per component: the product, then the sum
+ *                 : C' + d              the sky is a direction: no parallax
+ *   q    = Q - C'    den = dot(q, nw)    lam = num / den
+ *   ok   = lam > 0 && lam <= FLT_MAX    (false for a NaN)
+ *   h    = lam * q - e    px = dot(h, nu)    py = dot(h, nv)    z' = den / num
+ *   key  = (float)(s + 2)               the sky: 1
+ *   motion  = ok ? (px, py, z', key) : (0, 0, 0, 0)
+ *   surface = (key, s >= 0 ? t : 0, 0, 0)
+ * (px, py) are whole-frame pixel coordinates, pixel centres at integers (pixel00 is the centre of
+ * pixel (0, 0)); z' is the depth the previous camera would have reported for the point, in t's
+ * units (the viewport plane is at 1). vcrt_motion_project is the projection as code.
+ * Identity is exact: when prev_camera is NULL or has the current vcrt_camera's bits, and the
+ * pixel is sky or sphere s's previous centre and radius have the current bits,
+ *   motion = ((float)x, (float)y, s >= 0 ? t : 1.0f, key)
+ * so a static view of a static scene accumulates exactly.
+ *
+ * prev_spheres NULL: the current values; else count must be the scene's, and only the centres
+ * and radii are read. vcrt_draw_motion takes host pointers (the previous centres and radii go
+ * into a device table, the planes through staging planes; both kept, only grown, freed by
+ * vcrt_end); vcrt_draw_motion_device device pointers: prev_spheres the 40-byte records, 4-B
+ * aligned, the planes 16-B aligned. Either plane may be NULL, not both. Both planes are float4
+ * [elements] in the rank-local framebuffer's layout (vcrt_local_layout); slots outside the frame
+ * are left untouched; gathered planes go through vcrt_assemble_tiles as frames do. One launch of
+ * vcrt_frame_motion, one wave per local 8x8 tile; a pinhole renderer with camera-ray lists takes
+ * them (VCRT_FEATURE_LISTS=0: never; same bits). The framebuffer, the accumulation, vcrt_stats,
+ * the cost order and the frame's jitter and lens tables are left alone.
+ * Errors: VCRT_ERROR_INITIALIZATION_FAILED, before anything touches the GPU: before vcrt_begin,
+ * both planes NULL, a misaligned device pointer. VCRT_ERROR_FORMAT_NOT_SUPPORTED: prev_spheres
+ * with a count that is not the scene's, a scene of 2^24 - 2 spheres or more (the key would not
+ * be exact). VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object has no vcrt_frame_motion
+ * kernel (an A/B build of an older tree). */
+typedef struct vcrt_motion_stats {
+    uint64_t rays;         /* valid local pixels */
+    uint64_t hit_rays;     /* of them, centre rays that hit a sphere */
+    uint64_t projected;    /* pixels whose point projected (ok), identity included */
+    uint64_t identity;     /* pixels served by the identity rule */
+    uint64_t listed_rays;  /* rays answered from the camera-ray lists */
+    uint64_t group_tests;  /* as vcrt_feature_stats, per wave */
+    uint64_t bound_tests;
+    double   kernel_ms;    /* HIP events on the render stream */
+    double   host_ms;      /* wall time of the call */
+    char     kernel[48];   /* "vcrt_frame_motion" */
+} vcrt_motion_stats;
+vcrt_result vcrt_draw_motion(const vcrt_camera* prev_camera, const vcrt_sphere* prev_spheres,
+                             int32_t count, float* motion, float* surface,
+                             vcrt_motion_stats* stats);
+vcrt_result vcrt_draw_motion_device(const vcrt_camera* prev_camera,
+                                    const vcrt_sphere* prev_spheres, int32_t count, float* motion,
+                                    float* surface, vcrt_motion_stats* stats);
+/* The projection above as code (host only, no GPU): (px, py, z') of each of `count` world points
+ * through the camera prev_camera (NULL: desc's) at desc's width and height, into out [count][3];
+ * a NaN triple where the point does not project. VCRT_ERROR_INITIALIZATION_FAILED for an invalid
+ * desc, a negative count or a NULL array with count > 0. */
+vcrt_result vcrt_motion_project(const vcrt_render_desc* desc, const vcrt_camera* prev_camera,
+                                const float* points /* [count][3] */, int32_t count,
+                                float* out /* [count][3] */);
+
+/* Temporal accumulation: the previous call's output, gathered at the position each pixel's
+ * surface had in the previous frame, blended with the new frame. The denoiser above is spatial
+ * only; this is the link that lets samples outlive a camera move or a scene update. A pure image
+ * function of the caller's planes, like vcrt_denoise: a one-GPU framebuffer, or rank 0's
+ * assembled frame with the other planes put through vcrt_assemble_tiles. Added.
+ *
+ * Planes, each [height][width], row 0 at the top. float4: colour, the new frame; motion, this
+ * frame's reprojection map as vcrt_draw_motion writes it, (px, py, z, key) -- the pixel's surface
+ * lay at (px, py) of the previous frame at depth z, and key names the surface (1: the sky,
+ * s + 2: sphere s; 0: nothing to reproject); history_colour, the previous call's out;
+ * history_surface, the previous frame's surface plane (key, depth, -, -), the last two words
+ * not read; out. float: history_length, the previous call's out_length; out_length.
+ *
+ * Per pixel p with m = motion[p], W = (float)width, H = (float)height, every fp32 operation
+ * rounded on its own, no contraction, divisions correctly rounded:
+ *   if !(m.w >= 1 && m.x > -1 && m.x < W && m.y > -1 && m.y < H):   (a NaN fails)
+ *       out = colour[p], out_length = 1
+ *   fx = floorf(m.x), fy = floorf(m.y), ax = m.x - fx, ay = m.y - fy, ix = (int)fx, iy = (int)fy
+ *   the taps q = (ix + dx, iy + dy) in the order (dx, dy) = (0,0), (1,0), (0,1), (1,1):
+ *     b = (dx ? ax : 1 - ax) * (dy ? ay : 1 - ay)
+ *     skipped, nothing of q read, when b == 0 or q lies outside the frame; rejected unless
+ *       history_surface[q].x == m.w                      the same sphere, or sky on sky
+ *       history_length[q] >= 1
+ *       m.w == 1 || depth_tolerance == 0 ||              zq = history_surface[q].y
+ *         fabsf(m.z - zq) / ((fabsf(m.z) + fabsf(zq)) + 0x1p-20f) <= depth_tolerance
+ *     accepted: acc.c += b * history_colour[q].c (rgb), lsum += b * history_length[q],
+ *               wsum += b                                all from +0
+ *   if wsum > 0:
+ *       hcol.c = acc.c / wsum    L = lsum / wsum    N = fminf(L + 1, max_history)
+ *       a = fmaxf(alpha, 1 / N)
+ *       out.c = hcol.c + a * (colour.c - hcol.c)    out.a = colour.a    out_length = N
+ *   else: out = colour[p], out_length = 1
+ * While N stays below max_history and 1 / N above alpha this is the running mean of the samples
+ * seen at the surface point; from there on an exponential average. A sequence starts from a
+ * history_length plane of zeros (every tap rejected: out = colour, out_length = 1).
+ * The contract holds for finite planes; any other input is processed without a fault,
+ * deterministically, and is otherwise unspecified. No plane is read outside the frame, whatever
+ * motion holds: NaN, infinities, huge values.
+ *
+ * vcrt_reproject_host is the definition as code (host only, no GPU; csrc/reproject.cpp).
+ * vcrt_reproject takes host pointers, staged through device planes that are kept, only grown, and
+ * freed by vcrt_end; vcrt_reproject_device device pointers, the float4 planes 16-B and the float
+ * planes 4-B aligned, readable on the renderer's device. Both need vcrt_begin for the device, the
+ * stream and the code object, run one launch of vcrt_reproject_pass on the render stream -- one
+ * lane per pixel -- and return when done. They leave alone the framebuffer, the accumulation,
+ * vcrt_stats and the cost order. The planes' size need not be the renderer's.
+ * Errors: VCRT_ERROR_FORMAT_NOT_SUPPORTED, checked first, so it reads the same before vcrt_begin:
+ * a struct_size that is not sizeof(vcrt_reproject_params), a NaN parameter, alpha outside (0, 1],
+ * max_history outside 1 .. 65535, a negative depth_tolerance, width or height outside
+ * 1 .. 65535, more than 2^26 pixels. VCRT_ERROR_INITIALIZATION_FAILED, before anything touches
+ * the GPU: a NULL plane, out or out_length equal to an input pointer or to each other, a
+ * misaligned device plane, and (not vcrt_reproject_host) before vcrt_begin.
+ * VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object has no vcrt_reproject_pass kernel
+ * (an A/B build of an older tree). A NULL params takes vcrt_default_reproject_params. */
+typedef struct vcrt_reproject_params {
+    uint32_t struct_size;      /* sizeof(vcrt_reproject_params) */
+    float    alpha;            /* 0 < alpha <= 1: the least weight of the new frame */
+    float    max_history;      /* 1 .. 65535: cap of the history length */
+    float    depth_tolerance;  /* >= 0, relative; 0 = depth test off */
+} vcrt_reproject_params;
+/* The defaults: the alpha and depth_tolerance that minimise the error of eight accumulated 4-spp
+ * frames of an orbit of the final scene against the last view's 256-spp frame over a small grid
+ * (profiles/reproject_defaults.json); max_history 32. */
+vcrt_result vcrt_default_reproject_params(vcrt_reproject_params* params);
+typedef struct vcrt_reproject_stats {
+    double   kernel_ms;        /* the launch, HIP events on the render stream */
+    double   host_ms;          /* wall time of the call */
+    uint64_t accepted_pixels;  /* pixels with wsum > 0: blended with history */
+    char     kernel[48];       /* "vcrt_reproject_pass" */
+} vcrt_reproject_stats;
+vcrt_result vcrt_reproject_host(const float* colour, const float* motion,
+                                const float* history_colour, const float* history_surface,
+                                const float* history_length, int32_t width, int32_t height,
+                                const vcrt_reproject_params* params, float* out,
+                                float* out_length);
+vcrt_result vcrt_reproject(const float* colour, const float* motion, const float* history_colour,
+                           const float* history_surface, const float* history_length,
+                           int32_t width, int32_t height, const vcrt_reproject_params* params,
+                           float* out, float* out_length, vcrt_reproject_stats* stats);
+vcrt_result vcrt_reproject_device(const float* colour, const float* motion,
+                                  const float* history_colour, const float* history_surface,
+                                  const float* history_length, int32_t width, int32_t height,
+                                  const vcrt_reproject_params* params, float* out,
+                                  float* out_length, vcrt_reproject_stats* stats);
 
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file

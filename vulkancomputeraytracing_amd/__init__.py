@@ -12,7 +12,7 @@ from ._native import (VK_SUCCESS, VK_ERROR_INITIALIZATION_FAILED, VcrtError, KER
 from .renderer import (BeginRenderingOperation, DrawNextFrame, EndRenderingOperation, RAY_HIT_DTYPE,
                        Renderer, RenderDesc, SetRenderDescription, SetRenderScene, frame_rays, lens_offsets,
                        ambient_dirs, render, denoise_host, denoise_scales, default_denoise_params,
-                       tile_pixel_map,
+                       reproject_host, motion_project, default_reproject_params, tile_pixel_map,
                        tile_slots, tiles_for_rank)
 from .scene import SPHERE_DTYPE, builtin_scene, make_spheres, scene_generator_text
 
@@ -21,6 +21,7 @@ __all__ = [
     "RenderDesc", "SetRenderDescription", "SetRenderScene", "render", "tiles_for_rank",
     "tile_slots", "tile_pixel_map", "RAY_HIT_DTYPE", "lens_offsets", "frame_rays", "ambient_dirs",
     "denoise_host", "denoise_scales", "default_denoise_params",
+    "reproject_host", "motion_project", "default_reproject_params",
     "SPHERE_DTYPE", "builtin_scene", "make_spheres", "scene_generator_text", "VcrtError",
     "VK_SUCCESS", "VK_ERROR_INITIALIZATION_FAILED", "KERNEL_AUTO", "KERNEL_LDS", "KERNEL_SMEM",
     "KERNEL_CULL", "KERNEL_CULL_LANE", "KERNEL_CULL_FLAT", "TEXTURE_GLASS", "TEXTURE_LAMBERTIAN", "TEXTURE_METAL", "_native",

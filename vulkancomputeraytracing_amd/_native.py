@@ -187,6 +187,39 @@ class vcrt_denoise_stats(ctypes.Structure):
     ]
 
 
+class vcrt_motion_stats(ctypes.Structure):
+    _fields_ = [
+        ("rays", ctypes.c_uint64),
+        ("hit_rays", ctypes.c_uint64),
+        ("projected", ctypes.c_uint64),
+        ("identity", ctypes.c_uint64),
+        ("listed_rays", ctypes.c_uint64),
+        ("group_tests", ctypes.c_uint64),
+        ("bound_tests", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
+class vcrt_reproject_params(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("alpha", ctypes.c_float),
+        ("max_history", ctypes.c_float),
+        ("depth_tolerance", ctypes.c_float),
+    ]
+
+
+class vcrt_reproject_stats(ctypes.Structure):
+    _fields_ = [
+        ("kernel_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("accepted_pixels", ctypes.c_uint64),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
 class vcrt_camera_stats(ctypes.Structure):
     _fields_ = [
         ("host_ms", ctypes.c_double),
@@ -345,6 +378,25 @@ SIGNATURES = {
                                              ctypes.c_int32, ctypes.c_int32,
                                              ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p,
                                              ctypes.POINTER(vcrt_denoise_stats)]),
+    "vcrt_draw_motion": (ctypes.c_int32, [ctypes.POINTER(vcrt_camera), ctypes.c_void_p,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.POINTER(vcrt_motion_stats)]),
+    "vcrt_draw_motion_device": (ctypes.c_int32, [ctypes.POINTER(vcrt_camera), ctypes.c_void_p,
+                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.POINTER(vcrt_motion_stats)]),
+    "vcrt_motion_project": (ctypes.c_int32, [ctypes.POINTER(vcrt_render_desc),
+                                             ctypes.POINTER(vcrt_camera), ctypes.c_void_p,
+                                             ctypes.c_int32, ctypes.c_void_p]),
+    "vcrt_default_reproject_params": (ctypes.c_int32, [ctypes.POINTER(vcrt_reproject_params)]),
+    "vcrt_reproject_host": (ctypes.c_int32, [ctypes.c_void_p] * 5 + [ctypes.c_int32] * 2 +
+                            [ctypes.POINTER(vcrt_reproject_params), ctypes.c_void_p,
+                             ctypes.c_void_p]),
+    "vcrt_reproject": (ctypes.c_int32, [ctypes.c_void_p] * 5 + [ctypes.c_int32] * 2 +
+                       [ctypes.POINTER(vcrt_reproject_params), ctypes.c_void_p, ctypes.c_void_p,
+                        ctypes.POINTER(vcrt_reproject_stats)]),
+    "vcrt_reproject_device": (ctypes.c_int32, [ctypes.c_void_p] * 5 + [ctypes.c_int32] * 2 +
+                              [ctypes.POINTER(vcrt_reproject_params), ctypes.c_void_p,
+                               ctypes.c_void_p, ctypes.POINTER(vcrt_reproject_stats)]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

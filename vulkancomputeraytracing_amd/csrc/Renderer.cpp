@@ -81,3 +81,18 @@ VkResult Denoise(IN const float* colour, IN const float* albedo, IN const float*
     return static_cast<VkResult>(
         vcrt_denoise(colour, albedo, normal_depth, width, height, params, out, nullptr));
 }
+
+VkResult DrawMotion(IN const vcrt_camera* prev_camera, IN const vcrt_sphere* prev_spheres,
+                    IN int32_t count, OUT float* motion, OUT float* surface) {
+    return static_cast<VkResult>(
+        vcrt_draw_motion(prev_camera, prev_spheres, count, motion, surface, nullptr));
+}
+
+VkResult Reproject(IN const float* colour, IN const float* motion, IN const float* history_colour,
+                   IN const float* history_surface, IN const float* history_length,
+                   IN int32_t width, IN int32_t height, IN const vcrt_reproject_params* params,
+                   OUT float* out, OUT float* out_length) {
+    return static_cast<VkResult>(vcrt_reproject(colour, motion, history_colour, history_surface,
+                                                history_length, width, height, params, out,
+                                                out_length, nullptr));
+}

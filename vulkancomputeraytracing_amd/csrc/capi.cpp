@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -29,6 +30,7 @@
 #include "cluster.hpp"
 #include "comm_wait.hpp"
 #include "denoise_abi.h"
+#include "reproject_abi.h"
 #include "device_resources.hpp"
 #include "hip_status.hpp"
 #include "scene.hpp"
@@ -117,6 +119,18 @@ struct RendererState {
     DeviceBuffer<float4> d_dn_scratch[2];
     DeviceBuffer<float4> d_dn_stage[4];  // colour, albedo, guides, out
     Event ev_dn[9];
+    // the reprojection map (vcrt_draw_motion; null: the code object predates it): the host call's
+    // staging planes and its packed table of the previous centres and radii, kept and grown only;
+    // the tallies' slots are the feature buffers'
+    hipFunction_t k_frame_motion = nullptr;
+    DeviceBuffer<float4> d_mo_motion, d_mo_surface, d_mo_prev;
+    std::vector<float4> h_mo_prev;
+    // temporal accumulation (vcrt_reproject; null: the code object predates it): the host call's
+    // staging planes and the tally slots; kept and grown only
+    hipFunction_t k_reproject_pass = nullptr;
+    DeviceBuffer<float4> d_rp_stage[5];  // colour, motion, history colour, history surface, out
+    DeviceBuffer<float> d_rp_length[2];  // history length, out length
+    DeviceBuffer<unsigned long long> d_rp_counters;
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -695,6 +709,8 @@ constexpr KernelRow kKernels[] = {
     // the denoise kernels, both or neither
     {&RS::k_denoise_pass, "vcrt_denoise_pass", 16},
     {&RS::k_denoise_pass_lds, "vcrt_denoise_pass_lds", 16},
+    {&RS::k_reproject_pass, "vcrt_reproject_pass", 25},
+    {&RS::k_frame_motion, "vcrt_frame_motion", 26},
     // the camera-list kernels, each on its own (vcrt_set_camera asks for all four, else it runs
     // the host builders)
     {&RS::k_cl_prepare, "vcrt_camlist_prepare", 17},
@@ -2646,6 +2662,166 @@ vcrt_result vcrt_draw_occlusion(uint32_t first, uint32_t n, uint32_t m, float re
     return VCRT_SUCCESS;
 }
 
+// ---- the reprojection map ---------------------------------------------------------------------
+
+namespace {
+
+constexpr int64_t kMotionMaxSpheres = (int64_t{1} << 24) - 2;  // key = (float)(s + 2) stays exact
+
+vcrt::Camera camera_of(int32_t width, int32_t height, const vcrt_camera& c) {
+    return vcrt::make_camera(width, height, vcrt::mk(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]),
+                             vcrt::mk(c.lookat[0], c.lookat[1], c.lookat[2]),
+                             vcrt::mk(c.vup[0], c.vup[1], c.vup[2]), c.vfov,
+                             [](double x) { return std::tan(x); });
+}
+
+// The arguments both forms of the call check, before anything touches the GPU.
+vcrt_result motion_args(const vcrt_sphere* prev_spheres, int32_t count, const void* motion,
+                        const void* surface) {
+    if (!motion && !surface) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if ((prev_spheres && count != g.nspheres) || g.nspheres >= kMotionMaxSpheres)
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    return VCRT_SUCCESS;
+}
+
+// The launch on device pointers (checked by the callers): one wave per local tile; returns when
+// the kernel is done. prev: null (the current values), else `stride` floats a sphere.
+VkResult draw_motion_device(const vcrt_camera* prev_camera, const float* prev, uint32_t stride,
+                            float* motion, float* surface, vcrt_motion_stats* stats) {
+    if (stats) {
+        *stats = vcrt_motion_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_motion");
+    }
+    vcrt::MotionParams p{};
+    frame_ray_scene(p.scene, 1);
+    p.scene.jitter = nullptr;  // the centre ray has no jitter and no lens offset
+    p.scene.lens = nullptr;
+    p.motion = reinterpret_cast<float4*>(motion);
+    p.surface = reinterpret_cast<float4*>(surface);
+    p.prev = prev ? prev : reinterpret_cast<const float*>(g.d_center_radius.data());
+    p.prev_stride = prev ? stride : 4u;
+    p.same_camera =
+        !prev_camera || std::memcmp(prev_camera, &g.desc.camera, sizeof(vcrt_camera)) == 0;
+    // (a lens renderer has no lists: its rays do not share an origin)
+    p.use_lists = g.feature_lists && !lens_on() ? 1u : 0u;
+    const vcrt::MotionCamera mc = vcrt::motion_camera(
+        p.same_camera ? g.cam : camera_of(g.desc.width, g.desc.height, *prev_camera));
+    const vcrt::f3 v[5] = {mc.center, mc.e, mc.nw, mc.nu, mc.nv};
+    for (int i = 0; i < 5; i++) {
+        p.prev_cam[3 * i + 0] = v[i].x;
+        p.prev_cam[3 * i + 1] = v[i].y;
+        p.prev_cam[3 * i + 2] = v[i].z;
+    }
+    p.prev_cam[15] = mc.num;
+    unsigned long long slots[kFeatureCounterWords] = {};
+    float ms = 0.f;
+    const VkResult r = frame_ray_launch(g.k_frame_motion, p, stats ? slots : nullptr, &ms);
+    if (r != VK_SUCCESS) return r;
+    if (stats) {
+        unsigned long long counters[6] = {0, 0, 0, 0, 0, 0};
+        for (size_t s = 0; s < kFeatureCounterWords; s += 8)
+            for (int c = 0; c < 6; c++) counters[c] += slots[s + c];
+        stats->kernel_ms = ms;
+        stats->rays = g.local_pixels;
+        stats->hit_rays = counters[3];
+        stats->projected = counters[4];
+        stats->identity = counters[5];
+        stats->listed_rays = counters[0];
+        stats->group_tests = counters[1];
+        stats->bound_tests = counters[2];
+    }
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_draw_motion_device(const vcrt_camera* prev_camera,
+                                    const vcrt_sphere* prev_spheres, int32_t count, float* motion,
+                                    float* surface, vcrt_motion_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = motion_args(prev_spheres, count, motion, surface);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernel's 16-byte stores and its 4-byte loads of the records
+    if (((reinterpret_cast<uintptr_t>(motion) | reinterpret_cast<uintptr_t>(surface)) & 15u) ||
+        (reinterpret_cast<uintptr_t>(prev_spheres) & 3u))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_frame_motion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    static_assert(sizeof(vcrt_sphere) == 40 && offsetof(vcrt_sphere, radius) == 12,
+                  "the kernel reads centre and radius at the head of a 10-float record");
+    const VkResult r = draw_motion_device(prev_camera, reinterpret_cast<const float*>(prev_spheres),
+                                          10u, motion, surface, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_draw_motion(const vcrt_camera* prev_camera, const vcrt_sphere* prev_spheres,
+                             int32_t count, float* motion, float* surface,
+                             vcrt_motion_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = motion_args(prev_spheres, count, motion, surface);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.k_frame_motion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t elems = g.local_elems;
+    if (motion) VCRT_TRY(g.d_mo_motion.reserve(elems));
+    if (surface) VCRT_TRY(g.d_mo_surface.reserve(elems));
+    // packed tiles: the slots outside the frame keep what the caller's planes hold
+    if (g.desc.world_size > 1 && elems) {
+        if (motion)
+            VCRT_TRY(hipMemcpyAsync(g.d_mo_motion.data(), motion, sizeof(float4) * elems,
+                                    hipMemcpyHostToDevice, g.stream));
+        if (surface)
+            VCRT_TRY(hipMemcpyAsync(g.d_mo_surface.data(), surface, sizeof(float4) * elems,
+                                    hipMemcpyHostToDevice, g.stream));
+    }
+    // the previous centres and radii, packed
+    const float* prev = nullptr;
+    if (prev_spheres && count > 0) {
+        VCRT_TRY(g.d_mo_prev.reserve(static_cast<size_t>(count)));
+        g.h_mo_prev.resize(static_cast<size_t>(count));
+        for (int32_t s = 0; s < count; s++)
+            g.h_mo_prev[s] = make_float4(prev_spheres[s].center[0], prev_spheres[s].center[1],
+                                         prev_spheres[s].center[2], prev_spheres[s].radius);
+        VCRT_TRY(hipMemcpyAsync(g.d_mo_prev.data(), g.h_mo_prev.data(), sizeof(float4) * count,
+                                hipMemcpyHostToDevice, g.stream));
+        prev = reinterpret_cast<const float*>(g.d_mo_prev.data());
+    }
+    const VkResult r = draw_motion_device(
+        prev_camera, prev, 4u, motion ? reinterpret_cast<float*>(g.d_mo_motion.data()) : nullptr,
+        surface ? reinterpret_cast<float*>(g.d_mo_surface.data()) : nullptr, stats);
+    if (r != VK_SUCCESS) return r;
+    if (elems) {
+        if (motion)
+            VCRT_TRY(hipMemcpyAsync(motion, g.d_mo_motion.data(), sizeof(float4) * elems,
+                                    hipMemcpyDeviceToHost, g.stream));
+        if (surface)
+            VCRT_TRY(hipMemcpyAsync(surface, g.d_mo_surface.data(), sizeof(float4) * elems,
+                                    hipMemcpyDeviceToHost, g.stream));
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+    }
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+vcrt_result vcrt_motion_project(const vcrt_render_desc* desc, const vcrt_camera* prev_camera,
+                                const float* points, int32_t count, float* out) {
+    vcrt_render_desc dv;
+    if (!read_desc(desc, dv) || !desc_valid(dv) || count < 0 || (count > 0 && (!points || !out)))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    const vcrt::MotionCamera mc =
+        vcrt::motion_camera(camera_of(dv.width, dv.height, prev_camera ? *prev_camera : dv.camera));
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (int32_t i = 0; i < count; i++) {
+        const vcrt::f3 Q = vcrt::mk(points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+        vcrt::f3 r = vcrt::mk(nan, nan, nan);
+        vcrt::motion_project(mc, vcrt::sub(Q, mc.center), &r);
+        out[3 * i] = r.x;
+        out[3 * i + 1] = r.y;
+        out[3 * i + 2] = r.z;
+    }
+    return VCRT_SUCCESS;
+}
+
 // ---- the denoiser -----------------------------------------------------------------------------
 
 namespace {
@@ -2786,6 +2962,121 @@ vcrt_result vcrt_denoise(const float* colour, const float* albedo, const float* 
                                       reinterpret_cast<float*>(g.d_dn_stage[3].data()), stats);
     if (r != VK_SUCCESS) return r;
     VCRT_TRY(hipMemcpyAsync(out, g.d_dn_stage[3].data(), sizeof(float4) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+// ---- temporal accumulation ---------------------------------------------------------------------
+
+namespace {
+
+constexpr size_t kReprojectCounterWords = 8 * vcrt::kReprojectTallySlots;  // u64
+
+// The launch on device planes (checked by the callers); returns when it is done.
+VkResult reproject_device(const float* colour, const float* motion, const float* history_colour,
+                          const float* history_surface, const float* history_length,
+                          int32_t width, int32_t height, const vcrt_reproject_params& pr,
+                          float* out, float* out_length, vcrt_reproject_stats* stats) {
+    vcrt::ReprojectParams p{};
+    p.colour = colour;
+    p.motion = motion;
+    p.history_colour = history_colour;
+    p.history_surface = history_surface;
+    p.history_length = history_length;
+    p.out = out;
+    p.out_length = out_length;
+    p.width = static_cast<uint32_t>(width);
+    p.height = static_cast<uint32_t>(height);
+    p.alpha = pr.alpha;
+    p.max_history = pr.max_history;
+    p.depth_tolerance = pr.depth_tolerance;
+    p.tiles_x = (p.width + vcrt::kReprojectRowW - 1u) / vcrt::kReprojectRowW;
+    const uint32_t tiles_y = (p.height + vcrt::kReprojectRowH - 1u) / vcrt::kReprojectRowH;
+    if (!stats) {  // nothing to count or time
+        const VkResult r = launch(g.k_reproject_pass, p.tiles_x * tiles_y,
+                                  vcrt::kReprojectThreads, 0, p);
+        if (r != VK_SUCCESS) return r;
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+        return VK_SUCCESS;
+    }
+    std::vector<unsigned long long> slots(kReprojectCounterWords);
+    float ms = 0.f;
+    const VkResult r = timed_launch(
+        g.k_reproject_pass, p.tiles_x * tiles_y, vcrt::kReprojectThreads, p, g.d_rp_counters,
+        kReprojectCounterWords, [&p](unsigned long long* c) { p.tallies = c; }, slots.data(), &ms);
+    if (r != VK_SUCCESS) return r;
+    *stats = vcrt_reproject_stats{};
+    std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_reproject_pass");
+    stats->kernel_ms = ms;
+    for (size_t s = 0; s < vcrt::kReprojectTallySlots; s++)
+        stats->accepted_pixels += slots[8 * s];
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_reproject_device(const float* colour, const float* motion,
+                                  const float* history_colour, const float* history_surface,
+                                  const float* history_length, int32_t width, int32_t height,
+                                  const vcrt_reproject_params* params, float* out,
+                                  float* out_length, vcrt_reproject_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_reproject_params pr;
+    const vcrt_result a = vcrt::reproject_args(colour, motion, history_colour, history_surface,
+                                               history_length, width, height, params, out,
+                                               out_length, &pr);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernel's 16-byte loads and stores of the float4 planes, 4-byte ones of the lengths
+    if ((reinterpret_cast<uintptr_t>(colour) | reinterpret_cast<uintptr_t>(motion) |
+         reinterpret_cast<uintptr_t>(history_colour) |
+         reinterpret_cast<uintptr_t>(history_surface) | reinterpret_cast<uintptr_t>(out)) & 15u)
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if ((reinterpret_cast<uintptr_t>(history_length) | reinterpret_cast<uintptr_t>(out_length)) &
+        3u)
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_reproject_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = reproject_device(colour, motion, history_colour, history_surface,
+                                        history_length, width, height, pr, out, out_length,
+                                        stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_reproject(const float* colour, const float* motion, const float* history_colour,
+                           const float* history_surface, const float* history_length,
+                           int32_t width, int32_t height, const vcrt_reproject_params* params,
+                           float* out, float* out_length, vcrt_reproject_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_reproject_params pr;
+    const vcrt_result a = vcrt::reproject_args(colour, motion, history_colour, history_surface,
+                                               history_length, width, height, params, out,
+                                               out_length, &pr);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_reproject_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const float* host[4] = {colour, motion, history_colour, history_surface};
+    for (int k = 0; k < 5; k++) VCRT_TRY(g.d_rp_stage[k].reserve(pixels));
+    for (int k = 0; k < 2; k++) VCRT_TRY(g.d_rp_length[k].reserve(pixels));
+    for (int k = 0; k < 4; k++)
+        VCRT_TRY(hipMemcpyAsync(g.d_rp_stage[k].data(), host[k], sizeof(float4) * pixels,
+                                hipMemcpyHostToDevice, g.stream));
+    VCRT_TRY(hipMemcpyAsync(g.d_rp_length[0].data(), history_length, sizeof(float) * pixels,
+                            hipMemcpyHostToDevice, g.stream));
+    const auto plane = [](const DeviceBuffer<float4>& b) {
+        return reinterpret_cast<float*>(b.data());
+    };
+    const VkResult r = reproject_device(plane(g.d_rp_stage[0]), plane(g.d_rp_stage[1]),
+                                        plane(g.d_rp_stage[2]), plane(g.d_rp_stage[3]),
+                                        g.d_rp_length[0].data(), width, height, pr,
+                                        plane(g.d_rp_stage[4]), g.d_rp_length[1].data(), stats);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(out, g.d_rp_stage[4].data(), sizeof(float4) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipMemcpyAsync(out_length, g.d_rp_length[1].data(), sizeof(float) * pixels,
                             hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) stats->host_ms = ms_since(t0);

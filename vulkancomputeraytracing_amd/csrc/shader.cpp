@@ -37,8 +37,12 @@ VkResult CreateShaderStageFromFile(IN const char* filename, IN VkShaderStageFlag
         err = hipModuleLoadData(&module, data.data());
     }
     if (err == hipErrorInvalidImage || err == hipErrorNoBinaryForGpu ||
-        err == hipErrorInvalidKernelFile || err == hipErrorSharedObjectInitFailed)
+        err == hipErrorInvalidKernelFile || err == hipErrorSharedObjectInitFailed) {
+        // the refusal is this function's result: HIP's record of it is cleared, or the next
+        // launch check of whoever shares the runtime (a torch kernel) reports it as its own
+        (void)hipGetLastError();
         return VK_ERROR_INCOMPATIBLE_SHADER_BINARY_EXT;
+    }
     if (err != hipSuccess) return vcrt::to_vk(err);
     info->sType = 18;  // VK_STRUCTURE_TYPE_PIPELINE_SHADER_STAGE_CREATE_INFO
     info->stage = stage;

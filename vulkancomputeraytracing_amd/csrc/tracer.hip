@@ -4039,7 +4039,7 @@ extern "C" __global__ __launch_bounds__(1024) void vcrt_trace_cull_flat_boxes_le
 //  * else what vcrt_trace_rays runs: the per-lane culled scan on the global tables when the
 //    scene has them and every ray the wave's remaining lanes hold is in the guarded range,
 //  * else the linear scan.
-#if !defined(VCRT_PART) || VCRT_PART == 10
+#if !defined(VCRT_PART) || VCRT_PART == 10 || VCRT_PART == 12
 namespace {
 
 // The first hit of one sample's camera ray (o, d), aa = dot(d, d), by the three routes above, as
@@ -4361,6 +4361,122 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_frame_occlusion(
         if (wb) atomicAdd(slot + 2, wb);
         if (nh) atomicAdd(slot + 3, nh);
         if (nb) atomicAdd(slot + 4, nb);
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// The reprojection map (vcrt_draw_motion), a code-generation unit of its own (Makefile, part 12):
+// the feature kernel's shape -- one wave per local 8x8 tile, one lane per slot -- for one ray per
+// pixel, the centre ray (corner - camera centre: no jitter, no lens offset, so a lens renderer's
+// map is the pinhole's; it takes no list, its lists do not exist). The first hit goes through
+// frame_first_hit; the centre ray lies inside its quarter's footprint, so a pinhole frame's lists
+// serve it. The hit's normal is the feature kernel's; the point the sphere's previous centre and
+// radius put it at, or for the sky the ray's own direction from the previous centre, goes through
+// motion_project (vcrt_math.h). Identity -- the same camera and a sphere whose previous centre and
+// radius have the current bits, or the sky -- is written as such, not computed: (x, y, t or 1).
+#if !defined(VCRT_PART) || VCRT_PART == 12
+extern "C" __global__ __launch_bounds__(256) void vcrt_frame_motion(MotionParams p_arg) {
+    // the arguments through a pointer to the kernarg segment, as trace_impl reads them
+    (void)p_arg;
+    const MotionParams& p = *reinterpret_cast<const MotionParams*>(
+        (__attribute__((address_space(4))) const MotionParams*)
+            __builtin_amdgcn_kernarg_segment_ptr());
+    const TraceParams& S = p.scene;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lt = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (lt >= S.local_tiles) return;  // (the whole wave)
+    const uint32_t q = lt * 64u + lane;
+    const Pixel px = pixel_of(q, (uint32_t)S.width, (uint32_t)S.height, S.tiles_x,
+                              (uint32_t)S.world, (uint32_t)S.rank);
+    const bool lens = S.lens != nullptr;
+    uint32_t w_halves = 0u, w_bounds = 0u, listed = 0u, hits = 0u, projected = 0u, same = 0u;
+    if (px.valid) {
+        const f3 p00 = mk(S.cam[0], S.cam[1], S.cam[2]);
+        const f3 du = mk(S.cam[3], S.cam[4], S.cam[5]);
+        const f3 dv = mk(S.cam[6], S.cam[7], S.cam[8]);
+        const f3 cam = mk(S.cam[9], S.cam[10], S.cam[11]);
+        const f3 corner = viewport_corner(p00, du, dv, px.x, px.y);
+        // the sphere list of the lane's 4x4 quarter (slot 8 y + x), as trace_impl reads it
+        uint32_t inf = 15u;
+        if (p.use_lists != 0u && !lens && S.prim_info != nullptr)
+            inf = S.prim_info[2u * (lt * 4u + (((lane >> 5) & 1u) << 1) + ((lane >> 2) & 1u)) + 1u];
+        const int n = S.nspheres;
+        const float4* tgroup = S.cgroup + 5 * S.nbig;  // the hierarchy's group records
+        const f3 o = cam;
+        const f3 d = sub(corner, o);
+        const float aa = dot(d, d);
+        float max_t = kInfinity;
+        int best = -1;
+        frame_first_hit(S, inf, tgroup, n, o, d, aa, max_t, best, listed, w_halves, w_bounds);
+        const bool hit = best >= 0;
+        if (hit) ++hits;
+        MotionCamera mc;
+        mc.center = mk(p.prev_cam[0], p.prev_cam[1], p.prev_cam[2]);
+        mc.e = mk(p.prev_cam[3], p.prev_cam[4], p.prev_cam[5]);
+        mc.nw = mk(p.prev_cam[6], p.prev_cam[7], p.prev_cam[8]);
+        mc.nu = mk(p.prev_cam[9], p.prev_cam[10], p.prev_cam[11]);
+        mc.nv = mk(p.prev_cam[12], p.prev_cam[13], p.prev_cam[14]);
+        mc.num = p.prev_cam[15];
+        const float key = (float)(best + 2);
+        bool identity = p.same_camera != 0u;
+        f3 Q = add(mc.center, d);  // the sky is a direction: no parallax
+        if (hit) {
+            const float4 cr = S.center_radius[best];
+            const float* pr = p.prev + (size_t)p.prev_stride * (uint32_t)best;
+            const float pcx = pr[0], pcy = pr[1], pcz = pr[2], prr = pr[3];
+            identity = identity && __float_as_uint(pcx) == __float_as_uint(cr.x) &&
+                       __float_as_uint(pcy) == __float_as_uint(cr.y) &&
+                       __float_as_uint(pcz) == __float_as_uint(cr.z) &&
+                       __float_as_uint(prr) == __float_as_uint(cr.w);
+            const f3 point = add(scale(max_t, d), o);
+            // shade_segment's normal: the unscaled division, else the full one (same bits)
+            const f3 pcv = sub(point, mk(cr.x, cr.y, cr.z));
+            const float yr = recip_a(cr.w);
+            f3 normal = mk(div_a(pcv.x, cr.w, yr), div_a(pcv.y, cr.w, yr), div_a(pcv.z, cr.w, yr));
+            const float nmin = fminf(fminf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+            const float nmax = fmaxf(fmaxf(fabsf(pcv.x), fabsf(pcv.y)), fabsf(pcv.z));
+            if (!((S.flags & kFlagRadiiSafe) != 0u && nmin >= 0x1p-40f && nmax <= 0x1p30f)) {
+                asm volatile("");
+                normal = divs(pcv, cr.w);
+            }
+            Q = add(mk(pcx, pcy, pcz), scale(prr, normal));
+        }
+        float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (identity) {
+            m = make_float4((float)px.x, (float)px.y, hit ? max_t : 1.0f, key);
+            ++same;
+            ++projected;
+        } else {
+            f3 r;
+            if (motion_project(mc, sub(Q, mc.center), &r)) {
+                m = make_float4(r.x, r.y, r.z, key);
+                ++projected;
+            }
+        }
+        if (p.motion) p.motion[px.out_index] = m;
+        if (p.surface) p.surface[px.out_index] = make_float4(key, hit ? max_t : 0.0f, 0.f, 0.f);
+    }
+    // one atomic per wave and tally, into the block's slot (MotionParams.tallies)
+    unsigned long long nl = listed, wh = w_halves, wb = w_bounds, nh = hits, np = projected,
+                       ni = same;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nl += __shfl_xor(nl, off);
+        wh += __shfl_xor(wh, off);
+        wb += __shfl_xor(wb, off);
+        nh += __shfl_xor(nh, off);
+        np += __shfl_xor(np, off);
+        ni += __shfl_xor(ni, off);
+    }
+    if (lane == 0) {
+        unsigned long long* slot = p.tallies + 8u * (blockIdx.x & (kFeatureTallySlots - 1u));
+        if (nl) atomicAdd(slot + 0, nl);
+        if (wh) atomicAdd(slot + 1, wh / 2u);
+        if (wb) atomicAdd(slot + 2, wb);
+        if (nh) atomicAdd(slot + 3, nh);
+        if (np) atomicAdd(slot + 4, np);
+        if (ni) atomicAdd(slot + 5, ni);
     }
 }
 #endif

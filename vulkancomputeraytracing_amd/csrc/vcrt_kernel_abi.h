@@ -303,6 +303,29 @@ struct OcclusionBufferParams {
                                   //   occluded; zeroed before the launch, summed by the host
 };
 
+// The reprojection map (vcrt_draw_motion): the first hit of each pixel's centre ray as the feature
+// kernel finds it, carried to where the sphere was (prev) and projected through the previous
+// camera (vcrt_math.h MotionCamera, computed once on the host). The scene block is filled as
+// FeatureParams' is; the jitter and lens tables are not read (the centre ray has neither). One
+// wave per local tile, one lane per slot.
+struct MotionParams {
+    TraceParams scene;
+    float4* motion;        // [elements] (px, py, z', key), zeros when the point does not project;
+                           //   or null
+    float4* surface;       // [elements] (key, t or 0, 0, 0), or null
+    const float* prev;     // the previous (centre.xyz, radius) of sphere s at prev + prev_stride s:
+                           //   scene.center_radius (stride 4), the host call's packed table
+                           //   (stride 4) or the caller's vcrt_sphere records (stride 10)
+    uint32_t prev_stride;  // in floats
+    uint32_t same_camera;  // 1: the previous camera is the current one (the identity rule applies)
+    uint32_t use_lists;    // as FeatureParams.use_lists
+    float prev_cam[16];    // C' (0..2), e (3..5), nw (6..8), nu (9..11), nv (12..14), num (15)
+    unsigned long long* tallies;  // [kFeatureTallySlots][8]: per slot (64 B), [0] .. [2] as
+                                  //   FeatureParams.tallies, [3] rays that hit, [4] pixels that
+                                  //   projected (ok), [5] pixels served by the identity rule;
+                                  //   zeroed before the launch, summed by the host
+};
+
 // TraceParams.jitter from the host's jitter (vcrt_math.h rand2) and the camera: run at
 // vcrt_begin and for each progressive frame.
 struct SetupJitterParams {

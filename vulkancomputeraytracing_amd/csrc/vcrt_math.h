@@ -608,6 +608,41 @@ inline Camera make_camera(int width, int height, f3 lookfrom, f3 lookat, f3 vup,
 }
 
 // ---------------------------------------------------------------------------------------
+// The reprojection map (vcrt.h vcrt_draw_motion): a world point Q seen through the previous
+// camera. The five vectors and num are computed once on the host from that camera; the projection
+// is one fixed sequence of fp32 operations, the host helper's (vcrt_motion_project) and the
+// kernel's (tracer.hip vcrt_frame_motion).
+struct MotionCamera {
+    f3 center;  // C'
+    f3 e;       // pixel00' - C'
+    f3 nw;      // cross(delta_u', delta_v'): the viewport plane's normal
+    f3 nu, nv;  // delta_u' / |delta_u'|^2, delta_v' / |delta_v'|^2
+    float num;  // dot(e, nw)
+};
+
+inline MotionCamera motion_camera(const Camera& c) {
+    MotionCamera m;
+    m.center = c.center;
+    m.e = sub(c.pixel00, c.center);
+    m.nw = cross(c.delta_u, c.delta_v);
+    m.nu = divs(c.delta_u, dot(c.delta_u, c.delta_u));
+    m.nv = divs(c.delta_v, dot(c.delta_v, c.delta_v));
+    m.num = dot(m.e, m.nw);
+    return m;
+}
+
+// (px, py, z') of q = Q - C'; false when the point does not project (behind the camera, on its
+// plane, or a NaN), and then out is not written.
+VCRT_HD bool motion_project(const MotionCamera& m, f3 q, f3* out) {
+    const float den = dot(q, m.nw);
+    const float lam = m.num / den;
+    if (!(lam > 0.0f && lam <= 3.4028234663852886e38f)) return false;
+    const f3 h = sub(scale(lam, q), m.e);
+    *out = mk(dot(h, m.nu), dot(h, m.nv), den / m.num);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------
 // Thin lens (vcrt.h lens_radius; the reference has a pinhole only). The viewport lies in the
 // plane through lookat (focal_length = |lookfrom - lookat|), so that plane is in focus and a lens
 // only moves each sample's ray origin: sample index i starts at center + lens_offset(i, R, u, v),

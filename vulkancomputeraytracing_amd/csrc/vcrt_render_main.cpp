@@ -6,6 +6,9 @@
 // PREFIX its ambient visibility buffer (vcrt_draw_occlusion) as PREFIX_ao.ppm, sRGB8 as a frame.
 // --denoise FILE writes the last frame put through the denoiser (vcrt_denoise over the framebuffer
 // and the guide buffers of --feature-samples samples), PFM or PPM by FILE's suffix as --out.
+// --temporal FILE accumulates the frames of an --orbit: every frame after the first is put through
+// vcrt_reproject with the previous output as its history and the map of vcrt_draw_motion for the
+// previous frame's camera; FILE receives the last accumulated frame, and --denoise then filters it.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -25,7 +28,8 @@ int usage() {
                  "[--scene final|three|red|stress4096] [--frames F] [--progressive 0|1] [--device I] "
                  "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm] "
                  "[--features PREFIX] [--feature-samples N] [--ao PREFIX] [--ao-rays M] "
-                 "[--denoise file.ppm|file.pfm] [--denoise-levels L]\n");
+                 "[--denoise file.ppm|file.pfm] [--denoise-levels L] "
+                 "[--temporal file.ppm|file.pfm]\n");
     return 2;
 }
 
@@ -56,7 +60,7 @@ int main(int argc, char** argv) {
     vcrt_default_desc(&desc);
     int scene = VCRT_SCENE_FINAL, frames = 1;
     double orbit = 0.0;  // degrees about the world y axis through lookat, per frame
-    std::string out, features, ao, denoise;
+    std::string out, features, ao, denoise, temporal;
     int denoise_levels = 0;   // 0: vcrt_default_denoise_params'
     int feature_samples = 0;  // 0: the description's spp
     int ao_rays = 8;          // secondary rays per sample that hits
@@ -67,7 +71,8 @@ int main(int argc, char** argv) {
         const char* v = argv[++i];
         configured = configured || (a != "--out" && a != "--frames" && a != "--features" &&
                                     a != "--feature-samples" && a != "--ao" && a != "--ao-rays" &&
-                                    a != "--denoise" && a != "--denoise-levels");
+                                    a != "--denoise" && a != "--denoise-levels" &&
+                                    a != "--temporal");
         if (a == "--width") desc.width = std::atoi(v);
         else if (a == "--height") desc.height = std::atoi(v);
         else if (a == "--spp") desc.samples_per_pixel = std::atoi(v);
@@ -84,6 +89,7 @@ int main(int argc, char** argv) {
         else if (a == "--ao-rays") ao_rays = std::atoi(v);
         else if (a == "--denoise") denoise = v;
         else if (a == "--denoise-levels") denoise_levels = std::atoi(v);
+        else if (a == "--temporal") temporal = v;
         else if (a == "--scene") {
             const std::string s = v;
             scene = s == "final" ? VCRT_SCENE_FINAL : s == "three" ? VCRT_SCENE_THREE
@@ -107,7 +113,18 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "BeginRenderingOperation: %s\n", vcrt_result_string(r));
         return 1;
     }
+    // --temporal: the accumulated output, this frame's planes and the previous frame's
+    const size_t pixels = static_cast<size_t>(desc.width) * desc.height;
+    std::vector<float> acc, acc_len, next, next_len, colour, motion, surface, prev_surface;
+    if (!temporal.empty()) {
+        for (std::vector<float>* v : {&acc, &next, &colour, &motion, &surface, &prev_surface})
+            v->assign(4 * pixels, 0.0f);
+        acc_len.assign(pixels, 0.0f);
+        next_len.assign(pixels, 0.0f);
+    }
+    vcrt_camera prev_cam = desc.camera;
     for (int f = 0; f < frames && r == VK_SUCCESS; f++) {
+        vcrt_camera now_cam = f == 0 ? desc.camera : prev_cam;
         if (f >= 1 && orbit != 0.0) {
             // frame f looks from the command line's lookfrom turned by f * DEG about the y axis
             // through lookat (in double, rounded to float); the move rebuilds the lists on the GPU
@@ -120,6 +137,7 @@ int main(int argc, char** argv) {
             cam.lookfrom[2] = static_cast<float>(desc.camera.lookat[2] - dx * std::sin(th) +
                                                  dz * std::cos(th));
             if ((r = SetRenderCamera(&cam)) != VK_SUCCESS) break;
+            now_cam = cam;
         }
         r = DrawNextFrame();
         vcrt_stats st;
@@ -128,6 +146,42 @@ int main(int argc, char** argv) {
         std::printf("frame %d: %s  %.3f ms (kernel %.3f ms)  %.2f Msamples/s  %llu segments\n",
                     f, vcrt_result_string(r), st.frame_ms, st.kernel_ms, msps,
                     static_cast<unsigned long long>(st.segments));
+        if (r == VK_SUCCESS && !temporal.empty()) {
+            // frame 0 starts the sequence (out = frame, every length 1); a later frame gathers
+            // the previous output where the previous camera saw its surfaces
+            r = ReadFramebuffer(colour.data(), colour.size());
+            if (r == VK_SUCCESS)
+                r = DrawMotion(f == 0 ? nullptr : &prev_cam, nullptr, 0, motion.data(),
+                               surface.data());
+            if (r == VK_SUCCESS && f == 0) {
+                acc = colour;
+                acc_len.assign(pixels, 1.0f);
+            } else if (r == VK_SUCCESS) {
+                r = Reproject(colour.data(), motion.data(), acc.data(), prev_surface.data(),
+                              acc_len.data(), desc.width, desc.height, nullptr, next.data(),
+                              next_len.data());
+                acc.swap(next);
+                acc_len.swap(next_len);
+            }
+            prev_surface = surface;
+            if (r != VK_SUCCESS) std::fprintf(stderr, "temporal: %s\n", vcrt_result_string(r));
+        }
+        prev_cam = now_cam;
+    }
+    if (r == VK_SUCCESS && !temporal.empty()) {
+        const bool pfm =
+            temporal.size() > 4 && temporal.compare(temporal.size() - 4, 4, ".pfm") == 0;
+        std::vector<uint8_t> c8(pfm ? 0 : 4 * pixels);
+        if (!pfm) {
+            float th[255];
+            vcrt_srgb8_thresholds(th);
+            for (size_t i = 0; i < 4 * pixels; i++)
+                c8[i] = static_cast<uint8_t>(std::upper_bound(th, th + 255, acc[i]) - th);
+        }
+        if (!write_image(temporal, desc.width, desc.height, pfm, acc, c8)) {
+            std::fprintf(stderr, "cannot write %s: %s\n", temporal.c_str(), std::strerror(errno));
+            r = VK_ERROR_UNKNOWN;
+        }
     }
     if (r == VK_SUCCESS && !out.empty()) {
         const bool pfm = out.size() > 4 && out.compare(out.size() - 4, 4, ".pfm") == 0;
@@ -193,8 +247,9 @@ int main(int argc, char** argv) {
         }
     }
     if (r == VK_SUCCESS && !denoise.empty()) {
-        // the last frame through the a-trous filter, steered by its own guide buffers; a PPM is
-        // encoded as a frame's is: byte = the number of sRGB8 thresholds the channel reaches
+        // the last frame (with --temporal: the accumulated one) through the a-trous filter,
+        // steered by its own guide buffers; a PPM is encoded as a frame's is: byte = the number
+        // of sRGB8 thresholds the channel reaches
         const bool pfm = denoise.size() > 4 && denoise.compare(denoise.size() - 4, 4, ".pfm") == 0;
         const size_t n = static_cast<size_t>(desc.width) * desc.height;
         const uint32_t samples = static_cast<uint32_t>(
@@ -203,7 +258,8 @@ int main(int argc, char** argv) {
         vcrt_denoise_params dp;
         vcrt_default_denoise_params(&dp);
         if (denoise_levels != 0) dp.levels = denoise_levels;
-        r = ReadFramebuffer(frame.data(), frame.size());
+        if (temporal.empty()) r = ReadFramebuffer(frame.data(), frame.size());
+        else frame = acc;  // the accumulated frame
         if (r == VK_SUCCESS) r = DrawFeatures(0, samples, albedo.data(), normal.data(), nullptr);
         if (r == VK_SUCCESS)
             r = Denoise(frame.data(), albedo.data(), normal.data(), desc.width, desc.height, &dp,

@@ -262,6 +262,123 @@ def denoise_host(colour, albedo=None, normal_depth=None, **params) -> np.ndarray
     return out
 
 
+REPROJECT_FIELDS = ("alpha", "max_history", "depth_tolerance")
+
+
+def default_reproject_params() -> dict:
+    """vcrt_default_reproject_params as a dict: alpha, max_history, depth_tolerance."""
+    p = N.vcrt_reproject_params()
+    N.check("vcrt_default_reproject_params",
+            N.lib().vcrt_default_reproject_params(ctypes.byref(p)))
+    return {f: getattr(p, f) for f in REPROJECT_FIELDS}
+
+
+def _reproject_params(given: dict) -> N.vcrt_reproject_params:
+    """The C parameter block: the defaults with the fields `given` names (None: the default)."""
+    unknown = set(given) - set(REPROJECT_FIELDS)
+    if unknown:
+        raise TypeError(f"reproject: unexpected parameters {sorted(unknown)}")
+    p = N.vcrt_reproject_params()
+    N.check("vcrt_default_reproject_params",
+            N.lib().vcrt_default_reproject_params(ctypes.byref(p)))
+    for name, v in given.items():
+        if v is None:
+            continue
+        try:
+            setattr(p, name, float(v))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"reproject: {name}: a number expected ({e})") from None
+    return p
+
+
+REPROJECT_PLANES = ("colour", "motion", "history_colour", "history_surface", "history_length")
+
+
+def _check_reproject_planes(planes: dict) -> dict:
+    """The planes of a reproject call, validated before any native call: numpy float32
+    C-contiguous (converted) or torch float32 contiguous tensors on one CUDA device (as they
+    are); [height, width, 4] each, history_length [height, width]. Raises ValueError."""
+    colour = planes["colour"]
+    if colour is None:
+        raise ValueError("colour: a plane expected")
+    torch_in = _is_torch(colour)
+    out = {}
+    for name in REPROJECT_PLANES:
+        a = planes[name]
+        if a is None:
+            raise ValueError(f"{name}: a plane expected")
+        if _is_torch(a) != torch_in:
+            raise ValueError("the planes must all be numpy arrays or all torch tensors")
+        if torch_in:
+            import torch
+            if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous():
+                raise ValueError(f"{name}: a contiguous float32 CUDA tensor expected")
+            if a.device != colour.device:
+                raise ValueError(f"{name}: torch tensors must be on one CUDA device")
+        else:
+            try:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{name}: not convertible to a float32 array ({e})") from None
+        first = out.get("colour", a)
+        if name == "history_length":
+            if a.ndim != 2 or tuple(a.shape) != tuple(first.shape[:2]):
+                raise ValueError(f"{name}: shape [height, width] of the colour plane expected, "
+                                 f"got {tuple(a.shape)}")
+        elif a.ndim != 3 or a.shape[2] != 4 or tuple(a.shape) != tuple(first.shape):
+            raise ValueError(f"{name}: shape [height, width, 4] of the colour plane expected, "
+                             f"got {tuple(a.shape)}")
+        out[name] = a
+    return out
+
+
+def reproject_host(colour, motion, history_colour, history_surface, history_length, **params):
+    """Temporal accumulation's definition on the host (vcrt_reproject_host: no GPU) over numpy
+    planes [height, width, 4] and history_length [height, width]: (out, out_length);
+    Renderer.reproject computes the same bits on the GPU. params: alpha, max_history,
+    depth_tolerance (omitted: default_reproject_params)."""
+    if _is_torch(colour):
+        raise ValueError("reproject_host takes numpy planes")
+    pl = _check_reproject_planes(dict(colour=colour, motion=motion, history_colour=history_colour,
+                                      history_surface=history_surface,
+                                      history_length=history_length))
+    p = _reproject_params(params)
+    c = pl["colour"]
+    out, length = np.empty_like(c), np.empty(c.shape[:2], np.float32)
+    N.check("vcrt_reproject_host", N.lib().vcrt_reproject_host(
+        *(pl[n].ctypes.data for n in REPROJECT_PLANES), c.shape[1], c.shape[0], ctypes.byref(p),
+        out.ctypes.data, length.ctypes.data))
+    return out, length
+
+
+def _camera_c(desc: RenderDesc, camera) -> N.vcrt_camera:
+    """A vcrt_camera from `camera`: a RenderDesc, or a dict of the camera fields that differ from
+    desc's (lookfrom, lookat, vup, vfov)."""
+    if isinstance(camera, RenderDesc):
+        return camera.to_c().camera
+    if not isinstance(camera, dict) or set(camera) - {"lookfrom", "lookat", "vup", "vfov"}:
+        raise ValueError("camera: a RenderDesc or a dict of lookfrom, lookat, vup, vfov expected")
+    return desc.with_camera(**camera).to_c().camera
+
+
+def motion_project(desc: RenderDesc, points, prev_camera=None) -> np.ndarray:
+    """float32 [n, 3]: (px, py, z') of the world points [n, 3] through the camera prev_camera
+    (None: desc's; a RenderDesc or a dict of camera fields) at desc's size -- the projection of
+    Renderer.draw_motion (vcrt_motion_project: host only, no GPU). A NaN triple where a point
+    does not project."""
+    try:
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"points: not convertible to a float32 array ({e})") from None
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points: shape [n, 3] expected, got {tuple(pts.shape)}")
+    out = np.empty_like(pts)
+    cam = None if prev_camera is None else ctypes.byref(_camera_c(desc, prev_camera))
+    N.check("vcrt_motion_project", N.lib().vcrt_motion_project(
+        ctypes.byref(desc.to_c()), cam, pts.ctypes.data, len(pts), out.ctypes.data))
+    return out
+
+
 def pixel_scale_log2(max_abs_quantum_sum: float) -> int:
     """s of a pixel's quantization scale 2^s from its largest |quantum sum| (vcrt_pixel_scale_log2:
     host only, no GPU): 32 below 2^12, else the largest s with max * 2^s < 2^44. The oracle
@@ -875,6 +992,151 @@ class Renderer:
                          "pass_ms": list(st.pass_ms)[:st.passes], "passes": st.passes,
                          "lds_passes": st.lds_passes, "kernel": st.kernel.decode()}
         return out
+
+    def draw_motion(self, prev_camera=None, prev_spheres=None, device: bool = False,
+                    stats: bool = False) -> dict:
+        """The reprojection map of the frame's pixels (vcrt_draw_motion): {"motion", "surface"},
+        float32 [..., 4] each in the rank-local framebuffer's shape ([height, width, 4] at world
+        1, else the packed tiles [tiles, 64, 4], slots outside the frame 0). motion = (px, py, z',
+        key): where the surface the pixel's centre ray hits lay in the previous frame -- seen by
+        prev_camera (None: the current camera; a RenderDesc or a dict of the camera fields that
+        differed) with the spheres at prev_spheres (None: the current values; whatever
+        update_spheres accepts, of the scene's count) -- in whole-frame pixel coordinates, the
+        depth it had there and the surface's key (1 the sky, s + 2 sphere s; all zeros: the point
+        does not project). surface = (key, t, 0, 0) of this frame: the next frame's
+        history_surface for reproject.
+
+        numpy through the host call; with device=True torch tensors on the renderer's device,
+        filled through the device call after the caller's current stream is synchronised (a torch
+        prev_spheres [n, 10] is read where it lies and implies device=True). With stats=True the
+        dict also holds "stats": rays, hit_rays, projected, identity, listed_rays, group_tests,
+        bound_tests, kernel_ms, host_ms, kernel. The framebuffer, the accumulation and the frame
+        statistics are left alone."""
+        lib = self._L()
+        cam = None if prev_camera is None else ctypes.byref(_camera_c(self.desc, prev_camera))
+        elems, tiles = self.local_layout()
+        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
+                else (tiles, 64))
+        st = N.vcrt_motion_stats()
+        prev_ptr, count = None, 0
+        if prev_spheres is not None and _is_torch(prev_spheres):
+            import torch
+            t = prev_spheres
+            if t.dtype != torch.float32 or t.ndim != 2 or t.shape[1] != 10:
+                raise ValueError("prev_spheres: a torch tensor must be float32 [n, 10]")
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("prev_spheres: a torch tensor must be contiguous and on a CUDA "
+                                 "device")
+            if self.desc.device >= 0 and t.device.index != self.desc.device:
+                raise ValueError(f"prev_spheres on {t.device}, the renderer on device "
+                                 f"{self.desc.device}")
+            device = True
+            prev_ptr, count = t.data_ptr(), int(t.shape[0])
+        elif prev_spheres is not None:
+            arr = (builtin_scene(prev_spheres) if isinstance(prev_spheres, (str, int))
+                   else prev_spheres)
+            arr = np.asarray(arr)
+            if arr.dtype != SPHERE_DTYPE:
+                arr = np.ascontiguousarray(arr, dtype=np.float32)
+                if arr.ndim != 2 or arr.shape[1] != 10:
+                    raise ValueError(f"prev_spheres: shape [n, 10] expected, got {arr.shape}")
+                arr = arr.view(SPHERE_DTYPE).reshape(-1)
+            arr = np.ascontiguousarray(arr)
+            count = len(arr)
+        out = {}
+        if device:
+            import torch
+            dev = torch.device("cuda", self.desc.device if self.desc.device >= 0
+                               else torch.cuda.current_device())
+            for name in ("motion", "surface"):
+                out[name] = torch.zeros(lead + (4,), device=dev, dtype=torch.float32)
+            if prev_spheres is not None and prev_ptr is None:  # host values: to the device
+                staged = torch.from_numpy(arr.view(np.float32).reshape(-1, 10).copy()).to(dev)
+                prev_ptr = staged.data_ptr()
+            torch.cuda.current_stream(dev).synchronize()
+            N.check("vcrt_draw_motion_device", lib.vcrt_draw_motion_device(
+                cam, prev_ptr, count, out["motion"].data_ptr(), out["surface"].data_ptr(),
+                ctypes.byref(st)))
+        else:
+            for name in ("motion", "surface"):
+                out[name] = np.zeros(lead + (4,), dtype=np.float32)
+            N.check("vcrt_draw_motion", lib.vcrt_draw_motion(
+                cam, None if prev_spheres is None else arr.ctypes.data, count,
+                out["motion"].ctypes.data, out["surface"].ctypes.data, ctypes.byref(st)))
+        if stats:
+            names = [f for f, _ in N.vcrt_motion_stats._fields_ if f != "kernel"]
+            out["stats"] = {**{f: getattr(st, f) for f in names}, "kernel": st.kernel.decode()}
+        return out
+
+    def reproject(self, frame, motion, history=None, *, surface=None, alpha=None,
+                  max_history=None, depth_tolerance=None, stats: bool = False):
+        """Temporal accumulation (vcrt_reproject): `frame` blended with the previous output
+        gathered at each pixel's previous position -- on the GPU the bits reproject_host
+        computes. Returns (out, history'): history' = {"colour": out, "surface": surface,
+        "length": out_length} is what the next call takes as `history`.
+
+        frame: the new frame [height, width, 4]; motion: draw_motion's "motion" plane of this
+        frame, whole ([height, width, 4]: at world size > 1 the gathered planes put through
+        assemble_tiles); surface: this frame's "surface" plane, carried into history' for the
+        next call (None: history' holds None there and the caller fills it in). history=None
+        starts a sequence: out = frame, every length 1. params: alpha, max_history,
+        depth_tolerance (None: default_reproject_params').
+
+        numpy planes go through the host call and give numpy planes; torch tensors on the
+        renderer's device go through the device call on their data_ptr(), after the caller's
+        current stream is synchronised, and give torch tensors. With stats=True the result is
+        (out, history', stats dict): kernel_ms, host_ms, accepted_pixels, kernel. Shape and dtype
+        errors raise ValueError before any native call. The framebuffer, the accumulation and the
+        frame statistics are left alone."""
+        lib = self._L()
+        p = _reproject_params(dict(alpha=alpha, max_history=max_history,
+                                   depth_tolerance=depth_tolerance))
+        st = N.vcrt_reproject_stats()
+        if history is None:
+            if frame is None or (not _is_torch(frame) and np.ndim(frame) != 3):
+                raise ValueError("frame: a plane [height, width, 4] expected")
+            if _is_torch(frame):
+                import torch
+                out = frame.clone()
+                length = torch.ones(frame.shape[:2], dtype=torch.float32, device=frame.device)
+            else:
+                out = np.array(frame, dtype=np.float32)
+                length = np.ones(out.shape[:2], np.float32)
+            hist = {"colour": out, "surface": surface, "length": length}
+            if stats:
+                return out, hist, {"kernel_ms": 0.0, "host_ms": 0.0, "accepted_pixels": 0,
+                                   "kernel": ""}
+            return out, hist
+        if not isinstance(history, dict) or set(history) < {"colour", "surface", "length"}:
+            raise ValueError('history: a dict with "colour", "surface" and "length" expected')
+        pl = _check_reproject_planes(dict(colour=frame, motion=motion,
+                                          history_colour=history["colour"],
+                                          history_surface=history["surface"],
+                                          history_length=history["length"]))
+        c = pl["colour"]
+        h, w = int(c.shape[0]), int(c.shape[1])
+        if _is_torch(c):
+            import torch
+            if self.desc.device >= 0 and c.device.index != self.desc.device:
+                raise ValueError(f"planes on {c.device}, the renderer on device "
+                                 f"{self.desc.device}")
+            out = torch.empty_like(c)
+            length = torch.empty((h, w), dtype=torch.float32, device=c.device)
+            torch.cuda.current_stream(c.device).synchronize()
+            N.check("vcrt_reproject_device", lib.vcrt_reproject_device(
+                *(pl[n].data_ptr() for n in REPROJECT_PLANES), w, h, ctypes.byref(p),
+                out.data_ptr(), length.data_ptr(), ctypes.byref(st)))
+        else:
+            out, length = np.empty_like(c), np.empty((h, w), np.float32)
+            N.check("vcrt_reproject", lib.vcrt_reproject(
+                *(pl[n].ctypes.data for n in REPROJECT_PLANES), w, h, ctypes.byref(p),
+                out.ctypes.data, length.ctypes.data, ctypes.byref(st)))
+        hist = {"colour": out, "surface": surface, "length": length}
+        if stats:
+            return out, hist, {"kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
+                               "accepted_pixels": st.accepted_pixels,
+                               "kernel": st.kernel.decode()}
+        return out, hist
 
     def occluded(self, origins, dirs, tmax=None, stats: bool = False):
         """Is anything in the way within each ray's reach (vcrt_occlude_rays)? Shadow rays,
