@@ -54,5 +54,23 @@ VkResult Reproject(IN const float* colour, IN const float* motion, IN const floa
                    IN const float* history_surface, IN const float* history_length,
                    IN int32_t width, IN int32_t height, IN const vcrt_reproject_params* params,
                    OUT float* out, OUT float* out_length);
+// Variance-guided denoising (vcrt_reproject_moments, vcrt_variance, vcrt_denoise_variance; host
+// pointers, [height][width] float4 each and float for the lengths and the variances).
+// ReprojectMoments is Reproject with the luminance moments carried along: albedo may be NULL,
+// history_moments is the previous call's out_moments. Variance turns out_moments and the frame's
+// surface plane into the per-pixel variance DenoiseVariance steers its colour term with;
+// out_variance may be NULL. params NULL takes the calls' defaults.
+VkResult ReprojectMoments(IN const float* colour, IN const float* motion,
+                          IN const float* history_colour, IN const float* history_surface,
+                          IN const float* history_length, IN const float* albedo,
+                          IN const float* history_moments, IN int32_t width, IN int32_t height,
+                          IN const vcrt_reproject_moments_params* params, OUT float* out,
+                          OUT float* out_length, OUT float* out_moments);
+VkResult Variance(IN const float* moments, IN const float* surface, IN int32_t width,
+                  IN int32_t height, IN const vcrt_variance_params* params, OUT float* variance);
+VkResult DenoiseVariance(IN const float* colour, IN const float* albedo,
+                         IN const float* normal_depth, IN const float* variance, IN int32_t width,
+                         IN int32_t height, IN const vcrt_denoise_params* params, OUT float* out,
+                         OUT float* out_variance);
 
 #endif

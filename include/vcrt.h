@@ -30,10 +30,12 @@
  * sphere id of the frame's own camera rays; vcrt_frame_rays) and its ambient visibility buffer
  * (vcrt_draw_occlusion: the open share of short rays sent from those first hits;
  * vcrt_ambient_dirs); the denoiser those guides are for (vcrt_denoise: an edge-avoiding
- * a-trous filter over a frame and its guide planes; vcrt_denoise_host, vcrt_denoise_scales); and
+ * a-trous filter over a frame and its guide planes; vcrt_denoise_host, vcrt_denoise_scales);
  * temporal accumulation over a reprojection map (vcrt_draw_motion: where each pixel's surface
  * was in the previous frame, vcrt_motion_project; vcrt_reproject: the previous output gathered
- * there and blended with the new frame, vcrt_reproject_host).
+ * there and blended with the new frame, vcrt_reproject_host); and the variance-guided link between
+ * the two (vcrt_reproject_moments: the accumulation with luminance moments; vcrt_variance: their
+ * per-pixel variance; vcrt_denoise_variance: the filter steered by it; their _host forms).
  *
  * Conventions: plain C types and pointers only. Every function returns a VkResult-compatible
  * int32_t (0 = success, negative = error; values from the Vulkan registry). Nothing throws
@@ -929,6 +931,160 @@ vcrt_result vcrt_reproject_device(const float* colour, const float* motion,
                                   const float* history_length, int32_t width, int32_t height,
                                   const vcrt_reproject_params* params, float* out,
                                   float* out_length, vcrt_reproject_stats* stats);
+
+/* Variance-guided denoising (Schied et al. 2017, SVGF): the link between the two calls above. The
+ * accumulation carries the first and second moments of the demodulated luminance along
+ * (vcrt_reproject_moments), they become a per-pixel variance, estimated spatially where the
+ * history is short (vcrt_variance), and that variance sets the denoiser's colour threshold per
+ * pixel and is filtered with the signal (vcrt_denoise_variance). vcrt_reproject and vcrt_denoise
+ * are unchanged. Pure image functions of the caller's planes, each [height][width], row 0 at the
+ * top, with the three forms of the calls above. Added.
+ * Everywhere: every fp32 operation rounded on its own, no contraction, divisions correctly
+ * rounded, sums from +0 in the stated order, one lane per output pixel, eps = 0x1p-10f and
+ *   lum(v) = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z
+ *
+ * vcrt_reproject_moments: vcrt_reproject's five input planes and two output planes, whose bits
+ * are exactly vcrt_reproject's for the same planes and alpha, max_history, depth_tolerance; and
+ * albedo (float4, may be NULL), history_moments (float4, the previous call's out_moments) and
+ * out_moments (float4). Per pixel p, c = colour[p]:
+ *   s.c = albedo ? c.c / fmaxf(albedo[p].c, eps) : c.c    (rgb: the signal the denoiser filters)
+ *   Y = lum(s)    Y2 = Y * Y
+ *   the four taps are visited, skipped, rejected and accepted exactly as in vcrt_reproject; an
+ *   accepted tap q adds, after vcrt_reproject's five sums,
+ *     m1 += b * history_moments[q].x    m2 += b * history_moments[q].y
+ *   (a skipped or rejected tap's moments are not read)
+ *   if wsum > 0:  rn = 1 / N    (vcrt_reproject's a is fmaxf(alpha, rn))
+ *       h1 = m1 / wsum    h2 = m2 / wsum    am = fmaxf(alpha_moments, rn)
+ *       M1 = h1 + am * (Y - h1)    M2 = h2 + am * (Y2 - h2)
+ *   else: M1 = Y, M2 = Y2                                  (N = 1)
+ *   out_moments = (M1, M2, fmaxf(M2 - M1 * M1, 0), N)
+ * A sequence starts from history planes of zeros, as vcrt_reproject's does. No plane is read
+ * outside the frame, whatever motion holds. One launch of vcrt_reproject_moments_pass.
+ * Errors: vcrt_reproject's, with alpha_moments outside (0, 1] a FORMAT error, a NULL
+ * history_moments or out_moments, and an output plane equal to any other plane,
+ * INITIALIZATION_FAILED. A NULL params takes vcrt_default_reproject_moments_params.
+ *
+ * vcrt_variance: moments, the out_moments plane above; surface, this frame's surface plane from
+ * vcrt_draw_motion (only .x, the key, is read); variance, float [height][width]: the variance of
+ * the accumulated, demodulated luminance. Per pixel p = (x, y), N = fmaxf(moments[p].w, 1):
+ *   if moments[p].w >= min_history:  v = moments[p].z
+ *   else: the taps q = (x + dx, y + dy) for dx, dy in -3 .. 3, dy outer and dx inner, both
+ *     ascending; a tap counts when it is inside the frame and surface[q].x == surface[p].x; the
+ *     centre always counts. For every counting tap, in that order,
+ *       S1 += moments[q].x    S2 += moments[q].y    n += 1    (n a float, exact)
+ *     a1 = S1 / n    a2 = S2 / n
+ *     v = fmaxf(a2 - a1 * a1, 0) * (min_history / N)        SVGF's boost of young pixels
+ *   variance[p] = v * fmaxf(alpha, 1 / N)
+ * alpha is the vcrt_reproject alpha the sequence runs with: the factor is the newest frame's
+ * weight in the accumulated colour. That is the variance of the mean exactly while the
+ * accumulation is the running mean (weight 1 / N each); once the average is exponential the
+ * variance of the mean tends to alpha / (2 - alpha) of a sample's, so the factor alpha is an
+ * upper estimate. One launch of vcrt_variance_pass_lds, whose workgroup stages its 32 x 8 pixels
+ * with their halo of 3 in LDS; VCRT_VARIANCE_LDS=0 in the environment (read at every call) takes
+ * vcrt_variance_pass, which reads the taps directly: the same bits, 2 to 3.5 times the time
+ * wherever a seventh of the pixels or more is young (profiles/variance.json).
+ * Errors: FORMAT_NOT_SUPPORTED for a wrong struct_size, min_history outside 1 .. 65535, alpha
+ * outside (0, 1], a NaN, the shape limits above; INITIALIZATION_FAILED for a NULL plane, variance
+ * equal to an input, a misaligned device plane (moments, surface 16 B, variance 4 B), and (not
+ * _host) before vcrt_begin. A NULL params takes vcrt_default_variance_params.
+ *
+ * vcrt_denoise_variance: vcrt_denoise with one more input, variance (float [height][width]), and
+ * one more output, out_variance (float [height][width], may be NULL). The variance rides in the
+ * fourth channel of the signal: s_0.w = fmaxf(variance[p], 0), s_0.rgb as vcrt_denoise's. Per
+ * pass l and pixel p = (x, y), differing from vcrt_denoise in this only:
+ *   the colour term is ON when sigma_colour != 0; then, before the 25 taps,
+ *     the taps q = (x + dx, y + dy) for dx, dy in -1 .. 1 (spacing 1 at every pass), dy outer
+ *     and dx inner, both ascending, taps outside the frame skipped, k3 = {1/4, 1/2, 1/4}:
+ *       h3 = k3[dx + 1] * k3[dy + 1]    gsum += h3 * s_l(q).w    gw += h3
+ *     g  = gsum / gw
+ *     kv = 1.0f / ((sigma_colour * sigma_colour) * g + 0x1p-20f)   sigma_colour does not halve:
+ *                                                                 the variance shrinks instead
+ *   per tap: dy = lum(s_l(p)) - lum(s_l(q))    tl = (dy * dy) * kv    in the place of dl * kl_l
+ *   X, e, w, acc.c and wsum as vcrt_denoise's; after wsum += w:  vacc += (w * w) * s_l(q).w
+ *   s_{l+1}(p).rgb = acc / wsum    s_{l+1}(p).w = vacc / (wsum * wsum)
+ * Final: out as vcrt_denoise's (re-modulated, out.a = colour.a); out_variance[p] = s_levels(p).w.
+ * A tap whose guide terms alone reach 1 has w = 0 and adds +0 to every sum; its signal is not
+ * read. One launch per pass of vcrt_denoise_var_pass or, for the first VCRT_DENOISE_LDS passes,
+ * vcrt_denoise_var_pass_lds (the staged halo of 2 step holds the 3 x 3 taps; same bits).
+ * Errors: vcrt_denoise's for its parameters and planes; a NULL variance, variance equal to out,
+ * out_variance equal to any other plane, a misaligned device plane (the float planes 4 B):
+ * INITIALIZATION_FAILED. A NULL params takes vcrt_default_denoise_variance_params.
+ *
+ * The host forms stage through device planes that are kept, only grown, and freed by vcrt_end.
+ * All leave alone the framebuffer, the accumulation, vcrt_stats and the cost order.
+ * VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object lacks the call's kernels. */
+typedef struct vcrt_reproject_moments_params {
+    uint32_t struct_size;      /* sizeof(vcrt_reproject_moments_params) */
+    float    alpha;            /* as vcrt_reproject_params */
+    float    max_history;
+    float    depth_tolerance;
+    float    alpha_moments;    /* 0 < alpha_moments <= 1: the least weight of the new moments */
+} vcrt_reproject_moments_params;
+typedef struct vcrt_variance_params {
+    uint32_t struct_size;      /* sizeof(vcrt_variance_params) */
+    float    min_history;      /* 1 .. 65535: below it the variance is estimated spatially */
+    float    alpha;            /* 0 < alpha <= 1: the sequence's vcrt_reproject alpha */
+} vcrt_variance_params;
+typedef struct vcrt_variance_stats {
+    double   kernel_ms;        /* the launch, HIP events on the render stream */
+    double   host_ms;          /* wall time of the call */
+    uint64_t spatial_pixels;   /* pixels below min_history: estimated from their neighbours */
+    char     kernel[48];       /* "vcrt_variance_pass_lds" or "vcrt_variance_pass" */
+} vcrt_variance_stats;
+/* The defaults of the three calls: tools/variance_defaults.py's choice
+ * (profiles/variance_defaults.json). vcrt_default_denoise_variance_params is
+ * vcrt_default_denoise_params with the chain's sigma_colour. */
+vcrt_result vcrt_default_reproject_moments_params(vcrt_reproject_moments_params* params);
+vcrt_result vcrt_default_variance_params(vcrt_variance_params* params);
+vcrt_result vcrt_default_denoise_variance_params(vcrt_denoise_params* params);
+vcrt_result vcrt_reproject_moments_host(const float* colour, const float* motion,
+                                        const float* history_colour, const float* history_surface,
+                                        const float* history_length, const float* albedo,
+                                        const float* history_moments, int32_t width,
+                                        int32_t height,
+                                        const vcrt_reproject_moments_params* params, float* out,
+                                        float* out_length, float* out_moments);
+/* stats: vcrt_reproject_stats, kernel "vcrt_reproject_moments_pass" */
+vcrt_result vcrt_reproject_moments(const float* colour, const float* motion,
+                                   const float* history_colour, const float* history_surface,
+                                   const float* history_length, const float* albedo,
+                                   const float* history_moments, int32_t width, int32_t height,
+                                   const vcrt_reproject_moments_params* params, float* out,
+                                   float* out_length, float* out_moments,
+                                   vcrt_reproject_stats* stats);
+vcrt_result vcrt_reproject_moments_device(const float* colour, const float* motion,
+                                          const float* history_colour,
+                                          const float* history_surface,
+                                          const float* history_length, const float* albedo,
+                                          const float* history_moments, int32_t width,
+                                          int32_t height,
+                                          const vcrt_reproject_moments_params* params, float* out,
+                                          float* out_length, float* out_moments,
+                                          vcrt_reproject_stats* stats);
+vcrt_result vcrt_variance_host(const float* moments, const float* surface, int32_t width,
+                               int32_t height, const vcrt_variance_params* params,
+                               float* variance);
+vcrt_result vcrt_variance(const float* moments, const float* surface, int32_t width,
+                          int32_t height, const vcrt_variance_params* params, float* variance,
+                          vcrt_variance_stats* stats);
+vcrt_result vcrt_variance_device(const float* moments, const float* surface, int32_t width,
+                                 int32_t height, const vcrt_variance_params* params,
+                                 float* variance, vcrt_variance_stats* stats);
+vcrt_result vcrt_denoise_variance_host(const float* colour, const float* albedo,
+                                       const float* normal_depth, const float* variance,
+                                       int32_t width, int32_t height,
+                                       const vcrt_denoise_params* params, float* out,
+                                       float* out_variance);
+/* stats: vcrt_denoise_stats, kernel "vcrt_denoise_var_pass" */
+vcrt_result vcrt_denoise_variance(const float* colour, const float* albedo,
+                                  const float* normal_depth, const float* variance, int32_t width,
+                                  int32_t height, const vcrt_denoise_params* params, float* out,
+                                  float* out_variance, vcrt_denoise_stats* stats);
+vcrt_result vcrt_denoise_variance_device(const float* colour, const float* albedo,
+                                         const float* normal_depth, const float* variance,
+                                         int32_t width, int32_t height,
+                                         const vcrt_denoise_params* params, float* out,
+                                         float* out_variance, vcrt_denoise_stats* stats);
 
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file

@@ -13,7 +13,9 @@ from .renderer import (BeginRenderingOperation, DrawNextFrame, EndRenderingOpera
                        Renderer, RenderDesc, SetRenderDescription, SetRenderScene, frame_rays, lens_offsets,
                        ambient_dirs, render, denoise_host, denoise_scales, default_denoise_params,
                        reproject_host, motion_project, default_reproject_params, tile_pixel_map,
-                       tile_slots, tiles_for_rank)
+                       tile_slots, tiles_for_rank, reproject_moments_host, variance_host,
+                       denoise_variance_host, default_reproject_moments_params,
+                       default_variance_params, default_denoise_variance_params)
 from .scene import SPHERE_DTYPE, builtin_scene, make_spheres, scene_generator_text
 
 __all__ = [
@@ -22,6 +24,9 @@ __all__ = [
     "tile_slots", "tile_pixel_map", "RAY_HIT_DTYPE", "lens_offsets", "frame_rays", "ambient_dirs",
     "denoise_host", "denoise_scales", "default_denoise_params",
     "reproject_host", "motion_project", "default_reproject_params",
+    "reproject_moments_host", "variance_host", "denoise_variance_host",
+    "default_reproject_moments_params", "default_variance_params",
+    "default_denoise_variance_params",
     "SPHERE_DTYPE", "builtin_scene", "make_spheres", "scene_generator_text", "VcrtError",
     "VK_SUCCESS", "VK_ERROR_INITIALIZATION_FAILED", "KERNEL_AUTO", "KERNEL_LDS", "KERNEL_SMEM",
     "KERNEL_CULL", "KERNEL_CULL_LANE", "KERNEL_CULL_FLAT", "TEXTURE_GLASS", "TEXTURE_LAMBERTIAN", "TEXTURE_METAL", "_native",

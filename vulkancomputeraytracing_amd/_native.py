@@ -220,6 +220,33 @@ class vcrt_reproject_stats(ctypes.Structure):
     ]
 
 
+class vcrt_reproject_moments_params(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("alpha", ctypes.c_float),
+        ("max_history", ctypes.c_float),
+        ("depth_tolerance", ctypes.c_float),
+        ("alpha_moments", ctypes.c_float),
+    ]
+
+
+class vcrt_variance_params(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("min_history", ctypes.c_float),
+        ("alpha", ctypes.c_float),
+    ]
+
+
+class vcrt_variance_stats(ctypes.Structure):
+    _fields_ = [
+        ("kernel_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("spatial_pixels", ctypes.c_uint64),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
 class vcrt_camera_stats(ctypes.Structure):
     _fields_ = [
         ("host_ms", ctypes.c_double),
@@ -397,6 +424,40 @@ SIGNATURES = {
     "vcrt_reproject_device": (ctypes.c_int32, [ctypes.c_void_p] * 5 + [ctypes.c_int32] * 2 +
                               [ctypes.POINTER(vcrt_reproject_params), ctypes.c_void_p,
                                ctypes.c_void_p, ctypes.POINTER(vcrt_reproject_stats)]),
+    "vcrt_default_reproject_moments_params": (ctypes.c_int32,
+                                              [ctypes.POINTER(vcrt_reproject_moments_params)]),
+    "vcrt_default_variance_params": (ctypes.c_int32, [ctypes.POINTER(vcrt_variance_params)]),
+    "vcrt_default_denoise_variance_params": (ctypes.c_int32,
+                                             [ctypes.POINTER(vcrt_denoise_params)]),
+    "vcrt_reproject_moments_host": (ctypes.c_int32, [ctypes.c_void_p] * 7 + [ctypes.c_int32] * 2 +
+                                    [ctypes.POINTER(vcrt_reproject_moments_params)] +
+                                    [ctypes.c_void_p] * 3),
+    "vcrt_reproject_moments": (ctypes.c_int32, [ctypes.c_void_p] * 7 + [ctypes.c_int32] * 2 +
+                               [ctypes.POINTER(vcrt_reproject_moments_params)] +
+                               [ctypes.c_void_p] * 3 + [ctypes.POINTER(vcrt_reproject_stats)]),
+    "vcrt_reproject_moments_device": (ctypes.c_int32,
+                                      [ctypes.c_void_p] * 7 + [ctypes.c_int32] * 2 +
+                                      [ctypes.POINTER(vcrt_reproject_moments_params)] +
+                                      [ctypes.c_void_p] * 3 +
+                                      [ctypes.POINTER(vcrt_reproject_stats)]),
+    "vcrt_variance_host": (ctypes.c_int32, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 2 +
+                           [ctypes.POINTER(vcrt_variance_params), ctypes.c_void_p]),
+    "vcrt_variance": (ctypes.c_int32, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 2 +
+                      [ctypes.POINTER(vcrt_variance_params), ctypes.c_void_p,
+                       ctypes.POINTER(vcrt_variance_stats)]),
+    "vcrt_variance_device": (ctypes.c_int32, [ctypes.c_void_p] * 2 + [ctypes.c_int32] * 2 +
+                             [ctypes.POINTER(vcrt_variance_params), ctypes.c_void_p,
+                              ctypes.POINTER(vcrt_variance_stats)]),
+    "vcrt_denoise_variance_host": (ctypes.c_int32, [ctypes.c_void_p] * 4 + [ctypes.c_int32] * 2 +
+                                   [ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p,
+                                    ctypes.c_void_p]),
+    "vcrt_denoise_variance": (ctypes.c_int32, [ctypes.c_void_p] * 4 + [ctypes.c_int32] * 2 +
+                              [ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p,
+                               ctypes.c_void_p, ctypes.POINTER(vcrt_denoise_stats)]),
+    "vcrt_denoise_variance_device": (ctypes.c_int32,
+                                     [ctypes.c_void_p] * 4 + [ctypes.c_int32] * 2 +
+                                     [ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.POINTER(vcrt_denoise_stats)]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

@@ -96,3 +96,29 @@ VkResult Reproject(IN const float* colour, IN const float* motion, IN const floa
                                                 history_length, width, height, params, out,
                                                 out_length, nullptr));
 }
+
+VkResult ReprojectMoments(IN const float* colour, IN const float* motion,
+                          IN const float* history_colour, IN const float* history_surface,
+                          IN const float* history_length, IN const float* albedo,
+                          IN const float* history_moments, IN int32_t width, IN int32_t height,
+                          IN const vcrt_reproject_moments_params* params, OUT float* out,
+                          OUT float* out_length, OUT float* out_moments) {
+    return static_cast<VkResult>(vcrt_reproject_moments(
+        colour, motion, history_colour, history_surface, history_length, albedo, history_moments,
+        width, height, params, out, out_length, out_moments, nullptr));
+}
+
+VkResult Variance(IN const float* moments, IN const float* surface, IN int32_t width,
+                  IN int32_t height, IN const vcrt_variance_params* params, OUT float* variance) {
+    return static_cast<VkResult>(
+        vcrt_variance(moments, surface, width, height, params, variance, nullptr));
+}
+
+VkResult DenoiseVariance(IN const float* colour, IN const float* albedo,
+                         IN const float* normal_depth, IN const float* variance, IN int32_t width,
+                         IN int32_t height, IN const vcrt_denoise_params* params, OUT float* out,
+                         OUT float* out_variance) {
+    return static_cast<VkResult>(vcrt_denoise_variance(colour, albedo, normal_depth, variance,
+                                                       width, height, params, out, out_variance,
+                                                       nullptr));
+}

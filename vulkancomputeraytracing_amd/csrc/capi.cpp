@@ -35,6 +35,7 @@
 #include "hip_status.hpp"
 #include "scene.hpp"
 #include "scene_update_abi.h"
+#include "variance_abi.h"
 #include "vcrt.h"
 #include "vcrt_kernel_abi.h"
 #include "vcrt_math.h"
@@ -131,6 +132,16 @@ struct RendererState {
     DeviceBuffer<float4> d_rp_stage[5];  // colour, motion, history colour, history surface, out
     DeviceBuffer<float> d_rp_length[2];  // history length, out length
     DeviceBuffer<unsigned long long> d_rp_counters;
+    // variance-guided denoising (vcrt_reproject_moments, vcrt_variance, vcrt_denoise_variance;
+    // null: the code object predates them): the host calls' staging planes beyond those of
+    // vcrt_reproject and vcrt_denoise, which they share, and the variance pass's tally slots;
+    // kept and grown only
+    hipFunction_t k_reproject_moments_pass = nullptr, k_variance_pass = nullptr,
+                  k_variance_pass_lds = nullptr, k_denoise_var_pass = nullptr,
+                  k_denoise_var_pass_lds = nullptr;
+    DeviceBuffer<float4> d_vr_stage[3];  // albedo, history moments, out moments
+    DeviceBuffer<float> d_vr_plane[2];   // the variance in, the variance out
+    DeviceBuffer<unsigned long long> d_vr_counters;
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -711,6 +722,13 @@ constexpr KernelRow kKernels[] = {
     {&RS::k_denoise_pass_lds, "vcrt_denoise_pass_lds", 16},
     {&RS::k_reproject_pass, "vcrt_reproject_pass", 25},
     {&RS::k_frame_motion, "vcrt_frame_motion", 26},
+    // variance-guided denoising: the moments pass, the two variance passes and the two steered
+    // denoise passes, each pair both or neither
+    {&RS::k_reproject_moments_pass, "vcrt_reproject_moments_pass", 27},
+    {&RS::k_variance_pass, "vcrt_variance_pass", 28},
+    {&RS::k_variance_pass_lds, "vcrt_variance_pass_lds", 28},
+    {&RS::k_denoise_var_pass, "vcrt_denoise_var_pass", 29},
+    {&RS::k_denoise_var_pass_lds, "vcrt_denoise_var_pass_lds", 29},
     // the camera-list kernels, each on its own (vcrt_set_camera asks for all four, else it runs
     // the host builders)
     {&RS::k_cl_prepare, "vcrt_camlist_prepare", 17},
@@ -3078,6 +3096,386 @@ vcrt_result vcrt_reproject(const float* colour, const float* motion, const float
                             hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipMemcpyAsync(out_length, g.d_rp_length[1].data(), sizeof(float) * pixels,
                             hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+// ---- variance-guided denoising -----------------------------------------------------------------
+
+namespace {
+
+constexpr size_t kMomentsCounterWords = 8 * vcrt::kMomentsTallySlots;    // u64
+constexpr size_t kVarianceCounterWords = 8 * vcrt::kVarianceTallySlots;  // u64
+
+inline bool misaligned(std::initializer_list<const void*> planes, uintptr_t mask) {
+    uintptr_t bits = 0;
+    for (const void* p : planes) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & mask) != 0;
+}
+
+inline float* plane_of(const DeviceBuffer<float4>& b) { return reinterpret_cast<float*>(b.data()); }
+
+// The moments launch on device planes (checked by the callers); returns when it is done.
+VkResult reproject_moments_device(const float* colour, const float* motion,
+                                  const float* history_colour, const float* history_surface,
+                                  const float* history_length, const float* albedo,
+                                  const float* history_moments, int32_t width, int32_t height,
+                                  const vcrt_reproject_moments_params& pr, float* out,
+                                  float* out_length, float* out_moments,
+                                  vcrt_reproject_stats* stats) {
+    vcrt::ReprojectMomentsParams p{};
+    p.colour = colour;
+    p.motion = motion;
+    p.history_colour = history_colour;
+    p.history_surface = history_surface;
+    p.history_length = history_length;
+    p.albedo = albedo;
+    p.history_moments = history_moments;
+    p.out = out;
+    p.out_length = out_length;
+    p.out_moments = out_moments;
+    p.width = static_cast<uint32_t>(width);
+    p.height = static_cast<uint32_t>(height);
+    p.alpha = pr.alpha;
+    p.max_history = pr.max_history;
+    p.depth_tolerance = pr.depth_tolerance;
+    p.alpha_moments = pr.alpha_moments;
+    p.tiles_x = (p.width + vcrt::kMomentsRowW - 1u) / vcrt::kMomentsRowW;
+    const uint32_t tiles_y = (p.height + vcrt::kMomentsRowH - 1u) / vcrt::kMomentsRowH;
+    if (!stats) {  // nothing to count or time
+        const VkResult r = launch(g.k_reproject_moments_pass, p.tiles_x * tiles_y,
+                                  vcrt::kMomentsThreads, 0, p);
+        if (r != VK_SUCCESS) return r;
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+        return VK_SUCCESS;
+    }
+    std::vector<unsigned long long> slots(kMomentsCounterWords);
+    float ms = 0.f;
+    const VkResult r = timed_launch(
+        g.k_reproject_moments_pass, p.tiles_x * tiles_y, vcrt::kMomentsThreads, p,
+        g.d_rp_counters, kMomentsCounterWords, [&p](unsigned long long* c) { p.tallies = c; },
+        slots.data(), &ms);
+    if (r != VK_SUCCESS) return r;
+    *stats = vcrt_reproject_stats{};
+    std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_reproject_moments_pass");
+    stats->kernel_ms = ms;
+    for (size_t s = 0; s < vcrt::kMomentsTallySlots; s++) stats->accepted_pixels += slots[8 * s];
+    return VK_SUCCESS;
+}
+
+// The variance launch on device planes (checked by the callers); returns when it is done.
+VkResult variance_device(const float* moments, const float* surface, int32_t width, int32_t height,
+                         const vcrt_variance_params& pr, float* variance,
+                         vcrt_variance_stats* stats) {
+    vcrt::VarianceParams p{};
+    p.moments = moments;
+    p.surface = surface;
+    p.variance = variance;
+    p.width = static_cast<uint32_t>(width);
+    p.height = static_cast<uint32_t>(height);
+    p.min_history = pr.min_history;
+    p.alpha = pr.alpha;
+    // VCRT_VARIANCE_LDS=0: the taps read directly; unset or 1, the measured choice
+    // (tools/variance_bench.py, profiles/variance.json): from a staged footprint. Same bits.
+    const char* e = std::getenv("VCRT_VARIANCE_LDS");
+    const bool lds = !e || std::atoi(e) != 0;
+    const uint32_t tw = lds ? vcrt::kVarianceTileW : vcrt::kVarianceRowW;
+    const uint32_t th = lds ? vcrt::kVarianceTileH : vcrt::kVarianceRowH;
+    const hipFunction_t f = lds ? g.k_variance_pass_lds : g.k_variance_pass;
+    const uint32_t lds_bytes = lds ? vcrt::kVarianceLdsBytes : 0u;
+    p.tiles_x = (p.width + tw - 1u) / tw;
+    const uint32_t tiles_y = (p.height + th - 1u) / th;
+    if (stats) {
+        VCRT_TRY(g.d_vr_counters.reserve(kVarianceCounterWords));
+        p.tallies = g.d_vr_counters.data();
+        VCRT_TRY(hipMemsetAsync(p.tallies, 0, kVarianceCounterWords * sizeof(unsigned long long),
+                                g.stream));
+        VCRT_TRY(hipEventRecord(g.ev_start.get(), g.stream));
+    }
+    const VkResult r = launch(f, p.tiles_x * tiles_y, vcrt::kVarianceThreads, lds_bytes, p);
+    if (r != VK_SUCCESS) return r;
+    if (!stats) {
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+        return VK_SUCCESS;
+    }
+    std::vector<unsigned long long> slots(kVarianceCounterWords);
+    float ms = 0.f;
+    VCRT_TRY(hipEventRecord(g.ev_stop.get(), g.stream));
+    VCRT_TRY(hipMemcpyAsync(slots.data(), p.tallies,
+                            kVarianceCounterWords * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start.get(), g.ev_stop.get()));
+    *stats = vcrt_variance_stats{};
+    std::snprintf(stats->kernel, sizeof(stats->kernel),
+                  lds ? "vcrt_variance_pass_lds" : "vcrt_variance_pass");
+    stats->kernel_ms = ms;
+    for (size_t s = 0; s < vcrt::kVarianceTallySlots; s++) stats->spatial_pixels += slots[8 * s];
+    return VK_SUCCESS;
+}
+
+// The steered passes on device planes (checked by the callers); returns when the last is done.
+// Sequenced as denoise_device's: the scratch planes and events are the denoiser's.
+VkResult denoise_variance_device(const float* colour, const float* albedo,
+                                 const float* normal_depth, const float* variance, int32_t width,
+                                 int32_t height, const vcrt_denoise_params& pr, const float k4[4],
+                                 float* out, float* out_variance, vcrt_denoise_stats* stats) {
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const int32_t levels = pr.levels;
+    for (int32_t b = 0; b < std::min(levels - 1, 2); b++)
+        VCRT_TRY(g.d_dn_scratch[b].reserve(pixels));
+    for (int32_t l = 0; l <= levels; l++) VCRT_TRY(g.ev_dn[l].create());
+    const bool demod = pr.demodulate != 0 && albedo;
+    uint32_t terms = 0;
+    if (normal_depth && k4[0] != 0.0f) terms |= vcrt::kDenoiseNormal;
+    if (normal_depth && k4[1] != 0.0f) terms |= vcrt::kDenoiseDepth;
+    if (albedo && k4[2] != 0.0f) terms |= vcrt::kDenoiseAlbedo;
+    if (pr.sigma_colour != 0.0f) terms |= vcrt::kDenoiseColour;
+    const int32_t lds_passes = std::min(denoise_lds_passes(), levels);
+    const float* in = colour;
+    VCRT_TRY(hipEventRecord(g.ev_dn[0].get(), g.stream));
+    for (int32_t l = 0; l < levels; l++) {
+        vcrt::DenoiseVarParams p{};
+        p.in = in;
+        p.colour = colour;
+        p.albedo = albedo;
+        p.normal_depth = normal_depth;
+        p.variance = variance;
+        p.out = l == levels - 1 ? out : reinterpret_cast<float*>(g.d_dn_scratch[l & 1].data());
+        p.out_variance = out_variance;
+        p.width = static_cast<uint32_t>(width);
+        p.height = static_cast<uint32_t>(height);
+        p.step = 1u << l;
+        p.flags = terms | (l == 0 ? vcrt::kDenoiseVarIn : 0u) |
+                  (demod && l == 0 ? vcrt::kDenoiseDemodIn : 0u) |
+                  (demod && l == levels - 1 ? vcrt::kDenoiseModOut : 0u) |
+                  (l == levels - 1 ? vcrt::kDenoiseLast : 0u);
+        p.k_normal = k4[0];
+        p.k_depth = k4[1];
+        p.k_albedo = k4[2];
+        p.sc2 = pr.sigma_colour * pr.sigma_colour;
+        VkResult r;
+        if (l < lds_passes) {
+            const uint32_t halo = 2u * p.step;
+            const uint32_t entries =
+                (vcrt::kDenoiseTileW + 2u * halo) * (vcrt::kDenoiseTileH + 2u * halo);
+            const bool guides = (terms & (vcrt::kDenoiseNormal | vcrt::kDenoiseDepth)) != 0;
+            const uint32_t planes =
+                1u + ((terms & vcrt::kDenoiseAlbedo) ? 1u : 0u) + (guides ? 1u : 0u);
+            p.tiles_x = (p.width + vcrt::kDenoiseTileW - 1u) / vcrt::kDenoiseTileW;
+            const uint32_t tiles_y = (p.height + vcrt::kDenoiseTileH - 1u) / vcrt::kDenoiseTileH;
+            r = launch(g.k_denoise_var_pass_lds, p.tiles_x * tiles_y, vcrt::kDenoiseThreads,
+                       entries * planes * static_cast<uint32_t>(sizeof(float4)), p);
+        } else {
+            p.tiles_x = (p.width + vcrt::kDenoiseRowW - 1u) / vcrt::kDenoiseRowW;
+            const uint32_t tiles_y = (p.height + vcrt::kDenoiseRowH - 1u) / vcrt::kDenoiseRowH;
+            r = launch(g.k_denoise_var_pass, p.tiles_x * tiles_y, vcrt::kDenoiseThreads, 0, p);
+        }
+        if (r != VK_SUCCESS) return r;
+        VCRT_TRY(hipEventRecord(g.ev_dn[l + 1].get(), g.stream));
+        in = p.out;
+    }
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) {
+        *stats = vcrt_denoise_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_denoise_var_pass");
+        stats->passes = levels;
+        stats->lds_passes = lds_passes;
+        float ms = 0.f;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[0].get(), g.ev_dn[levels].get()));
+        stats->kernel_ms = ms;
+        for (int32_t l = 0; l < levels; l++) {
+            VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[l].get(), g.ev_dn[l + 1].get()));
+            stats->pass_ms[l] = ms;
+        }
+    }
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_reproject_moments_device(const float* colour, const float* motion,
+                                          const float* history_colour,
+                                          const float* history_surface,
+                                          const float* history_length, const float* albedo,
+                                          const float* history_moments, int32_t width,
+                                          int32_t height,
+                                          const vcrt_reproject_moments_params* params, float* out,
+                                          float* out_length, float* out_moments,
+                                          vcrt_reproject_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_reproject_moments_params pr;
+    const vcrt_result a = vcrt::reproject_moments_args(
+        colour, motion, history_colour, history_surface, history_length, albedo, history_moments,
+        width, height, params, out, out_length, out_moments, &pr);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernel's 16-byte loads and stores of the float4 planes, 4-byte ones of the lengths
+    if (misaligned({colour, motion, history_colour, history_surface, albedo, history_moments, out,
+                    out_moments}, 15u) ||
+        misaligned({history_length, out_length}, 3u))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_reproject_moments_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = reproject_moments_device(colour, motion, history_colour, history_surface,
+                                                history_length, albedo, history_moments, width,
+                                                height, pr, out, out_length, out_moments, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_reproject_moments(const float* colour, const float* motion,
+                                   const float* history_colour, const float* history_surface,
+                                   const float* history_length, const float* albedo,
+                                   const float* history_moments, int32_t width, int32_t height,
+                                   const vcrt_reproject_moments_params* params, float* out,
+                                   float* out_length, float* out_moments,
+                                   vcrt_reproject_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_reproject_moments_params pr;
+    const vcrt_result a = vcrt::reproject_moments_args(
+        colour, motion, history_colour, history_surface, history_length, albedo, history_moments,
+        width, height, params, out, out_length, out_moments, &pr);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_reproject_moments_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    // vcrt_reproject's staging planes, then albedo, history moments, out moments
+    const float* host[4] = {colour, motion, history_colour, history_surface};
+    for (int k = 0; k < 5; k++) VCRT_TRY(g.d_rp_stage[k].reserve(pixels));
+    for (int k = 0; k < 2; k++) VCRT_TRY(g.d_rp_length[k].reserve(pixels));
+    for (int k = 0; k < 3; k++)
+        if (k != 0 || albedo) VCRT_TRY(g.d_vr_stage[k].reserve(pixels));
+    for (int k = 0; k < 4; k++)
+        VCRT_TRY(hipMemcpyAsync(g.d_rp_stage[k].data(), host[k], sizeof(float4) * pixels,
+                                hipMemcpyHostToDevice, g.stream));
+    VCRT_TRY(hipMemcpyAsync(g.d_rp_length[0].data(), history_length, sizeof(float) * pixels,
+                            hipMemcpyHostToDevice, g.stream));
+    if (albedo)
+        VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[0].data(), albedo, sizeof(float4) * pixels,
+                                hipMemcpyHostToDevice, g.stream));
+    VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[1].data(), history_moments, sizeof(float4) * pixels,
+                            hipMemcpyHostToDevice, g.stream));
+    const VkResult r = reproject_moments_device(
+        plane_of(g.d_rp_stage[0]), plane_of(g.d_rp_stage[1]), plane_of(g.d_rp_stage[2]),
+        plane_of(g.d_rp_stage[3]), g.d_rp_length[0].data(),
+        albedo ? plane_of(g.d_vr_stage[0]) : nullptr, plane_of(g.d_vr_stage[1]), width, height, pr,
+        plane_of(g.d_rp_stage[4]), g.d_rp_length[1].data(), plane_of(g.d_vr_stage[2]), stats);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(out, g.d_rp_stage[4].data(), sizeof(float4) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipMemcpyAsync(out_length, g.d_rp_length[1].data(), sizeof(float) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipMemcpyAsync(out_moments, g.d_vr_stage[2].data(), sizeof(float4) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+vcrt_result vcrt_variance_device(const float* moments, const float* surface, int32_t width,
+                                 int32_t height, const vcrt_variance_params* params,
+                                 float* variance, vcrt_variance_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_variance_params pr;
+    const vcrt_result a = vcrt::variance_args(moments, surface, width, height, params, variance,
+                                              &pr);
+    if (a != VCRT_SUCCESS) return a;
+    if (misaligned({moments, surface}, 15u) || misaligned({variance}, 3u))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_variance_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = variance_device(moments, surface, width, height, pr, variance, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_variance(const float* moments, const float* surface, int32_t width,
+                          int32_t height, const vcrt_variance_params* params, float* variance,
+                          vcrt_variance_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_variance_params pr;
+    const vcrt_result a = vcrt::variance_args(moments, surface, width, height, params, variance,
+                                              &pr);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_variance_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    // the moments and the surface through two of the moments call's planes
+    for (int k = 1; k < 3; k++) VCRT_TRY(g.d_vr_stage[k].reserve(pixels));
+    VCRT_TRY(g.d_vr_plane[1].reserve(pixels));
+    VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[1].data(), moments, sizeof(float4) * pixels,
+                            hipMemcpyHostToDevice, g.stream));
+    VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[2].data(), surface, sizeof(float4) * pixels,
+                            hipMemcpyHostToDevice, g.stream));
+    const VkResult r = variance_device(plane_of(g.d_vr_stage[1]), plane_of(g.d_vr_stage[2]), width,
+                                       height, pr, g.d_vr_plane[1].data(), stats);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(variance, g.d_vr_plane[1].data(), sizeof(float) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+vcrt_result vcrt_denoise_variance_device(const float* colour, const float* albedo,
+                                         const float* normal_depth, const float* variance,
+                                         int32_t width, int32_t height,
+                                         const vcrt_denoise_params* params, float* out,
+                                         float* out_variance, vcrt_denoise_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_denoise_params pr;
+    float k4[4];
+    const vcrt_result a = vcrt::denoise_variance_args(colour, albedo, normal_depth, variance, width,
+                                                      height, params, out, out_variance, &pr, k4);
+    if (a != VCRT_SUCCESS) return a;
+    if (misaligned({colour, albedo, normal_depth, out}, 15u) ||
+        misaligned({variance, out_variance}, 3u))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_denoise_var_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = denoise_variance_device(colour, albedo, normal_depth, variance, width,
+                                               height, pr, k4, out, out_variance, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_denoise_variance(const float* colour, const float* albedo,
+                                  const float* normal_depth, const float* variance, int32_t width,
+                                  int32_t height, const vcrt_denoise_params* params, float* out,
+                                  float* out_variance, vcrt_denoise_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vcrt_denoise_params pr;
+    float k4[4];
+    const vcrt_result a = vcrt::denoise_variance_args(colour, albedo, normal_depth, variance, width,
+                                                      height, params, out, out_variance, &pr, k4);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_denoise_var_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    // vcrt_denoise's staging planes, then the two variance planes
+    const float* host[3] = {colour, albedo, normal_depth};
+    const float* dev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++)
+        if (k == 3 || host[k]) VCRT_TRY(g.d_dn_stage[k].reserve(pixels));
+    for (int k = 0; k < 2; k++) VCRT_TRY(g.d_vr_plane[k].reserve(pixels));
+    for (int k = 0; k < 3; k++) {
+        if (!host[k]) continue;
+        VCRT_TRY(hipMemcpyAsync(g.d_dn_stage[k].data(), host[k], sizeof(float4) * pixels,
+                                hipMemcpyHostToDevice, g.stream));
+        dev[k] = reinterpret_cast<const float*>(g.d_dn_stage[k].data());
+    }
+    VCRT_TRY(hipMemcpyAsync(g.d_vr_plane[0].data(), variance, sizeof(float) * pixels,
+                            hipMemcpyHostToDevice, g.stream));
+    const VkResult r = denoise_variance_device(
+        dev[0], dev[1], dev[2], g.d_vr_plane[0].data(), width, height, pr, k4,
+        plane_of(g.d_dn_stage[3]), out_variance ? g.d_vr_plane[1].data() : nullptr, stats);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(out, g.d_dn_stage[3].data(), sizeof(float4) * pixels,
+                            hipMemcpyDeviceToHost, g.stream));
+    if (out_variance)
+        VCRT_TRY(hipMemcpyAsync(out_variance, g.d_vr_plane[1].data(), sizeof(float) * pixels,
+                                hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;

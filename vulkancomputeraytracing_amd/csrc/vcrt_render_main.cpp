@@ -9,6 +9,9 @@
 // --temporal FILE accumulates the frames of an --orbit: every frame after the first is put through
 // vcrt_reproject with the previous output as its history and the map of vcrt_draw_motion for the
 // previous frame's camera; FILE receives the last accumulated frame, and --denoise then filters it.
+// --variance (a flag; needs --temporal and --denoise) runs the variance-guided chain instead: every
+// frame, the first included, goes through vcrt_reproject_moments with the frame's albedo, and the
+// denoiser is vcrt_denoise_variance steered by vcrt_variance of the last frame's moments.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -29,7 +32,7 @@ int usage() {
                  "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm] "
                  "[--features PREFIX] [--feature-samples N] [--ao PREFIX] [--ao-rays M] "
                  "[--denoise file.ppm|file.pfm] [--denoise-levels L] "
-                 "[--temporal file.ppm|file.pfm]\n");
+                 "[--temporal file.ppm|file.pfm] [--variance]\n");
     return 2;
 }
 
@@ -65,8 +68,13 @@ int main(int argc, char** argv) {
     int feature_samples = 0;  // 0: the description's spp
     int ao_rays = 8;          // secondary rays per sample that hits
     bool configured = false;  // any option that changes the description or the scene
+    bool variance = false;    // --variance: the variance-guided chain
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
+        if (a == "--variance") {  // the one option without a value
+            variance = true;
+            continue;
+        }
         if (i + 1 >= argc) return usage();
         const char* v = argv[++i];
         configured = configured || (a != "--out" && a != "--frames" && a != "--features" &&
@@ -97,6 +105,10 @@ int main(int argc, char** argv) {
             if (scene < 0) return usage();
         } else return usage();
     }
+    if (variance && (temporal.empty() || denoise.empty())) {
+        std::fprintf(stderr, "--variance needs --temporal and --denoise\n");
+        return usage();
+    }
     // Without options this is the reference's main() exactly: Begin/Draw/End with nothing set,
     // so BeginRenderingOperation takes the reference's compile-time configuration (1280x720,
     // 1 spp, depth 50, its camera: globals.glsl:9-24) and its world[] (the final scene).
@@ -116,12 +128,19 @@ int main(int argc, char** argv) {
     // --temporal: the accumulated output, this frame's planes and the previous frame's
     const size_t pixels = static_cast<size_t>(desc.width) * desc.height;
     std::vector<float> acc, acc_len, next, next_len, colour, motion, surface, prev_surface;
+    // --variance: the moments carried with the accumulation, and this frame's guide buffers
+    std::vector<float> mom, next_mom, v_albedo, v_normal;
     if (!temporal.empty()) {
         for (std::vector<float>* v : {&acc, &next, &colour, &motion, &surface, &prev_surface})
             v->assign(4 * pixels, 0.0f);
         acc_len.assign(pixels, 0.0f);
         next_len.assign(pixels, 0.0f);
     }
+    if (variance)
+        for (std::vector<float>* v : {&mom, &next_mom, &v_albedo, &v_normal})
+            v->assign(4 * pixels, 0.0f);
+    const uint32_t guide_samples = static_cast<uint32_t>(
+        feature_samples > 0 ? feature_samples : desc.samples_per_pixel);
     vcrt_camera prev_cam = desc.camera;
     for (int f = 0; f < frames && r == VK_SUCCESS; f++) {
         vcrt_camera now_cam = f == 0 ? desc.camera : prev_cam;
@@ -153,7 +172,19 @@ int main(int argc, char** argv) {
             if (r == VK_SUCCESS)
                 r = DrawMotion(f == 0 ? nullptr : &prev_cam, nullptr, 0, motion.data(),
                                surface.data());
-            if (r == VK_SUCCESS && f == 0) {
+            if (r == VK_SUCCESS && variance) {
+                // the moments ride along from the first frame on: frame 0 runs on history planes
+                // of zeros (every tap rejected: out = frame, every length 1, the moments Y, Y^2)
+                r = DrawFeatures(0, guide_samples, v_albedo.data(), v_normal.data(), nullptr);
+                if (r == VK_SUCCESS)
+                    r = ReprojectMoments(colour.data(), motion.data(), acc.data(),
+                                         prev_surface.data(), acc_len.data(), v_albedo.data(),
+                                         mom.data(), desc.width, desc.height, nullptr, next.data(),
+                                         next_len.data(), next_mom.data());
+                acc.swap(next);
+                acc_len.swap(next_len);
+                mom.swap(next_mom);
+            } else if (r == VK_SUCCESS && f == 0) {
                 acc = colour;
                 acc_len.assign(pixels, 1.0f);
             } else if (r == VK_SUCCESS) {
@@ -256,14 +287,24 @@ int main(int argc, char** argv) {
             feature_samples > 0 ? feature_samples : desc.samples_per_pixel);
         std::vector<float> frame(4 * n), albedo(4 * n), normal(4 * n), clean(4 * n);
         vcrt_denoise_params dp;
-        vcrt_default_denoise_params(&dp);
+        if (variance) vcrt_default_denoise_variance_params(&dp);
+        else vcrt_default_denoise_params(&dp);
         if (denoise_levels != 0) dp.levels = denoise_levels;
         if (temporal.empty()) r = ReadFramebuffer(frame.data(), frame.size());
         else frame = acc;  // the accumulated frame
         if (r == VK_SUCCESS) r = DrawFeatures(0, samples, albedo.data(), normal.data(), nullptr);
-        if (r == VK_SUCCESS)
+        if (r == VK_SUCCESS && variance) {
+            // the last frame's moments and surfaces give the variance that steers the filter
+            std::vector<float> var(n);
+            r = Variance(mom.data(), prev_surface.data(), desc.width, desc.height, nullptr,
+                         var.data());
+            if (r == VK_SUCCESS)
+                r = DenoiseVariance(frame.data(), albedo.data(), normal.data(), var.data(),
+                                    desc.width, desc.height, &dp, clean.data(), nullptr);
+        } else if (r == VK_SUCCESS) {
             r = Denoise(frame.data(), albedo.data(), normal.data(), desc.width, desc.height, &dp,
                         clean.data());
+        }
         if (r == VK_SUCCESS) {
             std::vector<uint8_t> c8(pfm ? 0 : 4 * n);
             if (!pfm) {

@@ -351,6 +351,191 @@ def reproject_host(colour, motion, history_colour, history_surface, history_leng
     return out, length
 
 
+REPROJECT_MOMENTS_FIELDS = REPROJECT_FIELDS + ("alpha_moments",)
+VARIANCE_FIELDS = ("min_history", "alpha")
+
+
+def _float_params(call: str, struct, default_fn: str, fields, given: dict):
+    """The C parameter block `struct` of float fields: the defaults with the fields `given` names
+    (None: the default)."""
+    unknown = set(given) - set(fields)
+    if unknown:
+        raise TypeError(f"{call}: unexpected parameters {sorted(unknown)}")
+    p = struct()
+    N.check(default_fn, getattr(N.lib(), default_fn)(ctypes.byref(p)))
+    for name, v in given.items():
+        if v is None:
+            continue
+        try:
+            setattr(p, name, float(v))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"{call}: {name}: a number expected ({e})") from None
+    return p
+
+
+def _reproject_moments_params(given: dict) -> N.vcrt_reproject_moments_params:
+    return _float_params("reproject_moments", N.vcrt_reproject_moments_params,
+                         "vcrt_default_reproject_moments_params", REPROJECT_MOMENTS_FIELDS, given)
+
+
+def _variance_params(given: dict) -> N.vcrt_variance_params:
+    return _float_params("variance", N.vcrt_variance_params, "vcrt_default_variance_params",
+                         VARIANCE_FIELDS, given)
+
+
+def _denoise_variance_params(given: dict) -> N.vcrt_denoise_params:
+    """vcrt_default_denoise_variance_params with the fields `given` names (None: the default)."""
+    unknown = set(given) - set(DENOISE_FIELDS)
+    if unknown:
+        raise TypeError(f"denoise_variance: unexpected parameters {sorted(unknown)}")
+    p = N.vcrt_denoise_params()
+    N.check("vcrt_default_denoise_variance_params",
+            N.lib().vcrt_default_denoise_variance_params(ctypes.byref(p)))
+    for name, v in given.items():
+        if v is None:
+            continue
+        try:
+            setattr(p, name, int(v) if name in ("levels", "demodulate") else float(v))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"denoise_variance: {name}: a number expected ({e})") from None
+    return p
+
+
+def default_reproject_moments_params() -> dict:
+    """vcrt_default_reproject_moments_params as a dict: reproject's fields and alpha_moments."""
+    p = _reproject_moments_params({})
+    return {f: getattr(p, f) for f in REPROJECT_MOMENTS_FIELDS}
+
+
+def default_variance_params() -> dict:
+    """vcrt_default_variance_params as a dict: min_history, alpha."""
+    p = _variance_params({})
+    return {f: getattr(p, f) for f in VARIANCE_FIELDS}
+
+
+def default_denoise_variance_params() -> dict:
+    """vcrt_default_denoise_variance_params as a dict: denoise's fields."""
+    p = _denoise_variance_params({})
+    return {f: getattr(p, f) for f in DENOISE_FIELDS}
+
+
+def _check_image_planes(planes: dict, scalar=(), optional=()) -> dict:
+    """Planes of one image call, validated before any native call: numpy float32 C-contiguous
+    (converted) or torch float32 contiguous tensors on one CUDA device (as they are). The first
+    plane is [height, width, 4] and sets the shape; the names in `scalar` are [height, width], the
+    others [height, width, 4]; the names in `optional` may be None. Raises ValueError."""
+    first_name = next(iter(planes))
+    first = planes[first_name]
+    if first is None:
+        raise ValueError(f"{first_name}: a plane expected")
+    torch_in = _is_torch(first)
+    out = {}
+    shape = None
+    for name, a in planes.items():
+        if a is None:
+            if name not in optional:
+                raise ValueError(f"{name}: a plane expected")
+            out[name] = None
+            continue
+        if _is_torch(a) != torch_in:
+            raise ValueError("the planes must all be numpy arrays or all torch tensors")
+        if torch_in:
+            import torch
+            if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous():
+                raise ValueError(f"{name}: a contiguous float32 CUDA tensor expected")
+            if a.device != first.device:
+                raise ValueError(f"{name}: torch tensors must be on one CUDA device")
+        else:
+            try:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"{name}: not convertible to a float32 array ({e})") from None
+        if shape is None:
+            if a.ndim != 3 or a.shape[2] != 4:
+                raise ValueError(f"{name}: shape [height, width, 4] expected, "
+                                 f"got {tuple(a.shape)}")
+            shape = tuple(a.shape)
+        elif name in scalar:
+            if tuple(a.shape) != shape[:2]:
+                raise ValueError(f"{name}: shape [height, width] of the {first_name} plane "
+                                 f"expected, got {tuple(a.shape)}")
+        elif tuple(a.shape) != shape:
+            raise ValueError(f"{name}: shape [height, width, 4] of the {first_name} plane "
+                             f"expected, got {tuple(a.shape)}")
+        out[name] = a
+    return out
+
+
+MOMENTS_PLANES = ("colour", "motion", "history_colour", "history_surface", "history_length",
+                  "albedo", "history_moments")
+
+
+def _ptr(a):
+    """The address of a checked plane (None: NULL)."""
+    if a is None:
+        return None
+    return a.data_ptr() if _is_torch(a) else a.ctypes.data
+
+
+def reproject_moments_host(colour, motion, history_colour, history_surface, history_length,
+                           history_moments, albedo=None, **params):
+    """Temporal accumulation with luminance moments, the definition on the host
+    (vcrt_reproject_moments_host: no GPU) over numpy planes: (out, out_length, out_moments);
+    Renderer.reproject_moments computes the same bits on the GPU. params: alpha, max_history,
+    depth_tolerance, alpha_moments (omitted: default_reproject_moments_params)."""
+    if _is_torch(colour):
+        raise ValueError("reproject_moments_host takes numpy planes")
+    pl = _check_image_planes(dict(colour=colour, motion=motion, history_colour=history_colour,
+                                  history_surface=history_surface,
+                                  history_length=history_length, albedo=albedo,
+                                  history_moments=history_moments),
+                             scalar=("history_length",), optional=("albedo",))
+    p = _reproject_moments_params(params)
+    c = pl["colour"]
+    out, length = np.empty_like(c), np.empty(c.shape[:2], np.float32)
+    moments = np.empty_like(c)
+    N.check("vcrt_reproject_moments_host", N.lib().vcrt_reproject_moments_host(
+        *(_ptr(pl[n]) for n in MOMENTS_PLANES), c.shape[1], c.shape[0], ctypes.byref(p),
+        out.ctypes.data, length.ctypes.data, moments.ctypes.data))
+    return out, length, moments
+
+
+def variance_host(moments, surface, **params) -> np.ndarray:
+    """The per-pixel variance of the accumulated luminance, the definition on the host
+    (vcrt_variance_host: no GPU) over numpy planes [height, width, 4]: float32 [height, width];
+    Renderer.variance computes the same bits on the GPU. params: min_history, alpha (omitted:
+    default_variance_params)."""
+    if _is_torch(moments):
+        raise ValueError("variance_host takes numpy planes")
+    pl = _check_image_planes(dict(moments=moments, surface=surface))
+    p = _variance_params(params)
+    m = pl["moments"]
+    out = np.empty(m.shape[:2], np.float32)
+    N.check("vcrt_variance_host", N.lib().vcrt_variance_host(
+        m.ctypes.data, pl["surface"].ctypes.data, m.shape[1], m.shape[0], ctypes.byref(p),
+        out.ctypes.data))
+    return out
+
+
+def denoise_variance_host(colour, variance, albedo=None, normal_depth=None, **params):
+    """The variance-steered denoiser's definition on the host (vcrt_denoise_variance_host: no
+    GPU) over numpy planes: (out [height, width, 4], out_variance [height, width]);
+    Renderer.denoise_variance computes the same bits on the GPU. params: denoise's (omitted:
+    default_denoise_variance_params)."""
+    if _is_torch(colour):
+        raise ValueError("denoise_variance_host takes numpy planes")
+    pl = _check_image_planes(dict(colour=colour, albedo=albedo, normal_depth=normal_depth,
+                                  variance=variance), scalar=("variance",),
+                             optional=("albedo", "normal_depth"))
+    p = _denoise_variance_params(params)
+    c = pl["colour"]
+    out, out_var = np.empty_like(c), np.empty(c.shape[:2], np.float32)
+    N.check("vcrt_denoise_variance_host", N.lib().vcrt_denoise_variance_host(
+        c.ctypes.data, _ptr(pl["albedo"]), _ptr(pl["normal_depth"]), pl["variance"].ctypes.data,
+        c.shape[1], c.shape[0], ctypes.byref(p), out.ctypes.data, out_var.ctypes.data))
+    return out, out_var
+
+
 def _camera_c(desc: RenderDesc, camera) -> N.vcrt_camera:
     """A vcrt_camera from `camera`: a RenderDesc, or a dict of the camera fields that differ from
     desc's (lookfrom, lookat, vup, vfov)."""
@@ -1137,6 +1322,153 @@ class Renderer:
                                "accepted_pixels": st.accepted_pixels,
                                "kernel": st.kernel.decode()}
         return out, hist
+
+    def _same_device(self, plane):
+        if self.desc.device >= 0 and plane.device.index != self.desc.device:
+            raise ValueError(f"planes on {plane.device}, the renderer on device "
+                             f"{self.desc.device}")
+
+    def reproject_moments(self, frame, motion, history=None, *, surface=None, albedo=None,
+                          alpha=None, max_history=None, depth_tolerance=None,
+                          alpha_moments=None, stats: bool = False):
+        """Temporal accumulation that carries the luminance moments along
+        (vcrt_reproject_moments): reproject's out and length, bit for bit, and the first and
+        second moments of the demodulated luminance -- on the GPU the bits
+        reproject_moments_host computes. Returns (out, history'): history' = {"colour": out,
+        "surface": surface, "length": out_length, "moments": out_moments} is what the next call
+        takes as `history` and what variance() reads.
+
+        frame, motion, surface as for reproject; albedo: draw_features' plane of this frame
+        (None: the moments are the colour's luminance). history=None starts a sequence: the call
+        runs on history planes of zeros. params: alpha, max_history, depth_tolerance,
+        alpha_moments (None: default_reproject_moments_params').
+
+        numpy planes go through the host call, torch tensors on the renderer's device through
+        the device call, as reproject's. With stats=True the result is (out, history', stats
+        dict). Shape and dtype errors raise ValueError before any native call."""
+        lib = self._L()
+        p = _reproject_moments_params(dict(alpha=alpha, max_history=max_history,
+                                           depth_tolerance=depth_tolerance,
+                                           alpha_moments=alpha_moments))
+        st = N.vcrt_reproject_stats()
+        if history is None:
+            if frame is None or (not _is_torch(frame) and np.ndim(frame) != 3):
+                raise ValueError("frame: a plane [height, width, 4] expected")
+            if _is_torch(frame):
+                import torch
+                zeros4 = torch.zeros_like(frame)
+                zeros1 = torch.zeros(frame.shape[:2], dtype=frame.dtype, device=frame.device)
+            else:
+                zeros4 = np.zeros(np.shape(frame), np.float32)
+                zeros1 = np.zeros(np.shape(frame)[:2], np.float32)
+            history = {"colour": zeros4, "surface": zeros4, "length": zeros1, "moments": zeros4}
+        if (not isinstance(history, dict)
+                or not set(history) >= {"colour", "surface", "length", "moments"}):
+            raise ValueError('history: a dict with "colour", "surface", "length" and "moments" '
+                             'expected')
+        pl = _check_image_planes(dict(colour=frame, motion=motion,
+                                      history_colour=history["colour"],
+                                      history_surface=history["surface"],
+                                      history_length=history["length"], albedo=albedo,
+                                      history_moments=history["moments"]),
+                                 scalar=("history_length",), optional=("albedo",))
+        c = pl["colour"]
+        h, w = int(c.shape[0]), int(c.shape[1])
+        if _is_torch(c):
+            import torch
+            self._same_device(c)
+            out, moments = torch.empty_like(c), torch.empty_like(c)
+            length = torch.empty((h, w), dtype=torch.float32, device=c.device)
+            torch.cuda.current_stream(c.device).synchronize()
+            fn, name = lib.vcrt_reproject_moments_device, "vcrt_reproject_moments_device"
+        else:
+            out, moments = np.empty_like(c), np.empty_like(c)
+            length = np.empty((h, w), np.float32)
+            fn, name = lib.vcrt_reproject_moments, "vcrt_reproject_moments"
+        N.check(name, fn(*(_ptr(pl[n]) for n in MOMENTS_PLANES), w, h, ctypes.byref(p),
+                         _ptr(out), _ptr(length), _ptr(moments), ctypes.byref(st)))
+        hist = {"colour": out, "surface": surface, "length": length, "moments": moments}
+        if stats:
+            return out, hist, {"kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
+                               "accepted_pixels": st.accepted_pixels,
+                               "kernel": st.kernel.decode()}
+        return out, hist
+
+    def variance(self, history, *, min_history=None, alpha=None, stats: bool = False):
+        """The per-pixel variance of the accumulated, demodulated luminance (vcrt_variance) from
+        reproject_moments' history' (its "moments" and "surface" planes): float32
+        [height, width] -- temporal where the history is min_history long, else the 7 x 7
+        spatial estimate over the pixel's surface; on the GPU the bits variance_host computes.
+        params: min_history, alpha -- the alpha the sequence's reproject_moments runs with (None:
+        default_variance_params'). numpy or torch planes, as reproject's. With stats=True the
+        result is (variance, stats dict): kernel_ms, host_ms, spatial_pixels, kernel."""
+        lib = self._L()
+        p = _variance_params(dict(min_history=min_history, alpha=alpha))
+        if not isinstance(history, dict) or not set(history) >= {"moments", "surface"}:
+            raise ValueError('history: a dict with "moments" and "surface" expected')
+        pl = _check_image_planes(dict(moments=history["moments"], surface=history["surface"]))
+        m = pl["moments"]
+        h, w = int(m.shape[0]), int(m.shape[1])
+        st = N.vcrt_variance_stats()
+        if _is_torch(m):
+            import torch
+            self._same_device(m)
+            out = torch.empty((h, w), dtype=torch.float32, device=m.device)
+            torch.cuda.current_stream(m.device).synchronize()
+            fn, name = lib.vcrt_variance_device, "vcrt_variance_device"
+        else:
+            out = np.empty((h, w), np.float32)
+            fn, name = lib.vcrt_variance, "vcrt_variance"
+        N.check(name, fn(_ptr(m), _ptr(pl["surface"]), w, h, ctypes.byref(p), _ptr(out),
+                         ctypes.byref(st)))
+        if stats:
+            return out, {"kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
+                         "spatial_pixels": st.spatial_pixels, "kernel": st.kernel.decode()}
+        return out
+
+    def denoise_variance(self, frame, variance, guides=None, *, levels=None, sigma_normal=None,
+                         sigma_depth=None, sigma_albedo=None, sigma_colour=None, demodulate=None,
+                         stats: bool = False):
+        """The frame through the variance-steered denoiser (vcrt_denoise_variance): denoise's
+        filter with the colour threshold set per pixel by `variance` (variance()'s plane), which
+        is filtered along -- on the GPU the bits denoise_variance_host computes. Returns
+        (out [height, width, 4], out_variance [height, width]).
+
+        frame: a plane [height, width, 4]; guides: a dict with "albedo" and "normal_depth" as
+        draw_features returns them (either may be missing or None: its terms are off; None: no
+        guides). params: denoise's keyword parameters (None:
+        default_denoise_variance_params'). numpy or torch planes, as denoise's. With stats=True
+        the result is (out, out_variance, stats dict) with denoise's fields."""
+        lib = self._L()
+        p = _denoise_variance_params(dict(levels=levels, sigma_normal=sigma_normal,
+                                          sigma_depth=sigma_depth, sigma_albedo=sigma_albedo,
+                                          sigma_colour=sigma_colour, demodulate=demodulate))
+        guides = guides or {}
+        pl = _check_image_planes(dict(colour=frame, albedo=guides.get("albedo"),
+                                      normal_depth=guides.get("normal_depth"),
+                                      variance=variance), scalar=("variance",),
+                                 optional=("albedo", "normal_depth"))
+        c = pl["colour"]
+        h, w = int(c.shape[0]), int(c.shape[1])
+        st = N.vcrt_denoise_stats()
+        if _is_torch(c):
+            import torch
+            self._same_device(c)
+            out = torch.empty_like(c)
+            out_var = torch.empty((h, w), dtype=torch.float32, device=c.device)
+            torch.cuda.current_stream(c.device).synchronize()
+            fn, name = lib.vcrt_denoise_variance_device, "vcrt_denoise_variance_device"
+        else:
+            out, out_var = np.empty_like(c), np.empty((h, w), np.float32)
+            fn, name = lib.vcrt_denoise_variance, "vcrt_denoise_variance"
+        N.check(name, fn(_ptr(c), _ptr(pl["albedo"]), _ptr(pl["normal_depth"]),
+                         _ptr(pl["variance"]), w, h, ctypes.byref(p), _ptr(out), _ptr(out_var),
+                         ctypes.byref(st)))
+        if stats:
+            return out, out_var, {"kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
+                                  "pass_ms": list(st.pass_ms)[:st.passes], "passes": st.passes,
+                                  "lds_passes": st.lds_passes, "kernel": st.kernel.decode()}
+        return out, out_var
 
     def occluded(self, origins, dirs, tmax=None, stats: bool = False):
         """Is anything in the way within each ray's reach (vcrt_occlude_rays)? Shadow rays,
