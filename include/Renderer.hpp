@@ -72,5 +72,16 @@ VkResult DenoiseVariance(IN const float* colour, IN const float* albedo,
                          IN const float* normal_depth, IN const float* variance, IN int32_t width,
                          IN int32_t height, IN const vcrt_denoise_params* params, OUT float* out,
                          OUT float* out_variance);
+// Adaptive sampling (vcrt_draw_samples, vcrt_sample_counts; host pointers in the framebuffer's
+// layout). DrawSamples traces min(counts[p], max_count) further samples of the frame's own rays per
+// pixel, the sample indices from `first` on, into sums (float4: radiance sum, sample count; added
+// to when accumulate != 0) and mean (float4, may be NULL). SampleCounts turns a variance plane
+// (float) into the count plane (uint16) that reaches the standard deviation params->target; total
+// (may be NULL) receives the sum of the counts.
+VkResult DrawSamples(IN uint32_t first, IN uint32_t max_count, IN const uint16_t* counts,
+                     IN int32_t accumulate, OUT float* sums, OUT float* mean);
+VkResult SampleCounts(IN const float* variance, IN uint32_t elements,
+                      IN const vcrt_sample_count_params* params, OUT uint16_t* counts,
+                      OUT uint64_t* total);
 
 #endif

@@ -1086,6 +1086,112 @@ vcrt_result vcrt_denoise_variance_device(const float* colour, const float* albed
                                          const vcrt_denoise_params* params, float* out,
                                          float* out_variance, vcrt_denoise_stats* stats);
 
+/* Adaptive sampling: per-pixel sample counts traced on the GPU. vcrt_draw_samples traces, for
+ * every local pixel, the number of further samples of the frame's own rays that a count plane
+ * names, and sums their radiance in a fixed order; vcrt_sample_counts turns a variance plane
+ * (vcrt_variance) into such a count plane. Nothing is uploaded per ray. Added.
+ *
+ * counts (uint16), sums (float4) and mean (float4, may be NULL) are [elements] planes in the
+ * rank-local framebuffer layout (vcrt_local_layout: world 1 [height][width]; world > 1 packed tiles
+ * [tiles][64]); slots outside the frame are neither read nor written. For a valid local pixel p,
+ *   n_p = min(counts[p], max_count)
+ * and its samples are the indices i = first .. first + n_p - 1: ray_i(x, y) is vcrt_frame_rays'
+ * ray of that index (the definition above vcrt_draw_features, pinhole or lens), and
+ *   r_i = ray_color(ray_i, desc.max_depth)
+ * bit for bit what vcrt_trace_rays returns for that ray. The order of summation is fixed with
+ * the quantum Q = 4 (vcrt_work_quantum's base): quantum k of pixel p covers the sample offsets
+ * 4 k .. min(4 k + 3, n_p - 1);
+ *   S_k = the fp32 sum of the quantum's r_i, from +0, in index order
+ *   S_p = the fp32 sum of the S_k, from +0, in ascending k
+ * every operation rounded on its own, no contraction. So the bits depend on (desc, camera, scene,
+ * first, max_count, counts) only -- not on which lane or wave traced which quantum, on the route
+ * that served a first hit (the camera-ray lists where the frame has them, else the scans of
+ * vcrt_trace_rays; VCRT_FEATURE_LISTS=0 turns the list route off, as for vcrt_draw_features), or
+ * on kernel_variant.
+ *   accumulate == 0:  sums[p] = (S_p, (float)n_p), which is (0, 0, 0, 0) when n_p == 0
+ *   accumulate != 0:  for n_p > 0, sums[p].rgb = old.rgb + S_p (one fp32 add per channel) and
+ *                     sums[p].a = old.a + (float)n_p; for n_p == 0 the slot is not written
+ * so a zeroed plane carried through several rounds holds (radiance sum, sample count) per pixel;
+ * the caller gives each round a `first` at or past the previous round's first + max_count (the
+ * indices need not be contiguous, only distinct). When mean is non-NULL,
+ *   mean[p] = (sums[p].rgb / sums[p].a, 1) after the update, the divisions correctly rounded;
+ *   mean[p] = (0, 0, 0, 1) where sums[p].a == 0
+ * Relation to the frame: with uniform counts 4, first 0 and a non-progressive desc of
+ * samples_per_pixel 4 and accumulate_quantum 4, mean.rgb equals the framebuffer's rgb bit for bit
+ * (both are the sequential sum divided once).
+ *
+ * Three kernels run on the render stream: vcrt_sample_scan (the exclusive prefix of
+ * ceil(n_p / 4), the item table, the totals; one 32-byte read-back sizes the scratch, 16 B per
+ * item, kept and only grown), vcrt_trace_samples (a persistent grid whose waves claim items for
+ * their idle lanes with one atomic; a lane runs its item's up to four paths one after another, so
+ * a pixel's quanta spread over lanes and waves) and vcrt_sample_resolve (one lane per pixel).
+ * The call is local, not collective, and returns when done. It leaves alone the framebuffer, the
+ * progressive accumulation, vcrt_stats, the measured cost order and the frame's jitter and lens
+ * tables: the jitter terms and lens origins of [first, first + max_count) are built with the
+ * kernel and host functions the frame uses into vcrt_draw_features' tables. After
+ * vcrt_set_camera, vcrt_update_spheres and vcrt_set_scene it sees the new state.
+ * vcrt_draw_samples takes host pointers (staged through device planes kept between calls; sums
+ * is uploaded first when accumulate != 0 or the planes are packed tiles); vcrt_draw_samples_device
+ * device pointers, the float4 planes 16-B aligned, counts 2-B aligned.
+ * Errors: VCRT_ERROR_FORMAT_NOT_SUPPORTED for max_count == 0, max_count > 256 or first +
+ * max_count > 2^19, checked before the renderer's state, so they read the same before vcrt_begin,
+ * and when the scan finds more than 2^28 quanta (nothing is written then);
+ * VCRT_ERROR_INITIALIZATION_FAILED, before anything touches the GPU, before vcrt_begin, for a
+ * NULL counts or sums, for mean == sums and for a misaligned device plane;
+ * VCRT_ERROR_FEATURE_NOT_PRESENT when the loaded code object lacks the three kernels (an A/B
+ * build of an older tree). */
+typedef struct vcrt_sample_stats {
+    uint64_t pixels;       /* valid local pixels with n_p > 0 */
+    uint64_t samples;      /* sum of n_p over the valid local pixels */
+    uint64_t items;        /* work items (quanta) traced */
+    uint64_t segments;     /* ray segments traced */
+    uint64_t listed_rays;  /* camera rays answered from the camera-ray lists (0 if the route is not used) */
+    uint64_t group_tests, bound_tests;   /* as vcrt_ray_stats */
+    double   scan_ms, kernel_ms, resolve_ms, host_ms;  /* HIP events on the render stream; wall */
+    char     kernel[48];   /* the tracing kernel's symbol */
+} vcrt_sample_stats;
+vcrt_result vcrt_draw_samples(uint32_t first, uint32_t max_count, const uint16_t* counts,
+                              int32_t accumulate, float* sums, float* mean,
+                              vcrt_sample_stats* stats);
+vcrt_result vcrt_draw_samples_device(uint32_t first, uint32_t max_count, const uint16_t* counts,
+                                     int32_t accumulate, float* sums, float* mean,
+                                     vcrt_sample_stats* stats);
+/* vcrt_sample_counts: a count plane from a variance plane, element-wise; variance is a float
+ * plane and counts a uint16 plane of `elements` entries each (any layout: the same one).
+ *   k = 1.0f / (target * target)      the product, then one correctly rounded division (host)
+ *   v = fmaxf(variance[e], 0)         (a NaN gives 0)
+ *   t = v * k
+ *   c = t >= (float)max_count ? max_count : (uint32_t)ceilf(t)
+ *   counts[e] = max(c, min_count)
+ * target is the standard deviation to reach: a pixel whose mean has variance v needs about
+ * v / target^2 times the samples it has. stats->total is the sum of the counts, so a caller can
+ * rescale target to a budget. The kernel (vcrt_sample_counts_pass) computes the host function's
+ * bits. Errors: FORMAT_NOT_SUPPORTED for a wrong struct_size, a target that is not positive and
+ * finite or whose k is not (NaN included), min_count > max_count, max_count > 256, elements == 0
+ * or > 2^31; INITIALIZATION_FAILED for a NULL params or plane, counts equal to variance, a
+ * misaligned device plane (variance 4 B, counts 2 B), and (not _host) before vcrt_begin;
+ * FEATURE_NOT_PRESENT when the loaded code object lacks the kernel. */
+typedef struct vcrt_sample_count_params {
+    uint32_t struct_size;  /* sizeof(vcrt_sample_count_params) */
+    float    target;       /* > 0: the standard deviation to reach */
+    uint32_t min_count, max_count;   /* min_count <= max_count <= 256 */
+} vcrt_sample_count_params;
+typedef struct vcrt_sample_count_stats {
+    uint64_t total;        /* the sum of the counts written */
+    double   kernel_ms;    /* the launch, HIP events on the render stream (0: _host) */
+    double   host_ms;      /* wall time of the call (0: _host) */
+    char     kernel[48];   /* "vcrt_sample_counts_pass" (empty: _host) */
+} vcrt_sample_count_stats;
+vcrt_result vcrt_sample_counts_host(const float* variance, uint32_t elements,
+                                    const vcrt_sample_count_params* params, uint16_t* counts,
+                                    vcrt_sample_count_stats* stats);
+vcrt_result vcrt_sample_counts(const float* variance, uint32_t elements,
+                               const vcrt_sample_count_params* params, uint16_t* counts,
+                               vcrt_sample_count_stats* stats);
+vcrt_result vcrt_sample_counts_device(const float* variance, uint32_t elements,
+                                      const vcrt_sample_count_params* params, uint16_t* counts,
+                                      vcrt_sample_count_stats* stats);
+
 /* Loads (or reloads) the tracer code object from a file; the analogue of
  * CreateShaderStageFromFile. Returns VCRT_ERROR_INCOMPATIBLE_SHADER_BINARY when the file
  * cannot be read or is not a gfx950 code object. Requires vcrt_begin. A lens renderer

@@ -15,7 +15,8 @@ from .renderer import (BeginRenderingOperation, DrawNextFrame, EndRenderingOpera
                        reproject_host, motion_project, default_reproject_params, tile_pixel_map,
                        tile_slots, tiles_for_rank, reproject_moments_host, variance_host,
                        denoise_variance_host, default_reproject_moments_params,
-                       default_variance_params, default_denoise_variance_params)
+                       default_variance_params, default_denoise_variance_params,
+                       sample_counts_host)
 from .scene import SPHERE_DTYPE, builtin_scene, make_spheres, scene_generator_text
 
 __all__ = [
@@ -26,7 +27,7 @@ __all__ = [
     "reproject_host", "motion_project", "default_reproject_params",
     "reproject_moments_host", "variance_host", "denoise_variance_host",
     "default_reproject_moments_params", "default_variance_params",
-    "default_denoise_variance_params",
+    "default_denoise_variance_params", "sample_counts_host",
     "SPHERE_DTYPE", "builtin_scene", "make_spheres", "scene_generator_text", "VcrtError",
     "VK_SUCCESS", "VK_ERROR_INITIALIZATION_FAILED", "KERNEL_AUTO", "KERNEL_LDS", "KERNEL_SMEM",
     "KERNEL_CULL", "KERNEL_CULL_LANE", "KERNEL_CULL_FLAT", "TEXTURE_GLASS", "TEXTURE_LAMBERTIAN", "TEXTURE_METAL", "_native",

@@ -247,6 +247,41 @@ class vcrt_variance_stats(ctypes.Structure):
     ]
 
 
+class vcrt_sample_stats(ctypes.Structure):
+    _fields_ = [
+        ("pixels", ctypes.c_uint64),
+        ("samples", ctypes.c_uint64),
+        ("items", ctypes.c_uint64),
+        ("segments", ctypes.c_uint64),
+        ("listed_rays", ctypes.c_uint64),
+        ("group_tests", ctypes.c_uint64),
+        ("bound_tests", ctypes.c_uint64),
+        ("scan_ms", ctypes.c_double),
+        ("kernel_ms", ctypes.c_double),
+        ("resolve_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
+class vcrt_sample_count_params(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("target", ctypes.c_float),
+        ("min_count", ctypes.c_uint32),
+        ("max_count", ctypes.c_uint32),
+    ]
+
+
+class vcrt_sample_count_stats(ctypes.Structure):
+    _fields_ = [
+        ("total", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("kernel", ctypes.c_char * 48),
+    ]
+
+
 class vcrt_camera_stats(ctypes.Structure):
     _fields_ = [
         ("host_ms", ctypes.c_double),
@@ -458,6 +493,25 @@ SIGNATURES = {
                                      [ctypes.c_void_p] * 4 + [ctypes.c_int32] * 2 +
                                      [ctypes.POINTER(vcrt_denoise_params), ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.POINTER(vcrt_denoise_stats)]),
+    "vcrt_draw_samples": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(vcrt_sample_stats)]),
+    "vcrt_draw_samples_device": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_uint32,
+                                                  ctypes.c_void_p, ctypes.c_int32,
+                                                  ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.POINTER(vcrt_sample_stats)]),
+    "vcrt_sample_counts_host": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.POINTER(vcrt_sample_count_params),
+                                                 ctypes.c_void_p,
+                                                 ctypes.POINTER(vcrt_sample_count_stats)]),
+    "vcrt_sample_counts": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.POINTER(vcrt_sample_count_params),
+                                            ctypes.c_void_p,
+                                            ctypes.POINTER(vcrt_sample_count_stats)]),
+    "vcrt_sample_counts_device": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32,
+                                                   ctypes.POINTER(vcrt_sample_count_params),
+                                                   ctypes.c_void_p,
+                                                   ctypes.POINTER(vcrt_sample_count_stats)]),
     "vcrt_shader_load": (ctypes.c_int32, [ctypes.c_char_p]),
     "vcrt_scene_builtin": (ctypes.c_int32,
                            [ctypes.c_int32, ctypes.POINTER(vcrt_sphere), ctypes.c_int32]),

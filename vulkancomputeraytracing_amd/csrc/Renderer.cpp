@@ -122,3 +122,18 @@ VkResult DenoiseVariance(IN const float* colour, IN const float* albedo,
                                                        width, height, params, out, out_variance,
                                                        nullptr));
 }
+
+VkResult DrawSamples(IN uint32_t first, IN uint32_t max_count, IN const uint16_t* counts,
+                     IN int32_t accumulate, OUT float* sums, OUT float* mean) {
+    return static_cast<VkResult>(
+        vcrt_draw_samples(first, max_count, counts, accumulate, sums, mean, nullptr));
+}
+
+VkResult SampleCounts(IN const float* variance, IN uint32_t elements,
+                      IN const vcrt_sample_count_params* params, OUT uint16_t* counts,
+                      OUT uint64_t* total) {
+    vcrt_sample_count_stats st;
+    const vcrt_result r = vcrt_sample_counts(variance, elements, params, counts, &st);
+    if (r == VCRT_SUCCESS && total) *total = st.total;
+    return static_cast<VkResult>(r);
+}

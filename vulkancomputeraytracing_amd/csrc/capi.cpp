@@ -142,6 +142,22 @@ struct RendererState {
     DeviceBuffer<float4> d_vr_stage[3];  // albedo, history moments, out moments
     DeviceBuffer<float> d_vr_plane[2];   // the variance in, the variance out
     DeviceBuffer<unsigned long long> d_vr_counters;
+    // adaptive sampling (vcrt_draw_samples, vcrt_sample_counts; null: the code object predates
+    // them): the scan's block sums, offsets and item table, the tracer's scratch (16 B per
+    // item), the counters (totals, work index, tally slots), the host calls' staging planes and
+    // the events around the three kernels; kept and grown only. The jitter and lens tables are
+    // the feature buffers'.
+    hipFunction_t k_sample_scan = nullptr, k_trace_samples = nullptr, k_sample_resolve = nullptr,
+                  k_sample_counts_pass = nullptr;
+    DeviceBuffer<uint4> d_sm_block_sums;
+    DeviceBuffer<uint32_t> d_sm_offsets;
+    DeviceBuffer<uint2> d_sm_items;
+    DeviceBuffer<float4> d_sm_scratch;
+    DeviceBuffer<unsigned long long> d_sm_counters;
+    DeviceBuffer<uint16_t> d_sm_counts;
+    DeviceBuffer<float4> d_sm_stage[2];  // sums, mean
+    DeviceBuffer<float> d_sm_variance;
+    Event ev_sm[5];
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
     bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
@@ -729,6 +745,11 @@ constexpr KernelRow kKernels[] = {
     {&RS::k_variance_pass_lds, "vcrt_variance_pass_lds", 28},
     {&RS::k_denoise_var_pass, "vcrt_denoise_var_pass", 29},
     {&RS::k_denoise_var_pass_lds, "vcrt_denoise_var_pass_lds", 29},
+    // adaptive sampling: the scan, the tracer and the resolve, all or none; the count rule
+    {&RS::k_sample_scan, "vcrt_sample_scan", 30},
+    {&RS::k_trace_samples, "vcrt_trace_samples", 30},
+    {&RS::k_sample_resolve, "vcrt_sample_resolve", 30},
+    {&RS::k_sample_counts_pass, "vcrt_sample_counts_pass", 31},
     // the camera-list kernels, each on its own (vcrt_set_camera asks for all four, else it runs
     // the host builders)
     {&RS::k_cl_prepare, "vcrt_camlist_prepare", 17},
@@ -3476,6 +3497,284 @@ vcrt_result vcrt_denoise_variance(const float* colour, const float* albedo,
     if (out_variance)
         VCRT_TRY(hipMemcpyAsync(out_variance, g.d_vr_plane[1].data(), sizeof(float) * pixels,
                                 hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+// ---- adaptive sampling -------------------------------------------------------------------------
+
+namespace {
+
+// d_sm_counters: the scan's totals (4 u64), the tracer's work index (u32, a slot of its own),
+// then the tally slots
+constexpr size_t kSampleTotalsWord = 0, kSampleWorkWord = 8, kSampleTallyWord = 16;
+constexpr size_t kSampleCounterWords = kSampleTallyWord + kFeatureCounterWords;
+
+// The arguments both forms of vcrt_draw_samples check, before anything touches the GPU. The
+// format errors come first, so that they read the same with and without a renderer.
+vcrt_result sample_args(uint32_t first, uint32_t max_count, const void* counts, const void* sums,
+                        const void* mean) {
+    if (max_count == 0 || max_count > vcrt::kSampleMaxCount ||
+        static_cast<uint64_t>(first) + max_count > kFeatureMaxIndex)
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!counts || !sums || mean == sums) return VCRT_ERROR_INITIALIZATION_FAILED;
+    return VCRT_SUCCESS;
+}
+
+// The three kernels on device planes (checked by the callers); returns when the resolve is done.
+VkResult draw_samples_device(uint32_t first, uint32_t max_count, const uint16_t* counts,
+                             int32_t accumulate, float* sums, float* mean,
+                             vcrt_sample_stats* stats) {
+    if (stats) {
+        *stats = vcrt_sample_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_trace_samples");
+    }
+    if (g.local_tiles == 0) {  // a rank without tiles has no slot to write
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+        return VK_SUCCESS;
+    }
+    for (Event& e : g.ev_sm) VCRT_TRY(e.create());
+    const uint32_t blocks =
+        (g.total_pixels + vcrt::kSampleScanSlots - 1u) / vcrt::kSampleScanSlots;
+    VCRT_TRY(g.d_sm_block_sums.reserve(blocks));
+    VCRT_TRY(g.d_sm_offsets.reserve(g.total_pixels));
+    VCRT_TRY(g.d_sm_counters.reserve(kSampleCounterWords));
+    unsigned long long* counters = g.d_sm_counters.data();
+    VCRT_TRY(hipMemsetAsync(counters, 0, kSampleCounterWords * sizeof(unsigned long long),
+                            g.stream));
+    // ---- the scan: block sums, their prefix and the totals; one read-back sizes the rest ----
+    vcrt::SampleScanParams sp{};
+    sp.counts = counts;
+    sp.block_sums = g.d_sm_block_sums.data();
+    sp.totals = counters + kSampleTotalsWord;
+    sp.offsets = g.d_sm_offsets.data();
+    sp.blocks = blocks;
+    sp.max_count = max_count;
+    sp.total_pixels = g.total_pixels;
+    sp.width = g.desc.width;
+    sp.height = g.desc.height;
+    sp.rank = g.desc.rank;
+    sp.world = g.desc.world_size;
+    sp.tiles_x = g.tiles_x;
+    VCRT_TRY(hipEventRecord(g.ev_sm[0].get(), g.stream));
+    sp.phase = 0;
+    VkResult r = launch(g.k_sample_scan, blocks, vcrt::kSampleScanBlock, 0, sp);
+    if (r != VK_SUCCESS) return r;
+    sp.phase = 1;
+    r = launch(g.k_sample_scan, 1, vcrt::kSampleScanBlock, 0, sp);
+    if (r != VK_SUCCESS) return r;
+    unsigned long long totals[4] = {};
+    VCRT_TRY(hipMemcpyAsync(totals, sp.totals, sizeof(totals), hipMemcpyDeviceToHost, g.stream));
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    const uint64_t items = totals[2];
+    if (items > vcrt::kSampleMaxItems) return VK_ERROR_FORMAT_NOT_SUPPORTED;
+    VCRT_TRY(g.d_sm_items.reserve(items));
+    VCRT_TRY(g.d_sm_scratch.reserve(items));
+    if (items) {
+        sp.items = g.d_sm_items.data();
+        sp.phase = 2;
+        r = launch(g.k_sample_scan, blocks, vcrt::kSampleScanBlock, 0, sp);
+        if (r != VK_SUCCESS) return r;
+    }
+    VCRT_TRY(hipEventRecord(g.ev_sm[1].get(), g.stream));
+    // ---- the tracer: the tables of [first, first + max_count), then the persistent grid ----
+    vcrt::SampleTraceParams tp{};
+    if (items) {
+        const VkResult t = feature_tables(first, max_count);
+        if (t != VK_SUCCESS) return t;
+        frame_ray_scene(tp.scene, max_count);
+        tp.scene.max_depth = g.desc.max_depth;
+        tp.items = g.d_sm_items.data();
+        tp.scratch = g.d_sm_scratch.data();
+        tp.count = static_cast<uint32_t>(items);
+        tp.use_lists = g.feature_lists ? 1u : 0u;
+        tp.work = reinterpret_cast<uint32_t*>(counters + kSampleWorkWord);
+        tp.tallies = counters + kSampleTallyWord;
+        int per_cu = 0;
+        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g.k_trace_samples,
+                                                               kQueryBlock, 0) != hipSuccess ||
+            per_cu <= 0)
+            per_cu = 1;
+        if (g.desc.blocks_per_cu > 0) per_cu = std::min(per_cu, g.desc.blocks_per_cu);
+        const uint32_t grid = std::min<uint32_t>(
+            static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(g.num_cus),
+            (tp.count + kQueryBlock - 1) / kQueryBlock);
+        VCRT_TRY(hipEventRecord(g.ev_sm[2].get(), g.stream));
+        r = launch(g.k_trace_samples, grid, kQueryBlock, 0, tp);
+        if (r != VK_SUCCESS) return r;
+    } else {
+        VCRT_TRY(hipEventRecord(g.ev_sm[2].get(), g.stream));
+    }
+    VCRT_TRY(hipEventRecord(g.ev_sm[3].get(), g.stream));
+    // ---- the resolve ----
+    vcrt::SampleResolveParams rp{};
+    rp.counts = counts;
+    rp.offsets = g.d_sm_offsets.data();
+    rp.scratch = g.d_sm_scratch.data();
+    rp.sums = reinterpret_cast<float4*>(sums);
+    rp.mean = reinterpret_cast<float4*>(mean);
+    rp.max_count = max_count;
+    rp.accumulate = accumulate != 0 ? 1u : 0u;
+    rp.total_pixels = g.total_pixels;
+    rp.width = g.desc.width;
+    rp.height = g.desc.height;
+    rp.rank = g.desc.rank;
+    rp.world = g.desc.world_size;
+    rp.tiles_x = g.tiles_x;
+    r = launch(g.k_sample_resolve, (g.total_pixels + 255u) / 256u, 256, 0, rp);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipEventRecord(g.ev_sm[4].get(), g.stream));
+    std::vector<unsigned long long> slots;
+    if (stats && items) {
+        slots.resize(kFeatureCounterWords);
+        VCRT_TRY(hipMemcpyAsync(slots.data(), counters + kSampleTallyWord,
+                                kFeatureCounterWords * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, g.stream));
+    }
+    VCRT_TRY(hipStreamSynchronize(g.stream));
+    if (stats) {
+        stats->samples = totals[0];
+        stats->pixels = totals[1];
+        stats->items = items;
+        for (size_t s = 0; s < slots.size(); s += 8) {
+            stats->listed_rays += slots[s];
+            stats->group_tests += slots[s + 1];
+            stats->bound_tests += slots[s + 2];
+            stats->segments += slots[s + 3];
+        }
+        float ms = 0.f;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_sm[0].get(), g.ev_sm[1].get()));
+        stats->scan_ms = ms;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_sm[2].get(), g.ev_sm[3].get()));
+        stats->kernel_ms = ms;
+        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_sm[3].get(), g.ev_sm[4].get()));
+        stats->resolve_ms = ms;
+    }
+    return VK_SUCCESS;
+}
+
+// The count rule's launch on device planes (checked by the callers); returns when it is done.
+VkResult sample_counts_device(const float* variance, uint32_t elements, float k,
+                              const vcrt_sample_count_params& pr, uint16_t* counts,
+                              vcrt_sample_count_stats* stats) {
+    vcrt::SampleCountParams p{};
+    p.variance = variance;
+    p.counts = counts;
+    p.elements = elements;
+    p.k = k;
+    p.min_count = pr.min_count;
+    p.max_count = pr.max_count;
+    constexpr size_t words = 8 * vcrt::kSampleCountTallySlots;
+    const uint32_t grid = std::min<uint32_t>(
+        (elements + vcrt::kSampleCountThreads - 1u) / vcrt::kSampleCountThreads,
+        vcrt::kSampleCountMaxBlocks);
+    std::vector<unsigned long long> slots(words);
+    float ms = 0.f;
+    const VkResult r = timed_launch(
+        g.k_sample_counts_pass, grid, vcrt::kSampleCountThreads, p, g.d_vr_counters, words,
+        [&p](unsigned long long* c) { p.tallies = c; }, stats ? slots.data() : nullptr, &ms);
+    if (r != VK_SUCCESS) return r;
+    if (stats) {
+        *stats = vcrt_sample_count_stats{};
+        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_sample_counts_pass");
+        stats->kernel_ms = ms;
+        for (size_t s = 0; s < words; s += 8) stats->total += slots[s];
+    }
+    return VK_SUCCESS;
+}
+
+}  // namespace
+
+vcrt_result vcrt_draw_samples_device(uint32_t first, uint32_t max_count, const uint16_t* counts,
+                                     int32_t accumulate, float* sums, float* mean,
+                                     vcrt_sample_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = sample_args(first, max_count, counts, sums, mean);
+    if (a != VCRT_SUCCESS) return a;
+    // the kernels' 16-byte loads and stores, 2-byte loads of the counts
+    if (misaligned({sums, mean}, 15u) || misaligned({counts}, 1u))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_trace_samples) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = draw_samples_device(first, max_count, counts, accumulate, sums, mean, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_draw_samples(uint32_t first, uint32_t max_count, const uint16_t* counts,
+                              int32_t accumulate, float* sums, float* mean,
+                              vcrt_sample_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const vcrt_result a = sample_args(first, max_count, counts, sums, mean);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.k_trace_samples) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const size_t elems = g.local_elems;
+    VCRT_TRY(g.d_sm_counts.reserve(elems));
+    VCRT_TRY(g.d_sm_stage[0].reserve(elems));
+    if (mean) VCRT_TRY(g.d_sm_stage[1].reserve(elems));
+    if (elems) {
+        VCRT_TRY(hipMemcpyAsync(g.d_sm_counts.data(), counts, sizeof(uint16_t) * elems,
+                                hipMemcpyHostToDevice, g.stream));
+        // the slots the call leaves alone keep what the caller's planes hold: those outside the
+        // frame (packed tiles) and, accumulating, every pixel's old sums
+        if (accumulate != 0 || g.desc.world_size > 1)
+            VCRT_TRY(hipMemcpyAsync(g.d_sm_stage[0].data(), sums, sizeof(float4) * elems,
+                                    hipMemcpyHostToDevice, g.stream));
+        if (mean && g.desc.world_size > 1)
+            VCRT_TRY(hipMemcpyAsync(g.d_sm_stage[1].data(), mean, sizeof(float4) * elems,
+                                    hipMemcpyHostToDevice, g.stream));
+    }
+    const VkResult r = draw_samples_device(first, max_count, g.d_sm_counts.data(), accumulate,
+                                           plane_of(g.d_sm_stage[0]),
+                                           mean ? plane_of(g.d_sm_stage[1]) : nullptr, stats);
+    if (r != VK_SUCCESS) return r;
+    if (elems) {
+        VCRT_TRY(hipMemcpyAsync(sums, g.d_sm_stage[0].data(), sizeof(float4) * elems,
+                                hipMemcpyDeviceToHost, g.stream));
+        if (mean)
+            VCRT_TRY(hipMemcpyAsync(mean, g.d_sm_stage[1].data(), sizeof(float4) * elems,
+                                    hipMemcpyDeviceToHost, g.stream));
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+    }
+    if (stats) stats->host_ms = ms_since(t0);
+    return VCRT_SUCCESS;
+}
+
+vcrt_result vcrt_sample_counts_device(const float* variance, uint32_t elements,
+                                      const vcrt_sample_count_params* params, uint16_t* counts,
+                                      vcrt_sample_count_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    float k;
+    const vcrt_result a = vcrt::sample_count_args(variance, elements, params, counts, &k);
+    if (a != VCRT_SUCCESS) return a;
+    if (misaligned({variance}, 3u) || misaligned({counts}, 1u))
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_sample_counts_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    const VkResult r = sample_counts_device(variance, elements, k, *params, counts, stats);
+    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
+    return r;
+}
+
+vcrt_result vcrt_sample_counts(const float* variance, uint32_t elements,
+                               const vcrt_sample_count_params* params, uint16_t* counts,
+                               vcrt_sample_count_stats* stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    float k;
+    const vcrt_result a = vcrt::sample_count_args(variance, elements, params, counts, &k);
+    if (a != VCRT_SUCCESS) return a;
+    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (!g.k_sample_counts_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
+    VCRT_TRY(g.d_sm_variance.reserve(elements));
+    VCRT_TRY(g.d_sm_counts.reserve(elements));
+    VCRT_TRY(hipMemcpyAsync(g.d_sm_variance.data(), variance, sizeof(float) * elements,
+                            hipMemcpyHostToDevice, g.stream));
+    const VkResult r = sample_counts_device(g.d_sm_variance.data(), elements, k, *params,
+                                            g.d_sm_counts.data(), stats);
+    if (r != VK_SUCCESS) return r;
+    VCRT_TRY(hipMemcpyAsync(counts, g.d_sm_counts.data(), sizeof(uint16_t) * elements,
+                            hipMemcpyDeviceToHost, g.stream));
     VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;

@@ -3514,8 +3514,9 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_fill(FillParams p) {
 
 // ---------------------------------------------------------------------------------------------
 // Ray queries: ray_color (functions.glsl:65-92) and the first hit_sphere scan of caller-supplied
-// rays, a code-generation unit of its own (Makefile, part 3).
-#if !defined(VCRT_PART) || VCRT_PART == 3
+// rays, a code-generation unit of its own (Makefile, part 3); shade_segment serves the adaptive
+// sampling kernel too (part 15).
+#if !defined(VCRT_PART) || VCRT_PART == 3 || VCRT_PART == 15
 namespace {
 
 // One traced segment shaded: the arithmetic of trace_impl's shade_and_advance, hit and sky
@@ -3594,7 +3595,9 @@ __device__ __forceinline__ bool shade_segment(const TraceParams& S, float max_t,
 }
 
 }  // namespace
+#endif
 
+#if !defined(VCRT_PART) || VCRT_PART == 3
 // A persistent grid of lanes, one ray per lane: a lane whose path has ended takes the next ray
 // index, and a wave claims the indices of all its needing lanes with one atomic (adjacent lanes
 // of a claim get adjacent rays). Every segment runs the per-lane culled scan on the global tables
@@ -4039,7 +4042,7 @@ extern "C" __global__ __launch_bounds__(1024) void vcrt_trace_cull_flat_boxes_le
 //  * else what vcrt_trace_rays runs: the per-lane culled scan on the global tables when the
 //    scene has them and every ray the wave's remaining lanes hold is in the guarded range,
 //  * else the linear scan.
-#if !defined(VCRT_PART) || VCRT_PART == 10 || VCRT_PART == 12
+#if !defined(VCRT_PART) || VCRT_PART == 10 || VCRT_PART == 12 || VCRT_PART == 15
 namespace {
 
 // The first hit of one sample's camera ray (o, d), aa = dot(d, d), by the three routes above, as
@@ -4478,6 +4481,351 @@ extern "C" __global__ __launch_bounds__(256) void vcrt_frame_motion(MotionParams
         if (np) atomicAdd(slot + 4, np);
         if (ni) atomicAdd(slot + 5, ni);
     }
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// Adaptive sampling (vcrt_draw_samples), a code-generation unit of its own (Makefile, part 15):
+// for every local pixel n_p = min(counts[p], max_count) further samples of the frame's own rays,
+// summed in quanta of kSampleQuantum (vcrt.h states the order). Three kernels:
+//   vcrt_sample_scan     the exclusive prefix of ceil(n_p / 4) over the local slots, the item
+//                        table (slot, quantum) and the totals;
+//   vcrt_trace_samples   vcrt_trace_rays' persistent grid over the items: a lane runs its item's
+//                        up to four paths one after another, keeps the quantum's sum in registers
+//                        and stores one float4 per item. The rays are vcrt_frame_features'
+//                        ((corner + jitter_i) - origin), the first segment goes through
+//                        frame_first_hit, every segment through shade_segment;
+//   vcrt_sample_resolve  one lane per local slot adds its quanta in ascending k and applies the
+//                        accumulate rule.
+// A pixel's quanta are items of their own, so a pixel with many samples spreads over lanes and
+// waves; the bits depend on the item's sample indices only, not on who traced it.
+// Bounds: a slot q < total_pixels indexes offsets; counts, sums and mean are read and written at
+// pixel_of's out_index of valid slots only (< elements); an item index is below count before the
+// item, the scratch or the tables are touched; a table index 4 k + j is below n_p <= max_count.
+#if !defined(VCRT_PART) || VCRT_PART == 15
+namespace {
+
+// Exclusive prefix of v over the 256 threads of the block (every thread calls), and the total.
+__device__ __forceinline__ uint32_t block_prefix(uint32_t v, uint32_t& total, uint32_t* wave_tot) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off);
+        if (lane >= (uint32_t)off) x += y;
+    }
+    __syncthreads();  // the previous call's reads are done
+    if (lane == 63u) wave_tot[wave] = x;
+    __syncthreads();
+    uint32_t before = 0u, all = 0u;
+#pragma unroll
+    for (uint32_t w = 0; w < kSampleScanBlock / 64u; ++w) {
+        const uint32_t t = wave_tot[w];
+        before += w < wave ? t : 0u;
+        all += t;
+    }
+    total = all;
+    return before + x - v;
+}
+
+// n_p of local slot q: 0 outside the frame
+__device__ __forceinline__ uint32_t sample_count_of(const uint16_t* counts, uint32_t max_count,
+                                                    const Pixel& px) {
+    if (!px.valid) return 0u;
+    const uint32_t c = counts[px.out_index];
+    return c < max_count ? c : max_count;
+}
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(256) void vcrt_sample_scan(SampleScanParams p) {
+    __shared__ uint32_t wave_tot[kSampleScanBlock / 64u];
+    __shared__ unsigned long long red[2][kSampleScanBlock / 64u];
+    const uint32_t t = threadIdx.x;
+    if (p.phase == 1u) {  // one block: block_sums' quanta -> their exclusive prefix; the totals
+        unsigned long long carry = 0ull, my_s = 0ull, my_p = 0ull;
+        for (uint32_t base = 0; base < p.blocks; base += kSampleScanBlock) {
+            const uint32_t b = base + t;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (b < p.blocks) v = p.block_sums[b];
+            uint32_t total;
+            const uint32_t ex = block_prefix(v.x, total, wave_tot);
+            if (b < p.blocks) p.block_sums[b].x = (uint32_t)(carry + ex);
+            carry += total;
+            my_s += v.y;
+            my_p += v.z;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            my_s += __shfl_xor(my_s, off);
+            my_p += __shfl_xor(my_p, off);
+        }
+        if ((t & 63u) == 0u) {
+            red[0][t >> 6] = my_s;
+            red[1][t >> 6] = my_p;
+        }
+        __syncthreads();
+        if (t == 0u) {
+            unsigned long long s = 0ull, n = 0ull;
+            for (uint32_t w = 0; w < kSampleScanBlock / 64u; ++w) {
+                s += red[0][w];
+                n += red[1][w];
+            }
+            p.totals[0] = s;
+            p.totals[1] = n;
+            p.totals[2] = carry;
+            p.totals[3] = 0ull;
+        }
+        return;
+    }
+    // phases 0 and 2: four consecutive slots per thread
+    const uint32_t q0 = blockIdx.x * kSampleScanSlots + 4u * t;
+    uint32_t n[4], quanta = 0u, samples = 0u, pixels = 0u;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        n[i] = 0u;
+        const uint32_t q = q0 + i;
+        if (q < p.total_pixels) {
+            const Pixel px = pixel_of(q, (uint32_t)p.width, (uint32_t)p.height, p.tiles_x,
+                                      (uint32_t)p.world, (uint32_t)p.rank);
+            n[i] = sample_count_of(p.counts, p.max_count, px);
+        }
+        quanta += (n[i] + kSampleQuantum - 1u) / kSampleQuantum;
+        samples += n[i];
+        pixels += n[i] != 0u ? 1u : 0u;
+    }
+    uint32_t total;
+    const uint32_t ex = block_prefix(quanta, total, wave_tot);
+    if (p.phase == 0u) {
+        uint32_t s = samples, c = pixels;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            s += __shfl_xor(s, off);
+            c += __shfl_xor(c, off);
+        }
+        if ((t & 63u) == 0u) {
+            red[0][t >> 6] = s;
+            red[1][t >> 6] = c;
+        }
+        __syncthreads();
+        if (t == 0u) {
+            unsigned long long ss = 0ull, cc = 0ull;
+            for (uint32_t w = 0; w < kSampleScanBlock / 64u; ++w) {
+                ss += red[0][w];
+                cc += red[1][w];
+            }
+            p.block_sums[blockIdx.x] = make_uint4(total, (uint32_t)ss, (uint32_t)cc, 0u);
+        }
+        return;
+    }
+    uint32_t off = p.block_sums[blockIdx.x].x + ex;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        const uint32_t q = q0 + i;
+        if (q >= p.total_pixels) break;
+        p.offsets[q] = off;
+        const uint32_t nq = (n[i] + kSampleQuantum - 1u) / kSampleQuantum;
+        for (uint32_t k = 0; k < nq; ++k) {
+            const uint32_t left = n[i] - kSampleQuantum * k;
+            const uint32_t m = left < kSampleQuantum ? left : kSampleQuantum;
+            p.items[off + k] = make_uint2(q, k | (m << 16));
+        }
+        off += nq;
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256) void vcrt_trace_samples(SampleTraceParams p_arg) {
+    // the arguments through a pointer to the kernarg segment, as trace_impl reads them
+    (void)p_arg;
+    const SampleTraceParams& p = *reinterpret_cast<const SampleTraceParams*>(
+        (__attribute__((address_space(4))) const SampleTraceParams*)
+            __builtin_amdgcn_kernarg_segment_ptr());
+    const TraceParams& S = p.scene;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (S.max_depth <= 0) {  // ray_color's undefined return (canonical 0): every quantum sums 0
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < p.count;
+             i += gridDim.x * blockDim.x)
+            p.scratch[i] = make_float4(0.f, 0.f, 0.f, (float)(p.items[i].y >> 16));
+        return;
+    }
+    const int n = S.nspheres;
+    const float4* tgroup = S.cgroup + 5 * S.nbig;  // the hierarchy's group records
+    const bool lens = S.lens != nullptr;
+    const bool lists = p.use_lists != 0u && !lens && S.prim_info != nullptr;
+    const f3 p00 = mk(S.cam[0], S.cam[1], S.cam[2]);
+    const f3 du = mk(S.cam[3], S.cam[4], S.cam[5]);
+    const f3 dv = mk(S.cam[6], S.cam[7], S.cam[8]);
+    const f3 cam = mk(S.cam[9], S.cam[10], S.cam[11]);
+    bool need = true, done = false, fresh = false;
+    uint32_t idx = 0u;
+    // the lane's item: its pixel's corner and list word, the table index of its next sample, the
+    // samples it has left and the quantum's sum so far
+    f3 corner = mk(0.f, 0.f, 0.f), qsum = mk(0.f, 0.f, 0.f);
+    uint32_t inf = 15u, tab = 0u, left = 0u, item_m = 0u;
+    f3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 1.f, 0.f), atten = mk(1.f, 1.f, 1.f);
+    int pass = 0;
+    uint32_t segs = 0u, listed = 0u;  // this lane's, all its items
+    uint32_t w_halves = 0u, w_bounds = 0u;
+    for (;;) {
+        // ---- lanes whose item has ended take the next items: one atomic per wave ----
+        const uint64_t need_mask = __ballot(need && !done);
+        if (need_mask != 0u) {
+            const int leader = __builtin_ctzll(need_mask);
+            uint32_t base = 0u;
+            if ((int)lane == leader) base = atomicAdd(p.work, (uint32_t)__popcll(need_mask));
+            base = __builtin_amdgcn_readfirstlane(__shfl(base, leader));
+            if (need && !done) {
+                idx = base + lanes_below(need_mask);
+                if (idx < p.count) {
+                    const uint2 it = p.items[idx];
+                    const uint32_t q = it.x;
+                    const Pixel px = pixel_of(q, (uint32_t)S.width, (uint32_t)S.height, S.tiles_x,
+                                              (uint32_t)S.world, (uint32_t)S.rank);
+                    // shader.comp:43's pixel corner, vcrt_setup_jitter's operations
+                    corner = viewport_corner(p00, du, dv, px.x, px.y);
+                    // the sphere list of the slot's 4x4 quarter, as vcrt_frame_features reads it
+                    inf = 15u;
+                    if (lists) {
+                        const uint32_t lt = q >> 6, slot = q & 63u;
+                        inf = S.prim_info[2u * (lt * 4u + (((slot >> 5) & 1u) << 1) +
+                                                ((slot >> 2) & 1u)) + 1u];
+                    }
+                    tab = kSampleQuantum * (it.y & 0xffffu);
+                    item_m = it.y >> 16;
+                    left = item_m;
+                    qsum = mk(0.f, 0.f, 0.f);
+                    fresh = true;
+                    need = false;
+                } else {  // no item left: nothing more is stored, and the ray held is guarded
+                    done = true;
+                    o = mk(0.f, 0.f, 0.f);
+                    d = mk(0.f, 1.f, 0.f);
+                }
+            }
+        }
+        if (__ballot(!done) == 0u) break;
+        if (done) continue;
+
+        // ---- first segments that have a camera-ray list, ahead of the scan: a lane starting a
+        // sample takes its first hit from its quarter's list and shades it here, so that the
+        // scan below serves its second segment together with the other lanes' later ones (a
+        // wave's lanes start their samples at different times: taken inside the scan's step
+        // the list route would cost every iteration both routes' time). A sample that ends on
+        // its first segment makes the lane start its next one: at most four trips per item.
+        for (;;) {
+            if (fresh) {  // the item's next sample: vcrt_frame_features' camera ray
+                const float4 j = S.jitter[tab];
+                o = cam;
+                if (lens) {
+                    const float4 l = S.lens[tab];
+                    o = mk(l.x, l.y, l.z);
+                }
+                d = sub(add(corner, mk(j.x, j.y, j.z)), o);
+                atten = mk(1.f, 1.f, 1.f);
+                pass = 0;
+            }
+            const float aa = dot(d, d);
+            const bool cam_seg = fresh && !need && (inf & 15u) != 15u && guard_a(aa);
+            if (__ballot(cam_seg) == 0u) break;
+            if (cam_seg) {
+                ++segs;
+                float max_t = kInfinity;
+                int best = -1;
+                frame_first_hit(S, inf, tgroup, n, o, d, aa, max_t, best, listed, w_halves,
+                                w_bounds);
+                fresh = false;
+                f3 normal = mk(0.f, 0.f, 0.f), contrib = mk(0.f, 0.f, 0.f);
+                bool ended = shade_segment(S, max_t, best, o, d, atten, normal, contrib);
+                if (!ended) {
+                    ++pass;
+                    ended = pass >= S.max_depth;  // undefined GLSL return -> vec3(0)
+                }
+                if (ended) {
+                    qsum = add(qsum, contrib);  // S_k, in index order
+                    ++tab;
+                    --left;
+                    if (left != 0u) {
+                        fresh = true;
+                    } else {
+                        p.scratch[idx] = make_float4(qsum.x, qsum.y, qsum.z, (float)item_m);
+                        need = true;
+                    }
+                }
+            }
+        }
+        if (need) continue;  // the item ended on a first segment: the next claim
+
+        // ---- one segment by the scans of vcrt_trace_rays (frame_first_hit with no list word):
+        // a first segment without a list, and every later one ----
+        ++segs;
+        float max_t = kInfinity;
+        int best = -1;
+        frame_first_hit(S, 15u, tgroup, n, o, d, dot(d, d), max_t, best, listed, w_halves,
+                        w_bounds);
+        fresh = false;
+
+        // ---- shade (textures.glsl) or sky (functions.glsl:85-89) ----
+        f3 normal = mk(0.f, 0.f, 0.f), contrib = mk(0.f, 0.f, 0.f);
+        bool ended = shade_segment(S, max_t, best, o, d, atten, normal, contrib);
+        if (!ended) {
+            ++pass;
+            ended = pass >= S.max_depth;  // undefined GLSL return -> vec3(0)
+        }
+        if (ended) {
+            qsum = add(qsum, contrib);  // S_k, in index order
+            ++tab;
+            --left;
+            if (left != 0u) {
+                fresh = true;
+            } else {
+                p.scratch[idx] = make_float4(qsum.x, qsum.y, qsum.z, (float)item_m);
+                need = true;
+            }
+        }
+    }
+    // one atomic per wave and tally, into the block's slot (SampleTraceParams.tallies)
+    unsigned long long nl = listed, wh = w_halves, wb = w_bounds, total = segs;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nl += __shfl_xor(nl, off);
+        wh += __shfl_xor(wh, off);
+        wb += __shfl_xor(wb, off);
+        total += __shfl_xor(total, off);
+    }
+    if (lane == 0) {
+        unsigned long long* slot = p.tallies + 8u * (blockIdx.x & (kFeatureTallySlots - 1u));
+        if (nl) atomicAdd(slot + 0, nl);
+        if (wh) atomicAdd(slot + 1, wh / 2u);
+        if (wb) atomicAdd(slot + 2, wb);
+        if (total) atomicAdd(slot + 3, total);
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256) void vcrt_sample_resolve(SampleResolveParams p) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= p.total_pixels) return;
+    const Pixel px = pixel_of(q, (uint32_t)p.width, (uint32_t)p.height, p.tiles_x,
+                              (uint32_t)p.world, (uint32_t)p.rank);
+    if (!px.valid) return;  // slots outside the frame are neither read nor written
+    const uint32_t np = sample_count_of(p.counts, p.max_count, px);
+    const uint32_t nq = (np + kSampleQuantum - 1u) / kSampleQuantum;
+    const float4* sk = p.scratch + p.offsets[q];
+    f3 s = mk(0.f, 0.f, 0.f);
+    for (uint32_t k = 0; k < nq; ++k) {  // S_p: from +0, ascending k
+        const float4 v = sk[k];
+        s = add(s, mk(v.x, v.y, v.z));
+    }
+    float4 out = make_float4(s.x, s.y, s.z, (float)np);
+    if (p.accumulate != 0u) {
+        const float4 old = p.sums[px.out_index];
+        out = np != 0u ? make_float4(old.x + s.x, old.y + s.y, old.z + s.z, old.w + (float)np)
+                       : old;
+    }
+    if (p.accumulate == 0u || np != 0u) p.sums[px.out_index] = out;
+    if (p.mean)
+        p.mean[px.out_index] = out.w == 0.0f
+                                   ? make_float4(0.f, 0.f, 0.f, 1.f)
+                                   : make_float4(out.x / out.w, out.y / out.w, out.z / out.w, 1.f);
 }
 #endif
 

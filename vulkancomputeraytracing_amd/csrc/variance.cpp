@@ -267,6 +267,46 @@ vcrt_result vcrt_variance_host(const float* moments, const float* surface, int32
     return VCRT_SUCCESS;
 }
 
+int32_t vcrt::sample_count_args(const float* variance, uint64_t elements,
+                                const vcrt_sample_count_params* params, const uint16_t* counts,
+                                float* k) {
+    if (!params) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (params->struct_size != sizeof(vcrt_sample_count_params))
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (!(params->target > 0.0f) || std::isinf(params->target))  // (a NaN fails)
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (params->min_count > params->max_count || params->max_count > 256u)
+        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (elements == 0 || elements > (uint64_t{1} << 31)) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    const float tt = params->target * params->target;
+    *k = 1.0f / tt;
+    // a target whose square leaves fp32's range has no k to multiply by
+    if (!(*k > 0.0f) || std::isinf(*k)) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
+    if (!variance || !counts || static_cast<const void*>(variance) == counts)
+        return VCRT_ERROR_INITIALIZATION_FAILED;
+    return VCRT_SUCCESS;
+}
+
+vcrt_result vcrt_sample_counts_host(const float* variance, uint32_t elements,
+                                    const vcrt_sample_count_params* params, uint16_t* counts,
+                                    vcrt_sample_count_stats* stats) {
+    float k;
+    const int32_t a = vcrt::sample_count_args(variance, elements, params, counts, &k);
+    if (a != VCRT_SUCCESS) return a;
+    uint64_t total = 0;
+    for (size_t e = 0; e < elements; e++) {
+        const uint32_t c = vcrt::sample_count_of_variance(variance[e], k, params->min_count,
+                                                          params->max_count);
+        counts[e] = static_cast<uint16_t>(c);
+        total += c;
+    }
+    if (stats) {
+        *stats = vcrt_sample_count_stats{};
+        stats->total = total;
+    }
+    return VCRT_SUCCESS;
+}
+
 vcrt_result vcrt_denoise_variance_host(const float* colour, const float* albedo,
                                        const float* normal_depth, const float* variance,
                                        int32_t width, int32_t height,

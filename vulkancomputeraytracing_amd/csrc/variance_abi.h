@@ -3,8 +3,10 @@
 // every form of the three calls shares (variance.cpp).
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 
+struct vcrt_sample_count_params;
 struct vcrt_reproject_moments_params;
 struct vcrt_variance_params;
 struct vcrt_denoise_params;
@@ -96,6 +98,39 @@ struct DenoiseVarParams {
     float k_normal, k_depth, k_albedo;
     float sc2;                  // sigma_colour * sigma_colour: it does not halve
     uint32_t tiles_x;           // workgroups per row of workgroups
+};
+
+// The checks of vcrt_sample_counts{_host,,_device}: the format errors first, then the pointers.
+// *k receives 1 / (target * target) (the product, then one correctly rounded division).
+int32_t sample_count_args(const float* variance, uint64_t elements,
+                          const vcrt_sample_count_params* params, const uint16_t* counts,
+                          float* k);
+// One element of vcrt_sample_counts (vcrt.h): the host function's and the kernel's statement.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t sample_count_of_variance(float variance, float k, uint32_t min_count,
+                                         uint32_t max_count) {
+    const float v = fmaxf(variance, 0.0f);  // (a NaN gives 0)
+    const float t = v * k;
+    const uint32_t c = t >= static_cast<float>(max_count) ? max_count
+                                                          : static_cast<uint32_t>(ceilf(t));
+    return c > min_count ? c : min_count;
+}
+
+// vcrt_sample_counts_pass: element-wise over a grid-stride loop; a wave adds its counts to the
+// block's tally slot.
+constexpr uint32_t kSampleCountThreads = 256;
+constexpr uint32_t kSampleCountTallySlots = 256;
+constexpr uint32_t kSampleCountMaxBlocks = 4096;
+
+struct SampleCountParams {
+    const float* variance;  // [elements]
+    uint16_t* counts;       // [elements]
+    uint32_t elements;      // <= 2^31
+    float k;                // 1 / target^2
+    uint32_t min_count, max_count;
+    unsigned long long* tallies;  // [kSampleCountTallySlots][8]: [0] the sum of the counts
 };
 
 }  // namespace vcrt

@@ -326,6 +326,65 @@ struct MotionParams {
                                   //   zeroed before the launch, summed by the host
 };
 
+// Adaptive sampling (vcrt_draw_samples): per local pixel n_p = min(counts, max_count) further
+// samples of the frame's own rays, in quanta of kSampleQuantum. Three kernels share the tables:
+//   offsets [total_pixels]  the index of each local slot's first item (exclusive prefix of its
+//                           quanta, 0 for slots outside the frame)
+//   items   [items]         (local slot q, quantum k | samples of the quantum << 16)
+//   scratch [items]         (S_k.rgb, samples of the quantum), written by the tracer
+constexpr uint32_t kSampleQuantum = 4;       // vcrt_work_quantum's base
+constexpr uint32_t kSampleMaxCount = 256;    // counts are clamped to max_count <= this
+constexpr uint32_t kSampleScanBlock = 256;   // threads of vcrt_sample_scan
+constexpr uint32_t kSampleScanSlots = 1024;  // local slots per block: four per thread
+constexpr uint64_t kSampleMaxItems = uint64_t{1} << 28;
+
+// vcrt_sample_scan, launched three times: phase 0, one block per kSampleScanSlots local slots,
+// writes block_sums; phase 1, one block, turns block_sums' quanta into their exclusive prefix
+// (modulo 2^32: the host refuses more than kSampleMaxItems before anything reads it) and writes
+// the totals; phase 2, phase 0's grid, writes offsets and items.
+struct SampleScanParams {
+    const uint16_t* counts;  // [elements] the caller's plane, rank-local framebuffer layout
+    uint4* block_sums;       // [blocks] (quanta, samples, pixels with n_p > 0, 0)
+    unsigned long long* totals;  // [4] samples, pixels, items, 0
+    uint32_t* offsets;       // [total_pixels]
+    uint2* items;            // [items]; phase 2 only
+    uint32_t phase, blocks;
+    uint32_t max_count;
+    uint32_t total_pixels;   // local_tiles * 64
+    int32_t width, height, rank, world;
+    uint32_t tiles_x;
+};
+
+// vcrt_trace_samples: a persistent grid over the items; a lane runs its item's paths one after
+// another. The scene block is filled as FeatureParams' is, with the frame's max_depth and the
+// call's jitter and lens tables of [first, first + max_count), indexed from 0.
+struct SampleTraceParams {
+    TraceParams scene;
+    const uint2* items;
+    float4* scratch;
+    uint32_t count;        // items, <= kSampleMaxItems
+    uint32_t use_lists;    // as FeatureParams.use_lists
+    uint32_t* work;        // the next item to hand out, zeroed before the launch (it ends below
+                           //   count + 64 * the grid's waves)
+    unsigned long long* tallies;  // [kFeatureTallySlots][8]: per slot (64 B), [0] .. [2] as
+                                  //   FeatureParams.tallies, [3] segments; zeroed before the launch
+};
+
+// vcrt_sample_resolve: one lane per local slot adds its S_k in ascending k and applies the
+// accumulate rule (vcrt.h vcrt_draw_samples).
+struct SampleResolveParams {
+    const uint16_t* counts;
+    const uint32_t* offsets;
+    const float4* scratch;
+    float4* sums;          // [elements]
+    float4* mean;          // [elements], or null
+    uint32_t max_count;
+    uint32_t accumulate;
+    uint32_t total_pixels;
+    int32_t width, height, rank, world;
+    uint32_t tiles_x;
+};
+
 // TraceParams.jitter from the host's jitter (vcrt_math.h rand2) and the camera: run at
 // vcrt_begin and for each progressive frame.
 struct SetupJitterParams {

@@ -12,6 +12,10 @@
 // --variance (a flag; needs --temporal and --denoise) runs the variance-guided chain instead: every
 // frame, the first included, goes through vcrt_reproject_moments with the frame's albedo, and the
 // denoiser is vcrt_denoise_variance steered by vcrt_variance of the last frame's moments.
+// --adaptive N0,TARGET,MAX with --adaptive-out FILE runs one adaptive-sampling loop on the last
+// frame's camera (vcrt_draw_samples, vcrt_sample_counts) and writes its mean plane: two uniform
+// rounds of N0 samples into one sums plane, the per-sample luminance variance estimated from the
+// means after the first and after both rounds, then one round of the counts that variance asks for.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -32,7 +36,17 @@ int usage() {
                  "[--lens-radius R] [--orbit DEG] [--out file.ppm|file.pfm] "
                  "[--features PREFIX] [--feature-samples N] [--ao PREFIX] [--ao-rays M] "
                  "[--denoise file.ppm|file.pfm] [--denoise-levels L] "
-                 "[--temporal file.ppm|file.pfm] [--variance]\n");
+                 "[--temporal file.ppm|file.pfm] [--variance] "
+                 "[--adaptive N0,TARGET,MAX --adaptive-out file.ppm|file.pfm]\n"
+                 "  --adaptive: per pixel, two uniform rounds of N0 samples (sample indices 0 .. "
+                 "2 N0 - 1), then up to MAX more.\n"
+                 "    Variance estimator: with Y1 the luminance of the mean after round one and "
+                 "Y12 after both,\n"
+                 "    d = Y12 - Y1 estimates the deviation of the 2 N0-sample mean, so a sample's "
+                 "variance is about\n"
+                 "    v = d * d * (2 N0); the third round takes clamp(ceil(v / TARGET^2), 0, MAX) "
+                 "samples per pixel:\n"
+                 "    the count at which the mean's standard deviation reaches TARGET.\n");
     return 2;
 }
 
@@ -52,6 +66,12 @@ bool write_image(const std::string& path, int width, int height, bool pfm,
     return std::fclose(f) == 0;
 }
 
+inline float lum(const float* c) {  // vcrt.h's lum, one rounded operation per step
+    float y = 0.2126f * c[0] + 0.7152f * c[1];
+    y = y + 0.0722f * c[2];
+    return y;
+}
+
 uint8_t unit_byte(float v) {  // clamp to [0, 1] (NaN: 0), round to nearest of 255 v
     return static_cast<uint8_t>((v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f) * 255.0f + 0.5f);
 }
@@ -63,7 +83,9 @@ int main(int argc, char** argv) {
     vcrt_default_desc(&desc);
     int scene = VCRT_SCENE_FINAL, frames = 1;
     double orbit = 0.0;  // degrees about the world y axis through lookat, per frame
-    std::string out, features, ao, denoise, temporal;
+    std::string out, features, ao, denoise, temporal, adaptive_out;
+    int adaptive_n0 = 0, adaptive_max = 0;  // --adaptive N0,TARGET,MAX (n0 0: off)
+    float adaptive_target = 0.0f;
     int denoise_levels = 0;   // 0: vcrt_default_denoise_params'
     int feature_samples = 0;  // 0: the description's spp
     int ao_rays = 8;          // secondary rays per sample that hits
@@ -80,7 +102,8 @@ int main(int argc, char** argv) {
         configured = configured || (a != "--out" && a != "--frames" && a != "--features" &&
                                     a != "--feature-samples" && a != "--ao" && a != "--ao-rays" &&
                                     a != "--denoise" && a != "--denoise-levels" &&
-                                    a != "--temporal");
+                                    a != "--temporal" && a != "--adaptive" &&
+                                    a != "--adaptive-out");
         if (a == "--width") desc.width = std::atoi(v);
         else if (a == "--height") desc.height = std::atoi(v);
         else if (a == "--spp") desc.samples_per_pixel = std::atoi(v);
@@ -98,6 +121,13 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise = v;
         else if (a == "--denoise-levels") denoise_levels = std::atoi(v);
         else if (a == "--temporal") temporal = v;
+        else if (a == "--adaptive-out") adaptive_out = v;
+        else if (a == "--adaptive") {
+            if (std::sscanf(v, "%d,%f,%d", &adaptive_n0, &adaptive_target, &adaptive_max) != 3 ||
+                adaptive_n0 < 1 || adaptive_n0 > 256 || adaptive_max < 1 || adaptive_max > 256 ||
+                !(adaptive_target > 0.0f))
+                return usage();
+        }
         else if (a == "--scene") {
             const std::string s = v;
             scene = s == "final" ? VCRT_SCENE_FINAL : s == "three" ? VCRT_SCENE_THREE
@@ -107,6 +137,10 @@ int main(int argc, char** argv) {
     }
     if (variance && (temporal.empty() || denoise.empty())) {
         std::fprintf(stderr, "--variance needs --temporal and --denoise\n");
+        return usage();
+    }
+    if ((adaptive_n0 != 0) != !adaptive_out.empty()) {
+        std::fprintf(stderr, "--adaptive and --adaptive-out go together\n");
         return usage();
     }
     // Without options this is the reference's main() exactly: Begin/Draw/End with nothing set,
@@ -320,6 +354,54 @@ int main(int argc, char** argv) {
             }
         } else {
             std::fprintf(stderr, "Denoise: %s\n", vcrt_result_string(r));
+        }
+    }
+    if (r == VK_SUCCESS && adaptive_n0 != 0) {
+        const bool pfm = adaptive_out.size() > 4 &&
+                         adaptive_out.compare(adaptive_out.size() - 4, 4, ".pfm") == 0;
+        const size_t n = static_cast<size_t>(desc.width) * desc.height;
+        const uint32_t n0 = static_cast<uint32_t>(adaptive_n0);
+        std::vector<uint16_t> counts(n, static_cast<uint16_t>(n0));
+        std::vector<float> sums(4 * n), mean1(4 * n), mean(4 * n), var(n);
+        // two uniform rounds into one sums plane: the means after the first and after both
+        r = DrawSamples(0, n0, counts.data(), 0, sums.data(), mean1.data());
+        if (r == VK_SUCCESS) r = DrawSamples(n0, n0, counts.data(), 1, sums.data(), mean.data());
+        uint64_t total = 0;
+        if (r == VK_SUCCESS) {
+            const float scale = 2.0f * static_cast<float>(n0);
+            for (size_t i = 0; i < n; i++) {
+                const float d = lum(&mean[4 * i]) - lum(&mean1[4 * i]);
+                const float dd = d * d;
+                var[i] = dd * scale;
+            }
+            vcrt_sample_count_params cp;
+            cp.struct_size = sizeof(cp);
+            cp.target = adaptive_target;
+            cp.min_count = 0;
+            cp.max_count = static_cast<uint32_t>(adaptive_max);
+            r = SampleCounts(var.data(), static_cast<uint32_t>(n), &cp, counts.data(), &total);
+        }
+        if (r == VK_SUCCESS)
+            r = DrawSamples(2u * n0, static_cast<uint32_t>(adaptive_max), counts.data(), 1,
+                            sums.data(), mean.data());
+        if (r == VK_SUCCESS) {
+            std::printf("adaptive: %u + %u uniform samples per pixel, %llu adaptive samples "
+                        "(%.2f per pixel)\n", n0, n0, static_cast<unsigned long long>(total),
+                        static_cast<double>(total) / static_cast<double>(n));
+            std::vector<uint8_t> c8(pfm ? 0 : 4 * n);
+            if (!pfm) {
+                float th[255];
+                vcrt_srgb8_thresholds(th);
+                for (size_t i = 0; i < 4 * n; i++)
+                    c8[i] = static_cast<uint8_t>(std::upper_bound(th, th + 255, mean[i]) - th);
+            }
+            if (!write_image(adaptive_out, desc.width, desc.height, pfm, mean, c8)) {
+                std::fprintf(stderr, "cannot write %s: %s\n", adaptive_out.c_str(),
+                             std::strerror(errno));
+                r = VK_ERROR_UNKNOWN;
+            }
+        } else {
+            std::fprintf(stderr, "adaptive: %s\n", vcrt_result_string(r));
         }
     }
     EndRenderingOperation();

@@ -517,6 +517,57 @@ def variance_host(moments, surface, **params) -> np.ndarray:
     return out
 
 
+SAMPLE_MAX_COUNT = 256  # vcrt_draw_samples' and vcrt_sample_counts' largest max_count
+
+
+def _sample_count_params(target, min_count, max_count) -> N.vcrt_sample_count_params:
+    """vcrt_sample_counts' parameters, validated before any native call."""
+    try:
+        target, min_count, max_count = float(target), int(min_count), int(max_count)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"target, min_count, max_count: numbers expected ({e})") from None
+    if not (target > 0.0 and np.isfinite(target)):
+        raise ValueError("target must be positive and finite")
+    if not 0 <= min_count <= max_count <= SAMPLE_MAX_COUNT:
+        raise ValueError(f"0 <= min_count <= max_count <= {SAMPLE_MAX_COUNT} expected")
+    p = N.vcrt_sample_count_params()
+    p.struct_size = ctypes.sizeof(N.vcrt_sample_count_params)
+    p.target, p.min_count, p.max_count = target, min_count, max_count
+    return p
+
+
+def _check_count_elements(n: int) -> None:
+    if not 1 <= n <= 1 << 31:
+        raise ValueError("variance: 1 .. 2^31 elements expected")
+
+
+def _variance_plane(variance) -> np.ndarray:
+    try:
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"variance: not convertible to a float32 array ({e})") from None
+    _check_count_elements(variance.size)
+    return variance
+
+
+def sample_counts_host(variance, target: float, min_count: int = 0, max_count: int = 64,
+                       stats: bool = False):
+    """The count plane of Renderer.draw_samples from a variance plane, the definition on the
+    host (vcrt_sample_counts_host: no GPU): counts[e] = max(c, min_count) with t = max(variance[e],
+    0) * (1 / target^2) and c = max_count if t >= max_count else ceil(t), uint16 in variance's
+    shape; Renderer.sample_counts computes the same bits on the GPU. With stats=True the result
+    is (counts, total)."""
+    if _is_torch(variance):
+        raise ValueError("sample_counts_host takes a numpy plane")
+    p = _sample_count_params(target, min_count, max_count)
+    variance = _variance_plane(variance)
+    out = np.empty(variance.shape, np.uint16)
+    st = N.vcrt_sample_count_stats()
+    N.check("vcrt_sample_counts_host", N.lib().vcrt_sample_counts_host(
+        variance.ctypes.data, variance.size, ctypes.byref(p), out.ctypes.data, ctypes.byref(st)))
+    return (out, st.total) if stats else out
+
+
 def denoise_variance_host(colour, variance, albedo=None, normal_depth=None, **params):
     """The variance-steered denoiser's definition on the host (vcrt_denoise_variance_host: no
     GPU) over numpy planes: (out [height, width, 4], out_variance [height, width]);
@@ -1327,6 +1378,125 @@ class Renderer:
         if self.desc.device >= 0 and plane.device.index != self.desc.device:
             raise ValueError(f"planes on {plane.device}, the renderer on device "
                              f"{self.desc.device}")
+
+    def draw_samples(self, counts, first: int = 0, max_count: int | None = None, sums=None,
+                     mean: bool = True, stats: bool = False, *, accumulate: bool | None = None):
+        """Adaptive sampling (vcrt_draw_samples): for every local pixel p, n_p = min(counts[p],
+        max_count) further samples of the frame's own rays, the sample indices first .. first +
+        n_p - 1, traced on the GPU and summed in vcrt.h's fixed order (quanta of four).
+
+        counts is an integer plane in the rank-local framebuffer's leading shape ([height, width]
+        at world 1, else the packed tiles [tiles, 64]): a numpy array (converted to uint16) or a
+        torch uint16 / int16 tensor on the renderer's device, which goes in without a host trip
+        after the caller's current stream is synchronised. max_count=None is 256, the most the
+        call accepts. sums=None starts a fresh plane; a given float32 [..., 4] plane (numpy, or
+        a tensor like counts) is updated in place: added to, or overwritten with
+        accumulate=False. A round that adds to a plane takes a `first` past the earlier rounds'
+        first + max_count. Returns a dict: "sums" (rgb the radiance sum, a the sample count),
+        "mean" when asked for (rgb / a, alpha 1; zeros where a pixel has no sample yet) and, with
+        stats=True, "stats": pixels, samples, items, segments, listed_rays, group_tests,
+        bound_tests, scan_ms, kernel_ms, resolve_ms, host_ms, kernel. Argument errors raise
+        ValueError before any native call. The framebuffer, the accumulation and the frame
+        statistics are left alone."""
+        max_count = SAMPLE_MAX_COUNT if max_count is None else max_count
+        first, max_count = _check_sample_range(first, max_count)
+        if max_count > SAMPLE_MAX_COUNT:
+            raise ValueError(f"max_count must not exceed {SAMPLE_MAX_COUNT}")
+        lib = self._L()
+        elems, tiles = self.local_layout()
+        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
+                else (tiles, 64))
+        on_device = _is_torch(counts)
+        if sums is not None and _is_torch(sums) != on_device:
+            raise ValueError("counts and sums must both be numpy arrays or both torch tensors")
+        if accumulate is None:
+            accumulate = sums is not None
+        if accumulate and sums is None:
+            raise ValueError("accumulate: a sums plane expected")
+        st = N.vcrt_sample_stats()
+        if on_device:
+            import torch
+            if counts.dtype not in (torch.uint16, torch.int16) or not counts.is_cuda \
+                    or not counts.is_contiguous():
+                raise ValueError("counts: a contiguous uint16 (or int16) CUDA tensor expected")
+            self._same_device(counts)
+            if tuple(counts.shape) != lead:
+                raise ValueError(f"counts: shape {lead} expected, got {tuple(counts.shape)}")
+            if sums is None:
+                sums = torch.zeros(lead + (4,), dtype=torch.float32, device=counts.device)
+            elif (sums.dtype != torch.float32 or not sums.is_cuda or not sums.is_contiguous()
+                  or sums.device != counts.device or tuple(sums.shape) != lead + (4,)):
+                raise ValueError(f"sums: a contiguous float32 CUDA tensor {lead + (4,)} on "
+                                 "counts' device expected")
+            mean_plane = (torch.zeros(lead + (4,), dtype=torch.float32, device=counts.device)
+                          if mean else None)
+            torch.cuda.current_stream(counts.device).synchronize()
+            fn, name = lib.vcrt_draw_samples_device, "vcrt_draw_samples_device"
+        else:
+            try:
+                c = np.asarray(counts)
+                if c.dtype.kind not in "iu":
+                    raise TypeError(f"dtype {c.dtype}")
+                if c.size and (c.min() < 0 or c.max() > 65535):
+                    raise ValueError("values outside 0 .. 65535")
+                counts = np.ascontiguousarray(c, dtype=np.uint16)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"counts: an integer plane expected ({e})") from None
+            if counts.shape != lead:
+                raise ValueError(f"counts: shape {lead} expected, got {counts.shape}")
+            if sums is None:
+                sums = np.zeros(lead + (4,), np.float32)
+            elif (not isinstance(sums, np.ndarray) or sums.dtype != np.float32
+                  or not sums.flags.c_contiguous or not sums.flags.writeable
+                  or sums.shape != lead + (4,)):
+                raise ValueError(f"sums: a writeable C-contiguous float32 array {lead + (4,)} "
+                                 "expected")
+            mean_plane = np.zeros(lead + (4,), np.float32) if mean else None
+            fn, name = lib.vcrt_draw_samples, "vcrt_draw_samples"
+        N.check(name, fn(first, max_count, _ptr(counts), 1 if accumulate else 0, _ptr(sums),
+                         _ptr(mean_plane), ctypes.byref(st)))
+        out = {"sums": sums}
+        if mean:
+            out["mean"] = mean_plane
+        if stats:
+            out["stats"] = {k: getattr(st, k) for k in
+                            ("pixels", "samples", "items", "segments", "listed_rays",
+                             "group_tests", "bound_tests", "scan_ms", "kernel_ms", "resolve_ms",
+                             "host_ms")}
+            out["stats"]["kernel"] = st.kernel.decode()
+        return out
+
+    def sample_counts(self, variance, target: float, min_count: int = 0, max_count: int = 64,
+                      stats: bool = False):
+        """A count plane for draw_samples from a variance plane (vcrt_sample_counts), on the
+        GPU the bits sample_counts_host computes: counts = clamp(ceil(max(variance, 0) /
+        target^2), min_count, max_count) as uint16 in variance's shape. variance is a float32
+        numpy array or a contiguous torch CUDA tensor (filled through the device call, no host
+        trip). With stats=True the result is (counts, stats dict): total (the sum of the
+        counts), kernel_ms, host_ms, kernel."""
+        lib = self._L()
+        p = _sample_count_params(target, min_count, max_count)
+        st = N.vcrt_sample_count_stats()
+        if _is_torch(variance):
+            import torch
+            if variance.dtype != torch.float32 or not variance.is_cuda \
+                    or not variance.is_contiguous():
+                raise ValueError("variance: a contiguous float32 CUDA tensor expected")
+            self._same_device(variance)
+            _check_count_elements(variance.numel())
+            out = torch.empty(tuple(variance.shape), dtype=torch.uint16, device=variance.device)
+            torch.cuda.current_stream(variance.device).synchronize()
+            fn, name, n = lib.vcrt_sample_counts_device, "vcrt_sample_counts_device", \
+                variance.numel()
+        else:
+            variance = _variance_plane(variance)
+            out = np.empty(variance.shape, np.uint16)
+            fn, name, n = lib.vcrt_sample_counts, "vcrt_sample_counts", variance.size
+        N.check(name, fn(_ptr(variance), n, ctypes.byref(p), _ptr(out), ctypes.byref(st)))
+        if stats:
+            return out, {"total": st.total, "kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
+                         "kernel": st.kernel.decode()}
+        return out
 
     def reproject_moments(self, frame, motion, history=None, *, surface=None, albedo=None,
                           alpha=None, max_history=None, depth_tolerance=None,
