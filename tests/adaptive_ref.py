@@ -53,21 +53,32 @@ def pixel_sum(r):
     return s_p
 
 
-def draw_samples(oracle, scene, desc, counts, first, max_count, sums=None):
+def draw_samples(oracle, scene, desc, counts, first, max_count, sums=None, sparse=False):
     """The whole frame's planes: (sums [H, W, 4], mean [H, W, 4], stats) for a count plane
     [H, W]. sums=None: accumulate == 0; else the old plane, which is accumulated into a copy.
-    stats: samples, pixels, items, segments."""
+    stats: samples, pixels, items, segments. sparse: the batch of low sample indices covers the
+    pixels with a sample only, and only the indices they use (a large frame with few such
+    pixels, a `first` whose first + LOW would pass the largest index); the planes are the same."""
     h, w = desc.height, desc.width
     n = clamp_counts(counts, max_count).reshape(-1)
     out = (np.zeros((h * w, 4), F) if sums is None
            else np.array(sums, F, copy=True).reshape(h * w, 4))
     # every pixel's first LOW indices in one batch that the count planes share, the rest per pixel
     low = LOW if n.max() > 0 else 0
-    rad, segs = radiance(oracle, scene, desc, first, low) if low else (None, None)
+    row = None  # pixel -> row of the batch (None: the pixel itself)
+    if sparse and low:
+        some = np.flatnonzero(n)
+        few = n[some][n[some] <= LOW]
+        low = int(few.max()) if few.size else 0
+        row = np.full(h * w, -1, np.int64)
+        row[some] = np.arange(len(some))
+    rad, segs = (radiance(oracle, scene, desc, first, low, pixels=None if row is None else some)
+                 if low else (None, None))
     nseg = 0
     for p in np.flatnonzero(n):
         if n[p] <= low:
-            r, sg = rad[p, :n[p]], segs[p, :n[p]]
+            q = p if row is None else row[p]
+            r, sg = rad[q, :n[p]], segs[q, :n[p]]
         else:
             r, sg = radiance(oracle, scene, desc, first, int(n[p]), pixels=[p])
             r, sg = r[0], sg[0]
