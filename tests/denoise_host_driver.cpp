@@ -1,9 +1,11 @@
 // Runs the kernels of csrc/denoise.hip on the host (tests/denoise_host/hip/hip_runtime.h) over
-// seeded planes and compares the result with vcrt_denoise_host word for word. The passes are
-// sequenced as capi.cpp's denoise_device sequences them. The direct kernel runs one thread at a
-// time; the LDS kernel's workgroup runs as 256 threads around a barrier.
+// seeded planes and compares the result with vcrt_denoise_host word for word. The launches are
+// the library's own: csrc/image_pass_plan.hpp's denoise_plan, as image_passes.cpp runs it. The
+// direct kernel runs one thread at a time; the LDS kernel's workgroup runs as 256 threads around a
+// barrier.
 //   denoise_host_driver W H levels sn sd sa sc demodulate lds_passes albedo(0|1) guides(0|1)
 // prints "bad <words that differ> pixels <W H> lds <passes run by the LDS kernel>".
+#include <algorithm>
 #include <barrier>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "denoise.hip"
+#include "image_pass_plan.hpp"
 #include "vcrt.h"
 
 dim3e blockIdx{0, 0, 0};
@@ -67,42 +70,21 @@ int main(int argc, char** argv) {
     if (vcrt_denoise_host(colour.data(), albedo, guides, w, h, &pr, want.data()) != VCRT_SUCCESS)
         return 3;
 
-    const bool demod = pr.demodulate != 0 && albedo;
-    uint32_t terms = 0;
-    if (guides && k4[0] != 0.0f) terms |= vcrt::kDenoiseNormal;
-    if (guides && k4[1] != 0.0f) terms |= vcrt::kDenoiseDepth;
-    if (albedo && k4[2] != 0.0f) terms |= vcrt::kDenoiseAlbedo;
-    float kl = k4[3];
-    const float* in = colour.data();
-    int lds_run = 0;
-    for (int l = 0; l < pr.levels; l++) {
-        const bool last = l == pr.levels - 1;
-        if (!last) scratch[l & 1].assign(words, -2.0f);
-        vcrt::DenoiseParams p{};
-        p.in = in;
-        p.colour = colour.data();
-        p.albedo = albedo;
-        p.normal_depth = guides;
-        p.out = last ? got.data() : scratch[l & 1].data();
-        p.width = static_cast<uint32_t>(w);
-        p.height = static_cast<uint32_t>(h);
-        p.step = 1u << l;
-        p.flags = terms | (kl != 0.0f ? vcrt::kDenoiseColour : 0u) |
-                  (demod && l == 0 ? vcrt::kDenoiseDemodIn : 0u) |
-                  (demod && last ? vcrt::kDenoiseModOut : 0u) | (last ? vcrt::kDenoiseLast : 0u);
-        p.k_normal = k4[0];
-        p.k_depth = k4[1];
-        p.k_albedo = k4[2];
-        p.kl = kl;
-        if (l < lds_passes && p.step <= vcrt::kDenoiseLdsMaxStep) {
-            lds_run++;
-            p.tiles_x = (p.width + vcrt::kDenoiseTileW - 1u) / vcrt::kDenoiseTileW;
-            const uint32_t tiles_y = (p.height + vcrt::kDenoiseTileH - 1u) / vcrt::kDenoiseTileH;
-            for (uint32_t b = 0; b < p.tiles_x * tiles_y; b++) {
+    for (std::vector<float>& s : scratch) s.resize(words);
+    float* const planes[2] = {scratch[0].data(), scratch[1].data()};
+    const vcrt::AtrousPlan<vcrt::DenoiseParams> plan = vcrt::denoise_plan(
+        colour.data(), albedo, guides, w, h, pr, k4, planes, lds_passes, got.data());
+    for (int l = 0; l < plan.passes; l++) {
+        const vcrt::PassLaunch<vcrt::DenoiseParams>& launch = plan.pass[l];
+        const vcrt::DenoiseParams p = launch.params;
+        if (p.out != got.data()) std::fill(p.out, p.out + words, -2.0f);
+        if (launch.lds) {
+            if (launch.lds_bytes > sizeof(l_planes)) return 5;
+            for (uint32_t b = 0; b < launch.grid; b++) {
                 blockIdx.x = b;
                 for (float4& v : l_planes) v = make_float4(-3.f, -3.f, -3.f, -3.f);
                 std::vector<std::thread> group;
-                for (uint32_t t = 0; t < vcrt::kDenoiseThreads; t++)
+                for (uint32_t t = 0; t < launch.block; t++)
                     group.emplace_back([t, p] {
                         threadIdx.x = t;
                         vcrt_denoise_pass_lds(p);
@@ -110,20 +92,16 @@ int main(int argc, char** argv) {
                 for (std::thread& t : group) t.join();
             }
         } else {
-            p.tiles_x = (p.width + vcrt::kDenoiseRowW - 1u) / vcrt::kDenoiseRowW;
-            const uint32_t tiles_y = (p.height + vcrt::kDenoiseRowH - 1u) / vcrt::kDenoiseRowH;
-            for (uint32_t b = 0; b < p.tiles_x * tiles_y; b++)
-                for (uint32_t t = 0; t < vcrt::kDenoiseThreads; t++) {
+            for (uint32_t b = 0; b < launch.grid; b++)
+                for (uint32_t t = 0; t < launch.block; t++) {
                     blockIdx.x = b;
                     threadIdx.x = t;
                     vcrt_denoise_pass(p);
                 }
         }
-        in = p.out;
-        kl = kl * 4.0f;
     }
     size_t bad = 0;
     for (size_t i = 0; i < words; i++) bad += std::memcmp(&got[i], &want[i], 4) != 0;
-    std::printf("bad %zu pixels %d lds %d\n", bad, w * h, lds_run);
+    std::printf("bad %zu pixels %d lds %d\n", bad, w * h, plan.lds_passes);
     return 0;
 }

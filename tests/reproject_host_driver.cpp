@@ -1,7 +1,8 @@
 // Runs the kernel of csrc/reproject.hip on the host (tests/reproject_host/hip/hip_runtime.h), one
-// thread at a time over the launch capi.cpp's reproject_device makes, on planes read from a file
-// and held in exactly sized heap blocks (so a sanitizer build sees any read outside them), and
-// compares the result with vcrt_reproject_host word for word.
+// thread at a time over the launch the library makes (csrc/image_pass_plan.hpp's reproject_plan,
+// as image_passes.cpp runs it), on planes read from a file and held in exactly sized heap blocks
+// (so a sanitizer build sees any read outside them), and compares the result with
+// vcrt_reproject_host word for word.
 //   reproject_host_driver PLANES W H alpha max_history depth_tolerance
 // PLANES: raw float32 -- colour, motion, history colour, history surface [H][W][4] each, then
 // history length [H][W]. Prints "bad <words that differ> pixels <W H> accepted <tally> want
@@ -11,6 +12,7 @@
 #include <cstring>
 #include <memory>
 
+#include "image_pass_plan.hpp"
 #include "reproject.hip"
 #include "vcrt.h"
 
@@ -45,27 +47,15 @@ int main(int argc, char** argv) {
     std::unique_ptr<unsigned long long[]> tallies(
         new unsigned long long[8 * vcrt::kReprojectTallySlots]());
 
-    vcrt::ReprojectParams p{};
-    p.colour = in[0].get();
-    p.motion = in[1].get();
-    p.history_colour = in[2].get();
-    p.history_surface = in[3].get();
-    p.history_length = in[4].get();
-    p.out = got.get();
-    p.out_length = got_len.get();
-    p.width = static_cast<uint32_t>(w);
-    p.height = static_cast<uint32_t>(h);
-    p.alpha = pr.alpha;
-    p.max_history = pr.max_history;
-    p.depth_tolerance = pr.depth_tolerance;
-    p.tiles_x = (p.width + vcrt::kReprojectRowW - 1u) / vcrt::kReprojectRowW;
-    p.tallies = tallies.get();
-    const uint32_t tiles_y = (p.height + vcrt::kReprojectRowH - 1u) / vcrt::kReprojectRowH;
-    for (uint32_t b = 0; b < p.tiles_x * tiles_y; b++)
-        for (uint32_t t = 0; t < vcrt::kReprojectThreads; t++) {
+    vcrt::PassLaunch<vcrt::ReprojectParams> launch =
+        vcrt::reproject_plan(in[0].get(), in[1].get(), in[2].get(), in[3].get(), in[4].get(), w, h,
+                             pr, got.get(), got_len.get());
+    launch.params.tallies = tallies.get();
+    for (uint32_t b = 0; b < launch.grid; b++)
+        for (uint32_t t = 0; t < launch.block; t++) {
             blockIdx.x = b;
             threadIdx.x = t;
-            vcrt_reproject_pass(p);
+            vcrt_reproject_pass(launch.params);
         }
     size_t bad = 0, blended = 0;
     unsigned long long accepted = 0;

@@ -1,8 +1,10 @@
 """The denoise kernels (csrc/denoise.hip) without a GPU: compiled for the host with g++ against a
 stand-in for the HIP runtime -- the direct kernel one thread at a time, the LDS kernel's workgroup
-as 256 threads around a barrier -- their planes equal vcrt_denoise_host's word for word. This pins
-the kernels' logic: the tap order, the skipped taps, the staged footprint's indexing, the fused
-demodulation and the ping-pong; tests/test_gpu_denoise.py pins the device's arithmetic."""
+as 256 threads around a barrier -- their planes equal vcrt_denoise_host's word for word. The
+driver runs the launches of csrc/image_pass_plan.hpp's denoise_plan, the ones the library makes
+(csrc/image_passes.cpp). This pins the kernels' logic and the library's sequencing: the tap order,
+the skipped taps, the staged footprint's indexing, the fused demodulation, the flags, the grids
+and the ping-pong; tests/test_gpu_denoise.py pins the device's arithmetic."""
 import os
 import subprocess
 

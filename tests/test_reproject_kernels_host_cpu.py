@@ -1,8 +1,9 @@
 """The temporal accumulation kernel (csrc/reproject.hip) without a GPU: compiled for the host with
 g++ against a stand-in for the HIP runtime and run one thread at a time over the generated planes
 of tests/reproject_ref -- motion that points outside the frame on every side, partial taps,
-integers, NaN, infinities, 1e30 -- its planes equal vcrt_reproject_host's word for word. The same
-driver, a stand-alone program, also runs built with -fsanitize=address,undefined over exactly sized
+integers, NaN, infinities, 1e30 -- its planes equal vcrt_reproject_host's word for word. The
+driver runs the launch of csrc/image_pass_plan.hpp's reproject_plan, the one the library makes
+(csrc/image_passes.cpp). The same driver, a stand-alone program, also runs built with -fsanitize=address,undefined over exactly sized
 heap planes: this is where "no plane is read outside the frame" is pinned.
 tests/test_gpu_reproject.py pins the device's arithmetic."""
 import os

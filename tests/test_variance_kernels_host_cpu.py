@@ -1,7 +1,9 @@
 """The variance-guided kernels (csrc/variance.hip) without a GPU: compiled for the host with g++
 against a stand-in for the HIP runtime and run over the generated planes of tests/variance_ref --
 the direct kernels one thread at a time, the LDS kernel's workgroup as 256 threads around a
-barrier -- their planes equal the _host functions' word for word. The same driver, a stand-alone
+barrier -- their planes equal the _host functions' word for word. The driver runs the launches of
+csrc/image_pass_plan.hpp's plans, the ones the library makes (csrc/image_passes.cpp), so the
+library's own sequencing is what is checked against the definitions. The same driver, a stand-alone
 program, also runs built with -fsanitize=address,undefined over exactly sized heap planes: this is
 where "no plane is read outside the frame" is pinned for the new planes.
 tests/test_gpu_variance.py pins the device's arithmetic."""

@@ -1,6 +1,7 @@
 // Runs the kernels of csrc/variance.hip on the host (tests/variance_host/hip/hip_runtime.h) over
-// the launches capi.cpp makes, on planes read from a file and held in exactly sized heap blocks (so
-// a sanitizer build sees any read outside them), and compares the results with the _host functions
+// the launches the library makes (csrc/image_pass_plan.hpp's plans, as image_passes.cpp runs
+// them), on planes read from a file and held in exactly sized heap blocks (so a sanitizer build
+// sees any read outside them), and compares the results with the _host functions
 // of csrc/variance.cpp word for word. The direct kernels run one thread at a time; the LDS kernel's
 // workgroup runs as 256 threads around a barrier.
 //   variance_host_driver PLANES W H moments  alpha max_history depth_tolerance alpha_moments albedo(0|1)
@@ -19,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "image_pass_plan.hpp"
 #include "variance.hip"
 #include "vcrt.h"
 
@@ -44,14 +46,34 @@ size_t differing(const Plane& a, const Plane& b, size_t words) {
     return bad;
 }
 
+// a direct kernel's launch, one thread at a time
 template <class Kernel, class Params>
-void run_rows(Kernel kernel, const Params& p, uint32_t blocks, uint32_t threads) {
-    for (uint32_t b = 0; b < blocks; b++)
-        for (uint32_t t = 0; t < threads; t++) {
+void run_rows(Kernel kernel, const vcrt::PassLaunch<Params>& l) {
+    for (uint32_t b = 0; b < l.grid; b++)
+        for (uint32_t t = 0; t < l.block; t++) {
             blockIdx.x = b;
             threadIdx.x = t;
-            kernel(p);
+            kernel(l.params);
         }
+}
+
+// an LDS kernel's launch: each workgroup as its threads around the barrier, over a stand-in for
+// the dynamic LDS that the launch's byte count must fit
+template <class Kernel, class Params>
+void run_group(Kernel kernel, const vcrt::PassLaunch<Params>& l) {
+    if (l.lds_bytes > sizeof(l_var_planes) || l.block != vcrt::kDenoiseThreads) std::exit(5);
+    const Params p = l.params;
+    for (uint32_t b = 0; b < l.grid; b++) {
+        blockIdx.x = b;
+        for (float4& v : l_var_planes) v = make_float4(-4.f, -4.f, -4.f, -4.f);
+        std::vector<std::thread> group;
+        for (uint32_t t = 0; t < l.block; t++)
+            group.emplace_back([t, p, kernel] {
+                threadIdx.x = t;
+                kernel(p);
+            });
+        for (std::thread& t : group) t.join();
+    }
 }
 
 enum { kColour, kMotion, kHcol, kHsurf, kHlen, kAlbedo, kNd, kHmom, kMoments, kSurface, kVar, kPlanes };
@@ -96,27 +118,12 @@ int main(int argc, char** argv) {
             return 4;
         std::unique_ptr<unsigned long long[]> tallies(
             new unsigned long long[8 * vcrt::kMomentsTallySlots]());
-        vcrt::ReprojectMomentsParams p{};
-        p.colour = in[kColour].get();
-        p.motion = in[kMotion].get();
-        p.history_colour = in[kHcol].get();
-        p.history_surface = in[kHsurf].get();
-        p.history_length = in[kHlen].get();
-        p.albedo = albedo;
-        p.history_moments = in[kHmom].get();
-        p.out = got.get();
-        p.out_length = got_len.get();
-        p.out_moments = got_mom.get();
-        p.width = static_cast<uint32_t>(w);
-        p.height = static_cast<uint32_t>(h);
-        p.alpha = pr.alpha;
-        p.max_history = pr.max_history;
-        p.depth_tolerance = pr.depth_tolerance;
-        p.alpha_moments = pr.alpha_moments;
-        p.tiles_x = (p.width + vcrt::kMomentsRowW - 1u) / vcrt::kMomentsRowW;
-        p.tallies = tallies.get();
-        const uint32_t tiles_y = (p.height + vcrt::kMomentsRowH - 1u) / vcrt::kMomentsRowH;
-        run_rows(vcrt_reproject_moments_pass, p, p.tiles_x * tiles_y, vcrt::kMomentsThreads);
+        vcrt::PassLaunch<vcrt::ReprojectMomentsParams> launch = vcrt::reproject_moments_plan(
+            in[kColour].get(), in[kMotion].get(), in[kHcol].get(), in[kHsurf].get(),
+            in[kHlen].get(), albedo, in[kHmom].get(), w, h, pr, got.get(), got_len.get(),
+            got_mom.get());
+        launch.params.tallies = tallies.get();
+        run_rows(vcrt_reproject_moments_pass, launch);
         bad = differing(got, want, 4 * pixels) + differing(got_len, want_len, pixels) +
               differing(got_mom, want_mom, 4 * pixels);
         for (uint32_t s = 0; s < vcrt::kMomentsTallySlots; s++) tally += tallies[8 * s];
@@ -133,35 +140,14 @@ int main(int argc, char** argv) {
             return 4;
         std::unique_ptr<unsigned long long[]> tallies(
             new unsigned long long[8 * vcrt::kVarianceTallySlots]());
-        vcrt::VarianceParams p{};
-        p.moments = in[kMoments].get();
-        p.surface = in[kSurface].get();
-        p.variance = got.get();
-        p.width = static_cast<uint32_t>(w);
-        p.height = static_cast<uint32_t>(h);
-        p.min_history = pr.min_history;
-        p.alpha = pr.alpha;
-        p.tiles_x = (p.width + vcrt::kVarianceRowW - 1u) / vcrt::kVarianceRowW;
-        p.tallies = tallies.get();
-        const uint32_t tiles_y = (p.height + vcrt::kVarianceRowH - 1u) / vcrt::kVarianceRowH;
-        if (lds) {
-            lds_run = 1;
-            p.tiles_x = (p.width + vcrt::kVarianceTileW - 1u) / vcrt::kVarianceTileW;
-            const uint32_t rows = (p.height + vcrt::kVarianceTileH - 1u) / vcrt::kVarianceTileH;
-            for (uint32_t b = 0; b < p.tiles_x * rows; b++) {
-                blockIdx.x = b;
-                for (float4& v : l_var_planes) v = make_float4(-4.f, -4.f, -4.f, -4.f);
-                std::vector<std::thread> group;
-                for (uint32_t t = 0; t < vcrt::kVarianceThreads; t++)
-                    group.emplace_back([t, p] {
-                        threadIdx.x = t;
-                        vcrt_variance_pass_lds(p);
-                    });
-                for (std::thread& t : group) t.join();
-            }
-        } else {
-            run_rows(vcrt_variance_pass, p, p.tiles_x * tiles_y, vcrt::kVarianceThreads);
-        }
+        vcrt::PassLaunch<vcrt::VarianceParams> launch = vcrt::variance_plan(
+            in[kMoments].get(), in[kSurface].get(), w, h, pr, lds, got.get());
+        launch.params.tallies = tallies.get();
+        lds_run = launch.lds;
+        if (launch.lds)
+            run_group(vcrt_variance_pass_lds, launch);
+        else
+            run_rows(vcrt_variance_pass, launch);
         bad = differing(got, want, pixels);
         for (uint32_t s = 0; s < vcrt::kVarianceTallySlots; s++) tally += tallies[8 * s];
     } else if (call == "denoise") {
@@ -180,63 +166,25 @@ int main(int argc, char** argv) {
         const float* guides = std::atoi(argv[13]) ? in[kNd].get() : nullptr;
         Plane want = filled(4 * pixels, -1.f), want_var = filled(pixels, -1.f);
         Plane got = filled(4 * pixels, -2.f), got_var = filled(pixels, -2.f);
-        Plane scratch[2];
+        Plane scratch[2] = {filled(4 * pixels, -3.f), filled(4 * pixels, -3.f)};
         float k4[4];
         if (vcrt_denoise_scales(&pr, k4) != VCRT_SUCCESS) return 4;
         if (vcrt_denoise_variance_host(colour, albedo, guides, in[kVar].get(), w, h, &pr,
                                        want.get(), want_var.get()) != VCRT_SUCCESS)
             return 4;
-        const bool demod = pr.demodulate != 0 && albedo;
-        uint32_t terms = 0;
-        if (guides && k4[0] != 0.0f) terms |= vcrt::kDenoiseNormal;
-        if (guides && k4[1] != 0.0f) terms |= vcrt::kDenoiseDepth;
-        if (albedo && k4[2] != 0.0f) terms |= vcrt::kDenoiseAlbedo;
-        if (pr.sigma_colour != 0.0f) terms |= vcrt::kDenoiseColour;
-        const float* src = colour;
-        for (int l = 0; l < pr.levels; l++) {
-            const bool last = l == pr.levels - 1;
-            if (!last) scratch[l & 1] = filled(4 * pixels, -3.f);
-            vcrt::DenoiseVarParams p{};
-            p.in = src;
-            p.colour = colour;
-            p.albedo = albedo;
-            p.normal_depth = guides;
-            p.variance = in[kVar].get();
-            p.out = last ? got.get() : scratch[l & 1].get();
-            p.out_variance = got_var.get();
-            p.width = static_cast<uint32_t>(w);
-            p.height = static_cast<uint32_t>(h);
-            p.step = 1u << l;
-            p.flags = terms | (l == 0 ? vcrt::kDenoiseVarIn : 0u) |
-                      (demod && l == 0 ? vcrt::kDenoiseDemodIn : 0u) |
-                      (demod && last ? vcrt::kDenoiseModOut : 0u) |
-                      (last ? vcrt::kDenoiseLast : 0u);
-            p.k_normal = k4[0];
-            p.k_depth = k4[1];
-            p.k_albedo = k4[2];
-            p.sc2 = pr.sigma_colour * pr.sigma_colour;
-            if (l < lds_passes && p.step <= vcrt::kDenoiseLdsMaxStep) {
-                lds_run++;
-                p.tiles_x = (p.width + vcrt::kDenoiseTileW - 1u) / vcrt::kDenoiseTileW;
-                const uint32_t tiles_y =
-                    (p.height + vcrt::kDenoiseTileH - 1u) / vcrt::kDenoiseTileH;
-                for (uint32_t b = 0; b < p.tiles_x * tiles_y; b++) {
-                    blockIdx.x = b;
-                    for (float4& v : l_var_planes) v = make_float4(-4.f, -4.f, -4.f, -4.f);
-                    std::vector<std::thread> group;
-                    for (uint32_t t = 0; t < vcrt::kDenoiseThreads; t++)
-                        group.emplace_back([t, p] {
-                            threadIdx.x = t;
-                            vcrt_denoise_var_pass_lds(p);
-                        });
-                    for (std::thread& t : group) t.join();
-                }
-            } else {
-                p.tiles_x = (p.width + vcrt::kDenoiseRowW - 1u) / vcrt::kDenoiseRowW;
-                const uint32_t tiles_y = (p.height + vcrt::kDenoiseRowH - 1u) / vcrt::kDenoiseRowH;
-                run_rows(vcrt_denoise_var_pass, p, p.tiles_x * tiles_y, vcrt::kDenoiseThreads);
-            }
-            src = p.out;
+        float* const planes[2] = {scratch[0].get(), scratch[1].get()};
+        const vcrt::AtrousPlan<vcrt::DenoiseVarParams> plan = vcrt::denoise_variance_plan(
+            colour, albedo, guides, in[kVar].get(), w, h, pr, k4, planes, lds_passes, got.get(),
+            got_var.get());
+        lds_run = plan.lds_passes;
+        for (int l = 0; l < plan.passes; l++) {
+            const vcrt::PassLaunch<vcrt::DenoiseVarParams>& launch = plan.pass[l];
+            float* out = launch.params.out;
+            if (out != got.get()) std::fill(out, out + 4 * pixels, -3.f);
+            if (launch.lds)
+                run_group(vcrt_denoise_var_pass_lds, launch);
+            else
+                run_rows(vcrt_denoise_var_pass, launch);
         }
         bad = differing(got, want, 4 * pixels) + differing(got_var, want_var, pixels);
     } else {

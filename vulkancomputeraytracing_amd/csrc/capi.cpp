@@ -3,10 +3,12 @@
 // Replaces the compute half of the reference's Renderer.cpp: the rgba32f storage image
 // (Renderer.cpp:433-468) becomes a device float4 buffer, the compute pipeline
 // (:532-543) a HIP module, and the per-frame vkCmdDispatch(W/16,H/16,1) + vkQueueSubmit
-// (:204-225, :673-686) one persistent-kernel launch on a HIP stream. All state is one file-level
-// object, as in the reference (Renderer.cpp:13-33): one renderer per process. Its device buffers,
-// pinned buffers and events are owners (device_resources.hpp) that free themselves, so teardown
-// is an assignment of a fresh state (vcrt_end) and there is no list of frees to maintain.
+// (:204-225, :673-686) one persistent-kernel launch on a HIP stream. All state is one object
+// (renderer_state.hpp), as in the reference (Renderer.cpp:13-33): one renderer per process. Its
+// device buffers, pinned buffers and events are owners (device_resources.hpp) that free
+// themselves, so teardown is an assignment of a fresh state (vcrt_end) and there is no list of
+// frees to maintain. The passes over caller-supplied planes (vcrt_denoise, vcrt_reproject, the
+// variance chain, vcrt_sample_counts) are in image_passes.cpp.
 #include <dlfcn.h>
 #include <unistd.h>
 
@@ -29,22 +31,30 @@
 #include "camera_lists_abi.h"
 #include "cluster.hpp"
 #include "comm_wait.hpp"
-#include "denoise_abi.h"
-#include "reproject_abi.h"
 #include "device_resources.hpp"
 #include "hip_status.hpp"
+#include "renderer_state.hpp"
 #include "scene.hpp"
 #include "scene_update_abi.h"
-#include "variance_abi.h"
 #include "vcrt.h"
 #include "vcrt_kernel_abi.h"
 #include "vcrt_math.h"
+
+// The one state (renderer_state.hpp, where the comment on why it is never deleted stands).
+vcrt::RendererState& vcrt::g = *new vcrt::RendererState;
 
 namespace {
 
 using vcrt::DeviceBuffer;
 using vcrt::Event;
+using vcrt::g;
+using vcrt::launch;
+using vcrt::misaligned;
+using vcrt::ms_since;
 using vcrt::PinnedBuffer;
+using vcrt::plane_of;
+using vcrt::RendererState;
+using vcrt::timed_launch;
 using vcrt::to_vk;
 
 // segments (u64 at 8), work_done[2] (u64 at 16), then the work-queue counters from 256
@@ -54,263 +64,6 @@ constexpr uint32_t kStageMaxBytes = 8192;
 constexpr int32_t kDefaultChunk = 64;        // samples per work item (upper end)
 constexpr uint32_t kRegionCount = 88;       // tracer.hip kRegions: region counters per wave
 constexpr uint32_t kRegionDebugBase = 40;   // their sums in vcrt_stats.debug[40..127]
-
-struct RendererState {
-    bool begun = false;
-    vcrt_render_desc desc{};
-    int device = 0;
-    int num_cus = 0;
-    size_t max_lds = 0;
-    hipStream_t stream = nullptr;
-    Event ev_start, ev_stop, ev_resolve;
-    VkPipelineShaderStageCreateInfo stage{};
-    hipFunction_t k_trace_lds = nullptr, k_trace_smem = nullptr, k_assemble = nullptr,
-                  k_fill = nullptr, k_trace_lds_stats = nullptr, k_trace_smem_stats = nullptr,
-                  k_resolve = nullptr, k_encode = nullptr, k_trace_cull = nullptr,
-                  k_trace_cull_stats = nullptr, k_trace_cull_lane_lds = nullptr,
-                  k_trace_cull_lane_lds_stats = nullptr, k_trace_cull_lane = nullptr,
-                  k_trace_cull_lane_stats = nullptr, k_trace_cull_lane_lds_wide = nullptr,
-                  k_trace_cull_lane_lds_wide_stats = nullptr, k_trace_cull_flat = nullptr,
-                  k_trace_cull_flat_stats = nullptr, k_trace_cull_flat_global = nullptr,
-                  k_trace_cull_flat_global_stats = nullptr, k_trace_cull_flat_boxes = nullptr,
-                  k_trace_cull_flat_boxes_stats = nullptr, k_setup_jitter = nullptr;
-    // the flat scans' cost-order builds (null: the code object predates them; no cost order)
-    hipFunction_t k_trace_cull_flat_cost = nullptr, k_trace_cull_flat_global_cost = nullptr,
-                  k_trace_cull_flat_boxes_cost = nullptr;
-    // ray queries (vcrt_trace_rays; null: the code object predates them). The host call stages
-    // through device buffers kept and grown between calls; the counters (the work index at 0,
-    // three u64 tallies from 8) are the query's own, so a frame's are left alone.
-    hipFunction_t k_trace_rays = nullptr;
-    // the thin-lens frame kernels (desc.lens_radius > 0; null: the code object predates them):
-    // the SMEM scan, then the three flat scans and their cost-order builds
-    hipFunction_t k_smem_lens = nullptr, k_flat_lens = nullptr, k_flat_lens_cost = nullptr,
-                  k_flat_global_lens = nullptr, k_flat_global_lens_cost = nullptr,
-                  k_flat_boxes_lens = nullptr, k_flat_boxes_lens_cost = nullptr;
-    DeviceBuffer<float> d_rq_rays;  // [n][3] the origins, then [n][3] the directions
-    DeviceBuffer<float4> d_rq_radiance;
-    DeviceBuffer<vcrt_ray_hit> d_rq_hits;
-    DeviceBuffer<unsigned long long> d_rq_counters;
-    // occlusion queries (vcrt_occlude_rays; null: the code object predates them): the host call
-    // stages its rays in d_rq_rays and the reaches and answers here; tallies in d_rq_counters
-    hipFunction_t k_occlude_rays = nullptr;
-    DeviceBuffer<float> d_oq_tmax;
-    DeviceBuffer<uint8_t> d_oq_occluded;
-    // feature buffers (vcrt_draw_features; null: the code object predates them): the jitter
-    // terms and lens origins of the call's own sample indices (the frame's tables are left
-    // alone), the host call's staging planes and the tallies' slots; kept and grown only
-    hipFunction_t k_frame_features = nullptr;
-    bool feature_lists = true;  // VCRT_FEATURE_LISTS=0: no ray takes the camera-ray lists
-    DeviceBuffer<float2> d_ft_jitter_in;
-    DeviceBuffer<float4> d_ft_jitter, d_ft_lens;
-    std::vector<float2> h_ft_jitter;
-    std::vector<float4> h_ft_lens;
-    DeviceBuffer<float4> d_ft_albedo, d_ft_normal_depth;
-    DeviceBuffer<int32_t> d_ft_sphere;
-    DeviceBuffer<unsigned long long> d_ft_counters;
-    // the ambient visibility buffer (vcrt_draw_occlusion; null: the code object predates it): the
-    // u_j table of the call and the host call's staging plane, kept and grown only; the jitter and
-    // lens tables and the tallies' slots are the feature buffers'
-    hipFunction_t k_frame_occlusion = nullptr;
-    DeviceBuffer<float4> d_ao_dirs, d_ao_plane;
-    std::vector<float4> h_ao_dirs;
-    // the denoiser (vcrt_denoise; null: the code object predates it): the two scratch planes the
-    // passes between the first and the last go through, the host call's four staging planes and
-    // the events around the passes; kept and grown only
-    hipFunction_t k_denoise_pass = nullptr, k_denoise_pass_lds = nullptr;
-    DeviceBuffer<float4> d_dn_scratch[2];
-    DeviceBuffer<float4> d_dn_stage[4];  // colour, albedo, guides, out
-    Event ev_dn[9];
-    // the reprojection map (vcrt_draw_motion; null: the code object predates it): the host call's
-    // staging planes and its packed table of the previous centres and radii, kept and grown only;
-    // the tallies' slots are the feature buffers'
-    hipFunction_t k_frame_motion = nullptr;
-    DeviceBuffer<float4> d_mo_motion, d_mo_surface, d_mo_prev;
-    std::vector<float4> h_mo_prev;
-    // temporal accumulation (vcrt_reproject; null: the code object predates it): the host call's
-    // staging planes and the tally slots; kept and grown only
-    hipFunction_t k_reproject_pass = nullptr;
-    DeviceBuffer<float4> d_rp_stage[5];  // colour, motion, history colour, history surface, out
-    DeviceBuffer<float> d_rp_length[2];  // history length, out length
-    DeviceBuffer<unsigned long long> d_rp_counters;
-    // variance-guided denoising (vcrt_reproject_moments, vcrt_variance, vcrt_denoise_variance;
-    // null: the code object predates them): the host calls' staging planes beyond those of
-    // vcrt_reproject and vcrt_denoise, which they share, and the variance pass's tally slots;
-    // kept and grown only
-    hipFunction_t k_reproject_moments_pass = nullptr, k_variance_pass = nullptr,
-                  k_variance_pass_lds = nullptr, k_denoise_var_pass = nullptr,
-                  k_denoise_var_pass_lds = nullptr;
-    DeviceBuffer<float4> d_vr_stage[3];  // albedo, history moments, out moments
-    DeviceBuffer<float> d_vr_plane[2];   // the variance in, the variance out
-    DeviceBuffer<unsigned long long> d_vr_counters;
-    // adaptive sampling (vcrt_draw_samples, vcrt_sample_counts; null: the code object predates
-    // them): the scan's block sums, offsets and item table, the tracer's scratch (16 B per
-    // item), the counters (totals, work index, tally slots), the host calls' staging planes and
-    // the events around the three kernels; kept and grown only. The jitter and lens tables are
-    // the feature buffers'.
-    hipFunction_t k_sample_scan = nullptr, k_trace_samples = nullptr, k_sample_resolve = nullptr,
-                  k_sample_counts_pass = nullptr;
-    DeviceBuffer<uint4> d_sm_block_sums;
-    DeviceBuffer<uint32_t> d_sm_offsets;
-    DeviceBuffer<uint2> d_sm_items;
-    DeviceBuffer<float4> d_sm_scratch;
-    DeviceBuffer<unsigned long long> d_sm_counters;
-    DeviceBuffer<uint16_t> d_sm_counts;
-    DeviceBuffer<float4> d_sm_stage[2];  // sums, mean
-    DeviceBuffer<float> d_sm_variance;
-    Event ev_sm[5];
-    // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
-    int cull_lane_tables = 0;
-    bool accum_ring = true;      // VCRT_ACCUM_RING=0: chunk sums straight to global memory
-    bool stage_tables = true;    // VCRT_STAGE_TABLES=0: the SMEM scan reads its tables globally
-    uint32_t ring_max = vcrt::kRingMaxEntries;
-    int max_blocks_per_cu = 0;  // VCRT_MAX_BLOCKS_PER_CU: caps the occupancy rule (0: none)
-    // the cost-ordered schedule ("cost order" in vcrt_draw_next_frame): -1 auto, 0 off, 1 on
-    // (VCRT_WORK_ORDER=cost / static); the first frame of a configuration measures each pixel's
-    // segments, later frames hand out the blocks most expensive first
-    int cost_order = -1;
-    bool cost_partition = false;  // the partition is the cost partition (default_chunk)
-    DeviceBuffer<uint32_t> d_pixel_cost;   // [total_pixels] segments (TraceParams.pixel_cost)
-    DeviceBuffer<uint32_t> d_block_order;  // [blocks] TraceParams.block_order
-    uint64_t order_key = 0;  // the configuration the order was measured for (0: none)
-    uint32_t nch_magic[2] = {0u, 0u};  // TraceParams.nch_magic of the partition
-    // deferred fetches (TraceParams.fetch_min / fetch_wait; VCRT_FETCH_MIN, VCRT_FETCH_WAIT;
-    // fetch_min 0: the rule in trace_frame)
-    uint32_t fetch_min = 0u, fetch_wait = 0u;
-    int flat_block = 0;  // VCRT_FLAT_BLOCK: threads per group of the LDS flat scan (0: 256)
-    uint32_t lds_per_cu = 0;     // LDS bytes per CU (160 KB on gfx950)
-    // diagnostics (environment: VCRT_DEBUG_STATS=1, VCRT_WORK_ORDER=forward)
-    int debug_stats = 0;  // 1: the stats kernels; 2: the product kernels with a debug buffer
-                          //    (builds with VCRT_WAVE_END_TIMES record wave start/end times)
-    uint32_t work_flags = 0;
-    DeviceBuffer<unsigned long long> d_debug;  // vcrt_stats.debug's image
-    DeviceBuffer<uint32_t> d_region;  // stats kernels: [waves][kRegionCount] region entry counts
-    // scene
-    int32_t nspheres = 0;
-    bool scene_bounded = false;  // every |center|, radius <= 2^30: discriminants stay finite
-    bool radii_safe = false;     // every |radius| in [2^-40, 2^30] (kFlagRadiiSafe)
-    int32_t accum_log2 = vcrt::kAccumMaxScaleLog2;  // the scale s pixels start at (flags)
-    DeviceBuffer<float4> d_geom;  // pair-SoA groups of four (+1 padding group)
-    DeviceBuffer<float4> d_center_radius, d_shade;
-    DeviceBuffer<float4> d_material;  // (material id, 1 / param, Schlick r0^2, 0) per sphere
-    // culled-scan tables (cluster.hpp); ncgroups == 0 when culling does not apply
-    int32_t ncgroups = 0, ncbig = 0;
-    float cmargin[4] = {0, 0, 0, 0};  // box margin constants (CullTables::margin)
-    bool cslab_on = false;            // the shared y slab (CullTables::slab, slab_lohi)
-    float cslab[2] = {0, 0};
-    DeviceBuffer<float4> d_cgroup, d_cbound, d_cbound_nf, d_cnode;
-    DeviceBuffer<float4> d_cnode_nf;  // node-pair boxes, near/far layout, padded to whole chunks
-    DeviceBuffer<float4> d_ctop;
-    // the footprint tables of the LDS-table flat scan (CullTables::fp_*), packed to their width
-    DeviceBuffer<uint32_t> d_fp_tab;
-    float cfp_x[2] = {1, 0}, cfp_z[2] = {1, 0}, cfp_y[2] = {0, 0}, cfp_k2 = 0;
-    uint32_t cfp_always = 0xffffffffu;
-    // the group-level footprint tables (CullTables::gf_*) and whether a frame may use them
-    DeviceBuffer<uint4> d_gf_tab;
-    float cgf_x[2] = {1, 0}, cgf_z[2] = {1, 0}, cgf_k2 = 0;
-    uint32_t cgf_n = 0, cgf_always[4] = {0, 0, 0, 0};
-    bool cgf_ok = false;
-    // camera-ray tile lists (primary.cpp), flat scan only; vcrt_set_camera reuses the buffers
-    // and grows them only
-    DeviceBuffer<uint32_t> d_prim_info;
-    DeviceBuffer<uint16_t> d_prim_ids;
-    DeviceBuffer<float> d_cam_rec;  // camera-relative records: big groups, sphere lists
-    bool primary_lists = true;      // VCRT_PRIMARY_LISTS=0 turns them off
-    size_t prim_nids = 0, prim_npairs = 0;  // the installed lists' sizes: ids, pair records
-    // the scene as vcrt_set_scene got it and its culling tables: vcrt_set_camera's host builders
-    // (VCRT_CAMERA_LISTS=host, or a code object without the list kernels) and sizes
-    std::vector<vcrt_sphere> h_spheres;
-    vcrt::CullTables h_ct;
-    // the camera-list kernels (camera_lists.hip; null: the code object predates them) and their
-    // scratch: grown boxes and sphere entries, counts + offsets + totals; kept and grown only
-    hipFunction_t k_cl_prepare = nullptr, k_cl_count = nullptr, k_cl_scan = nullptr,
-                  k_cl_fill = nullptr;
-    DeviceBuffer<double> d_cl_boxes, d_cl_spheres;
-    DeviceBuffer<uint32_t> d_cl_counts;
-    PinnedBuffer<uint32_t> h_cl_totals;  // [2]
-    Event ev_cl[2];
-    vcrt_camera_stats cam_stats{};
-    // vcrt_update_spheres: the refit kernels (scene_update.hip; null: the code object predates
-    // them), the staged spheres, the summary and its pinned copy; kept and grown only
-    hipFunction_t k_su_rows = nullptr, k_su_groups = nullptr, k_su_levels = nullptr,
-                  k_su_footprint = nullptr;
-    DeviceBuffer<float> d_su_spheres;
-    DeviceBuffer<vcrt::SceneSummary> d_su_summary;
-    PinnedBuffer<vcrt::SceneSummary> h_su_summary;
-    Event ev_su[2];
-    vcrt_scene_update_stats su_stats{};
-    // h_ct holds the grouping but not yet the tables of h_spheres: the device refit leaves them
-    // on the device, and current_tables() restates them when the host needs them
-    bool h_ct_stale = false;
-    // work decomposition
-    int32_t quantum = 1;  // the accumulation quantum G (a power of two)
-    int32_t chunk = 1, nchunks = 1;
-    int32_t tail_start = 0, tail_chunk = 1, tail_nchunks = 0;  // TraceParams' tail
-    uint32_t total_pixels = 0, total_items = 0;
-    bool direct = false;  // one item per pixel, not progressive: lanes write pixels (kFlagDirect)
-    DeviceBuffer<double> d_accum;  // [total_pixels][4] exact sums of the quantized chunk sums
-    // d_accum holds zeros: a memset, or the last resolve wrote them back (vcrt_resolve
-    // zero_accum), so a non-progressive frame needs no memset of its own
-    bool accum_clean = false;
-    // Outlier quanta (vcrt_math.h "Accumulation"): [total_pixels] the float bits of each pixel's
-    // largest |quantum sum| that passed 2^12 (0: none); once one has, every frame of the
-    // configuration quantizes each pixel at its own scale (pixel_scale, kFlagPixelScale)
-    DeviceBuffer<uint32_t> d_pixel_emax;
-    bool pixel_scale = false;
-    int32_t min_scale = vcrt::kAccumMaxScaleLog2;  // the smallest pixel scale so far
-    uint64_t accumulated = 0;               // samples per pixel accumulated (progressive)
-    // the host's jitter (jx, jy) of a frame's sample indices: two pinned buffers used in turn,
-    // each reused only once the copy recorded by its event is done (progressive frames set up
-    // their jitter without waiting for the stream)
-    PinnedBuffer<float2> h_jitter[2];
-    // the lens origins of the same sample indices (desc.lens_radius > 0, else null), built on
-    // the host (vcrt_math.h lens_offset) in the same two turns and under the same events
-    PinnedBuffer<float4> h_lens[2];
-    DeviceBuffer<float4> d_lens;  // TraceParams.lens
-    Event ev_jitter[2];
-    int jitter_slot = 0;
-    DeviceBuffer<float> d_srgb_thresholds;
-    DeviceBuffer<uchar4> d_srgb;  // vcrt_read_framebuffer_srgb8's staging, kept and grown only
-    // per-frame inputs / outputs
-    DeviceBuffer<float2> d_jitter_in;  // the host's jitter (jx, jy) of the frame's sample indices
-    DeviceBuffer<float4> d_jitter;     // TraceParams.jitter (vcrt_setup_jitter)
-    DeviceBuffer<float4> d_corner;     // TraceParams.corner (vcrt_setup_jitter, at vcrt_begin)
-    DeviceBuffer<float4> d_fb_own;
-    float4* d_fb = nullptr;  // current render target (own, the gather's or caller-provided)
-    size_t fb_bytes = 0;
-    DeviceBuffer<unsigned long long> d_counters;  // kCounterBytes
-    // the counters' first four u64 (outlier max, segments, work tallies), read back each frame:
-    // host-pinned, written by vcrt_resolve (which then zeroes d_counters: counters_clean) or
-    // copied when no resolve runs
-    PinnedBuffer<unsigned long long> h_counters;
-    bool counters_clean = false;
-    uint32_t tiles_x = 0, local_tiles = 0;
-    uint32_t local_elems = 0;   // float4 elements of the rank-local framebuffer
-    uint64_t local_pixels = 0;  // frame pixels this rank renders
-    uint32_t pad_tiles = 0;     // tiles of the largest rank: the packed framebuffers' size
-    // multi-GPU, one process per GPU (vcrt_comm_init): the ranks' packed framebuffers go to
-    // rank 0 in one grouped RCCL send/recv inside vcrt_draw_next_frame; rank 0 assembles them
-    ncclComm_t comm = nullptr;  // non-blocking (comm_wait.hpp): every wait has a deadline
-    bool comm_lost = false;     // the communicator failed or timed out and was aborted: every
-                                // later draw returns VK_ERROR_DEVICE_LOST (until vcrt_begin)
-    DeviceBuffer<float4> d_gather;  // rank 0: [world][pad_tiles][64], its own tiles in slot 0
-    DeviceBuffer<float4> d_frame;   // rank 0: the assembled frame [height][width]
-    Event ev_gather_start, ev_gather;
-    vcrt::Camera cam{};
-    vcrt_stats stats{};
-};
-
-// The state lives on the heap and is never deleted: a file-static RendererState would run its
-// members' destructors at process exit, and a process that ends without vcrt_end would then call
-// hipFree and hipEventDestroy from a static destructor, possibly after the HIP runtime has torn
-// itself down. As it is, such a process makes no HIP call at exit; the resources are released in
-// vcrt_end alone, by move-assigning a fresh state.
-RendererState& g = *new RendererState;
-
-#define VCRT_TRY(expr)                          \
-    do {                                        \
-        hipError_t e_ = (expr);                 \
-        if (e_ != hipSuccess) return to_vk(e_); \
-    } while (0)
 
 // Samples per work item when the caller leaves it to us: 64, halved (down to 16) while the
 // largest rank's share of the frame would be fewer than kChunkItems = 2^24 - 2^21 items (~45 per
@@ -873,36 +626,6 @@ VkResult nccl_vk(ncclResult_t e) {
                                                              : VK_ERROR_UNKNOWN;
 }
 
-template <typename Params>
-VkResult launch(hipFunction_t f, uint32_t grid, uint32_t block, uint32_t lds, Params& params) {
-    void* args[] = {&params};
-    VCRT_TRY(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, lds, g.stream, args, nullptr));
-    return VK_SUCCESS;
-}
-
-// One timed launch of a query or guide kernel with tallies of its own, waited for: `counters`
-// (words u64, allocated on first use) is zeroed and handed to `bind`, which points the params at
-// it; the launch runs between ev_start and ev_stop. With a host destination the counters come
-// back into it and *ms is the kernel time; without one neither is read.
-template <typename Params, typename Bind>
-VkResult timed_launch(hipFunction_t f, uint32_t grid, uint32_t block, Params& params,
-                      DeviceBuffer<unsigned long long>& counters, size_t words, Bind&& bind,
-                      unsigned long long* host, float* ms) {
-    const size_t bytes = words * sizeof(unsigned long long);
-    VCRT_TRY(counters.reserve(words));
-    bind(counters.data());
-    VCRT_TRY(hipMemsetAsync(counters.data(), 0, bytes, g.stream));
-    VCRT_TRY(hipEventRecord(g.ev_start.get(), g.stream));
-    const VkResult r = launch(f, grid, block, 0, params);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipEventRecord(g.ev_stop.get(), g.stream));
-    if (host)
-        VCRT_TRY(hipMemcpyAsync(host, counters.data(), bytes, hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (host) VCRT_TRY(hipEventElapsedTime(ms, g.ev_start.get(), g.ev_stop.get()));
-    return VK_SUCCESS;
-}
-
 // FeatureParams.tallies, OcclusionBufferParams.tallies: slots of 64 B, summed by the callers
 constexpr size_t kFeatureCounterWords = 8 * vcrt::kFeatureTallySlots;  // u64
 
@@ -915,7 +638,7 @@ VkResult frame_ray_launch(hipFunction_t f, Params& p, unsigned long long* slots,
         VCRT_TRY(hipStreamSynchronize(g.stream));
         return VK_SUCCESS;
     }
-    return timed_launch(f, (g.local_tiles + 3u) / 4u, 256, p, g.d_ft_counters,
+    return timed_launch(f, (g.local_tiles + 3u) / 4u, 256, 0, p, g.d_ft_counters,
                         kFeatureCounterWords, [&p](unsigned long long* c) { p.tallies = c; },
                         slots, ms);
 }
@@ -2278,7 +2001,7 @@ VkResult ray_query_device(const float* origins, const float* dirs, uint32_t coun
     unsigned long long counters[kRayCounterWords] = {};
     float ms = 0.f;
     const VkResult r = timed_launch(
-        g.k_trace_rays, query_grid(g.k_trace_rays, count), kQueryBlock, p, g.d_rq_counters,
+        g.k_trace_rays, query_grid(g.k_trace_rays, count), kQueryBlock, 0, p, g.d_rq_counters,
         kRayCounterWords,
         [&p](unsigned long long* c) {
             p.work = reinterpret_cast<uint32_t*>(c);
@@ -2303,7 +2026,7 @@ vcrt_result vcrt_trace_rays_device(const float* origins, const float* dirs, uint
     const vcrt_result a = ray_query_args(origins, dirs, count, max_depth, radiance, hits);
     if (a != VCRT_SUCCESS) return a;
     // the kernel's 16-byte stores
-    if ((reinterpret_cast<uintptr_t>(radiance) | reinterpret_cast<uintptr_t>(hits)) & 15u)
+    if (misaligned({radiance, hits}, 15u))
         return VCRT_ERROR_INITIALIZATION_FAILED;
     return ray_query_device(origins, dirs, count, max_depth, radiance, hits, stats);
 }
@@ -2372,8 +2095,8 @@ VkResult occlusion_device(const float* origins, const float* dirs, const float* 
     unsigned long long counters[kRayCounterWords] = {};
     float ms = 0.f;
     const VkResult r = timed_launch(
-        g.k_occlude_rays, query_grid(g.k_occlude_rays, count), kQueryBlock, p, g.d_rq_counters,
-        kRayCounterWords, [&p](unsigned long long* c) { p.tallies = c + 1; },
+        g.k_occlude_rays, query_grid(g.k_occlude_rays, count), kQueryBlock, 0, p,
+        g.d_rq_counters, kRayCounterWords, [&p](unsigned long long* c) { p.tallies = c + 1; },
         stats ? counters : nullptr, &ms);
     if (r != VK_SUCCESS) return r;
     if (stats) {
@@ -2529,10 +2252,6 @@ VkResult draw_features_device(uint32_t first, uint32_t n, float* albedo, float* 
     return VK_SUCCESS;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 vcrt_result vcrt_draw_features_device(uint32_t first, uint32_t n, float* albedo,
@@ -2542,8 +2261,7 @@ vcrt_result vcrt_draw_features_device(uint32_t first, uint32_t n, float* albedo,
     const vcrt_result a = feature_args(first, n, albedo, normal_depth, sphere);
     if (a != VCRT_SUCCESS) return a;
     // the kernel's 16-byte stores (and the ids' 4-byte ones)
-    if (((reinterpret_cast<uintptr_t>(albedo) | reinterpret_cast<uintptr_t>(normal_depth)) & 15u) ||
-        (reinterpret_cast<uintptr_t>(sphere) & 3u))
+    if (misaligned({albedo, normal_depth}, 15u) || misaligned({sphere}, 3u))
         return VCRT_ERROR_INITIALIZATION_FAILED;
     if (!g.k_frame_features) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     const VkResult r = draw_features_device(first, n, albedo, normal_depth, sphere, stats);
@@ -2670,7 +2388,7 @@ vcrt_result vcrt_draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, f
     const vcrt_result a = ambient_args(first, n, m, reach, visibility);
     if (a != VCRT_SUCCESS) return a;
     // the kernel's 16-byte stores
-    if (reinterpret_cast<uintptr_t>(visibility) & 15u) return VCRT_ERROR_INITIALIZATION_FAILED;
+    if (misaligned({visibility}, 15u)) return VCRT_ERROR_INITIALIZATION_FAILED;
     if (!g.k_frame_occlusion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     const VkResult r = draw_occlusion_device(first, n, m, reach, visibility, stats);
     if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
@@ -2782,8 +2500,7 @@ vcrt_result vcrt_draw_motion_device(const vcrt_camera* prev_camera,
     const vcrt_result a = motion_args(prev_spheres, count, motion, surface);
     if (a != VCRT_SUCCESS) return a;
     // the kernel's 16-byte stores and its 4-byte loads of the records
-    if (((reinterpret_cast<uintptr_t>(motion) | reinterpret_cast<uintptr_t>(surface)) & 15u) ||
-        (reinterpret_cast<uintptr_t>(prev_spheres) & 3u))
+    if (misaligned({motion, surface}, 15u) || misaligned({prev_spheres}, 3u))
         return VCRT_ERROR_INITIALIZATION_FAILED;
     if (!g.k_frame_motion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
     static_assert(sizeof(vcrt_sphere) == 40 && offsetof(vcrt_sphere, radius) == 12,
@@ -2858,647 +2575,6 @@ vcrt_result vcrt_motion_project(const vcrt_render_desc* desc, const vcrt_camera*
         out[3 * i + 1] = r.y;
         out[3 * i + 2] = r.z;
     }
-    return VCRT_SUCCESS;
-}
-
-// ---- the denoiser -----------------------------------------------------------------------------
-
-namespace {
-
-// VCRT_DENOISE_LDS: how many leading passes stage their footprint in LDS (at most the passes of
-// step 1 and 2). Unset: both -- see tools/denoise_bench.py and profiles/denoise.json for the A/B.
-int32_t denoise_lds_passes() {
-    static_assert(vcrt::kDenoiseLdsMaxStep == 2, "the LDS kernel takes passes 0 and 1");
-    int32_t n = 2;
-    if (const char* e = std::getenv("VCRT_DENOISE_LDS")) n = std::atoi(e);
-    return std::min(std::max(n, 0), 2);
-}
-
-// The passes on device planes (checked by the callers); returns when the last is done.
-VkResult denoise_device(const float* colour, const float* albedo, const float* normal_depth,
-                        int32_t width, int32_t height, const vcrt_denoise_params& pr,
-                        const float k4[4], float* out, vcrt_denoise_stats* stats) {
-    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    const int32_t levels = pr.levels;
-    // pass l reads the plane pass l - 1 wrote: the colour, the scratch planes in turn, the output
-    for (int32_t b = 0; b < std::min(levels - 1, 2); b++)
-        VCRT_TRY(g.d_dn_scratch[b].reserve(pixels));
-    for (int32_t l = 0; l <= levels; l++) VCRT_TRY(g.ev_dn[l].create());
-    const bool demod = pr.demodulate != 0 && albedo;
-    uint32_t terms = 0;
-    if (normal_depth && k4[0] != 0.0f) terms |= vcrt::kDenoiseNormal;
-    if (normal_depth && k4[1] != 0.0f) terms |= vcrt::kDenoiseDepth;
-    if (albedo && k4[2] != 0.0f) terms |= vcrt::kDenoiseAlbedo;
-    const int32_t lds_passes = std::min(denoise_lds_passes(), levels);
-    float kl = k4[3];
-    const float* in = colour;
-    VCRT_TRY(hipEventRecord(g.ev_dn[0].get(), g.stream));
-    for (int32_t l = 0; l < levels; l++) {
-        vcrt::DenoiseParams p{};
-        p.in = in;
-        p.colour = colour;
-        p.albedo = albedo;
-        p.normal_depth = normal_depth;
-        p.out = l == levels - 1 ? out : reinterpret_cast<float*>(g.d_dn_scratch[l & 1].data());
-        p.width = static_cast<uint32_t>(width);
-        p.height = static_cast<uint32_t>(height);
-        p.step = 1u << l;
-        p.flags = terms | (kl != 0.0f ? vcrt::kDenoiseColour : 0u) |
-                  (demod && l == 0 ? vcrt::kDenoiseDemodIn : 0u) |
-                  (demod && l == levels - 1 ? vcrt::kDenoiseModOut : 0u) |
-                  (l == levels - 1 ? vcrt::kDenoiseLast : 0u);
-        p.k_normal = k4[0];
-        p.k_depth = k4[1];
-        p.k_albedo = k4[2];
-        p.kl = kl;
-        VkResult r;
-        if (l < lds_passes) {
-            const uint32_t halo = 2u * p.step;
-            const uint32_t entries =
-                (vcrt::kDenoiseTileW + 2u * halo) * (vcrt::kDenoiseTileH + 2u * halo);
-            const bool guides = (terms & (vcrt::kDenoiseNormal | vcrt::kDenoiseDepth)) != 0;
-            const uint32_t planes =
-                1u + ((terms & vcrt::kDenoiseAlbedo) ? 1u : 0u) + (guides ? 1u : 0u);
-            p.tiles_x = (p.width + vcrt::kDenoiseTileW - 1u) / vcrt::kDenoiseTileW;
-            const uint32_t tiles_y = (p.height + vcrt::kDenoiseTileH - 1u) / vcrt::kDenoiseTileH;
-            r = launch(g.k_denoise_pass_lds, p.tiles_x * tiles_y, vcrt::kDenoiseThreads,
-                       entries * planes * static_cast<uint32_t>(sizeof(float4)), p);
-        } else {
-            p.tiles_x = (p.width + vcrt::kDenoiseRowW - 1u) / vcrt::kDenoiseRowW;
-            const uint32_t tiles_y = (p.height + vcrt::kDenoiseRowH - 1u) / vcrt::kDenoiseRowH;
-            r = launch(g.k_denoise_pass, p.tiles_x * tiles_y, vcrt::kDenoiseThreads, 0, p);
-        }
-        if (r != VK_SUCCESS) return r;
-        VCRT_TRY(hipEventRecord(g.ev_dn[l + 1].get(), g.stream));
-        in = p.out;
-        kl = kl * 4.0f;
-    }
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) {
-        *stats = vcrt_denoise_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_denoise_pass");
-        stats->passes = levels;
-        stats->lds_passes = lds_passes;
-        float ms = 0.f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[0].get(), g.ev_dn[levels].get()));
-        stats->kernel_ms = ms;
-        for (int32_t l = 0; l < levels; l++) {
-            VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[l].get(), g.ev_dn[l + 1].get()));
-            stats->pass_ms[l] = ms;
-        }
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_denoise_device(const float* colour, const float* albedo,
-                                const float* normal_depth, int32_t width, int32_t height,
-                                const vcrt_denoise_params* params, float* out,
-                                vcrt_denoise_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_denoise_params pr;
-    float k4[4];
-    const vcrt_result a = vcrt::denoise_args(colour, albedo, normal_depth, width, height, params,
-                                             out, &pr, k4);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernels' 16-byte loads and stores
-    if ((reinterpret_cast<uintptr_t>(colour) | reinterpret_cast<uintptr_t>(albedo) |
-         reinterpret_cast<uintptr_t>(normal_depth) | reinterpret_cast<uintptr_t>(out)) & 15u)
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_denoise_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = denoise_device(colour, albedo, normal_depth, width, height, pr, k4, out,
-                                      stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_denoise(const float* colour, const float* albedo, const float* normal_depth,
-                         int32_t width, int32_t height, const vcrt_denoise_params* params,
-                         float* out, vcrt_denoise_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_denoise_params pr;
-    float k4[4];
-    const vcrt_result a = vcrt::denoise_args(colour, albedo, normal_depth, width, height, params,
-                                             out, &pr, k4);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_denoise_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    const float* host[3] = {colour, albedo, normal_depth};
-    const float* dev[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; k++)  // the three inputs that are there, and the output
-        if (k == 3 || host[k])
-            VCRT_TRY(g.d_dn_stage[k].reserve(pixels));
-    for (int k = 0; k < 3; k++) {
-        if (!host[k]) continue;
-        VCRT_TRY(hipMemcpyAsync(g.d_dn_stage[k].data(), host[k], sizeof(float4) * pixels,
-                                hipMemcpyHostToDevice, g.stream));
-        dev[k] = reinterpret_cast<const float*>(g.d_dn_stage[k].data());
-    }
-    const VkResult r = denoise_device(dev[0], dev[1], dev[2], width, height, pr, k4,
-                                      reinterpret_cast<float*>(g.d_dn_stage[3].data()), stats);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(out, g.d_dn_stage[3].data(), sizeof(float4) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
-// ---- temporal accumulation ---------------------------------------------------------------------
-
-namespace {
-
-constexpr size_t kReprojectCounterWords = 8 * vcrt::kReprojectTallySlots;  // u64
-
-// The launch on device planes (checked by the callers); returns when it is done.
-VkResult reproject_device(const float* colour, const float* motion, const float* history_colour,
-                          const float* history_surface, const float* history_length,
-                          int32_t width, int32_t height, const vcrt_reproject_params& pr,
-                          float* out, float* out_length, vcrt_reproject_stats* stats) {
-    vcrt::ReprojectParams p{};
-    p.colour = colour;
-    p.motion = motion;
-    p.history_colour = history_colour;
-    p.history_surface = history_surface;
-    p.history_length = history_length;
-    p.out = out;
-    p.out_length = out_length;
-    p.width = static_cast<uint32_t>(width);
-    p.height = static_cast<uint32_t>(height);
-    p.alpha = pr.alpha;
-    p.max_history = pr.max_history;
-    p.depth_tolerance = pr.depth_tolerance;
-    p.tiles_x = (p.width + vcrt::kReprojectRowW - 1u) / vcrt::kReprojectRowW;
-    const uint32_t tiles_y = (p.height + vcrt::kReprojectRowH - 1u) / vcrt::kReprojectRowH;
-    if (!stats) {  // nothing to count or time
-        const VkResult r = launch(g.k_reproject_pass, p.tiles_x * tiles_y,
-                                  vcrt::kReprojectThreads, 0, p);
-        if (r != VK_SUCCESS) return r;
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-        return VK_SUCCESS;
-    }
-    std::vector<unsigned long long> slots(kReprojectCounterWords);
-    float ms = 0.f;
-    const VkResult r = timed_launch(
-        g.k_reproject_pass, p.tiles_x * tiles_y, vcrt::kReprojectThreads, p, g.d_rp_counters,
-        kReprojectCounterWords, [&p](unsigned long long* c) { p.tallies = c; }, slots.data(), &ms);
-    if (r != VK_SUCCESS) return r;
-    *stats = vcrt_reproject_stats{};
-    std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_reproject_pass");
-    stats->kernel_ms = ms;
-    for (size_t s = 0; s < vcrt::kReprojectTallySlots; s++)
-        stats->accepted_pixels += slots[8 * s];
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_reproject_device(const float* colour, const float* motion,
-                                  const float* history_colour, const float* history_surface,
-                                  const float* history_length, int32_t width, int32_t height,
-                                  const vcrt_reproject_params* params, float* out,
-                                  float* out_length, vcrt_reproject_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_reproject_params pr;
-    const vcrt_result a = vcrt::reproject_args(colour, motion, history_colour, history_surface,
-                                               history_length, width, height, params, out,
-                                               out_length, &pr);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernel's 16-byte loads and stores of the float4 planes, 4-byte ones of the lengths
-    if ((reinterpret_cast<uintptr_t>(colour) | reinterpret_cast<uintptr_t>(motion) |
-         reinterpret_cast<uintptr_t>(history_colour) |
-         reinterpret_cast<uintptr_t>(history_surface) | reinterpret_cast<uintptr_t>(out)) & 15u)
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if ((reinterpret_cast<uintptr_t>(history_length) | reinterpret_cast<uintptr_t>(out_length)) &
-        3u)
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_reproject_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = reproject_device(colour, motion, history_colour, history_surface,
-                                        history_length, width, height, pr, out, out_length,
-                                        stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_reproject(const float* colour, const float* motion, const float* history_colour,
-                           const float* history_surface, const float* history_length,
-                           int32_t width, int32_t height, const vcrt_reproject_params* params,
-                           float* out, float* out_length, vcrt_reproject_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_reproject_params pr;
-    const vcrt_result a = vcrt::reproject_args(colour, motion, history_colour, history_surface,
-                                               history_length, width, height, params, out,
-                                               out_length, &pr);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_reproject_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    const float* host[4] = {colour, motion, history_colour, history_surface};
-    for (int k = 0; k < 5; k++) VCRT_TRY(g.d_rp_stage[k].reserve(pixels));
-    for (int k = 0; k < 2; k++) VCRT_TRY(g.d_rp_length[k].reserve(pixels));
-    for (int k = 0; k < 4; k++)
-        VCRT_TRY(hipMemcpyAsync(g.d_rp_stage[k].data(), host[k], sizeof(float4) * pixels,
-                                hipMemcpyHostToDevice, g.stream));
-    VCRT_TRY(hipMemcpyAsync(g.d_rp_length[0].data(), history_length, sizeof(float) * pixels,
-                            hipMemcpyHostToDevice, g.stream));
-    const auto plane = [](const DeviceBuffer<float4>& b) {
-        return reinterpret_cast<float*>(b.data());
-    };
-    const VkResult r = reproject_device(plane(g.d_rp_stage[0]), plane(g.d_rp_stage[1]),
-                                        plane(g.d_rp_stage[2]), plane(g.d_rp_stage[3]),
-                                        g.d_rp_length[0].data(), width, height, pr,
-                                        plane(g.d_rp_stage[4]), g.d_rp_length[1].data(), stats);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(out, g.d_rp_stage[4].data(), sizeof(float4) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipMemcpyAsync(out_length, g.d_rp_length[1].data(), sizeof(float) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
-// ---- variance-guided denoising -----------------------------------------------------------------
-
-namespace {
-
-constexpr size_t kMomentsCounterWords = 8 * vcrt::kMomentsTallySlots;    // u64
-constexpr size_t kVarianceCounterWords = 8 * vcrt::kVarianceTallySlots;  // u64
-
-inline bool misaligned(std::initializer_list<const void*> planes, uintptr_t mask) {
-    uintptr_t bits = 0;
-    for (const void* p : planes) bits |= reinterpret_cast<uintptr_t>(p);
-    return (bits & mask) != 0;
-}
-
-inline float* plane_of(const DeviceBuffer<float4>& b) { return reinterpret_cast<float*>(b.data()); }
-
-// The moments launch on device planes (checked by the callers); returns when it is done.
-VkResult reproject_moments_device(const float* colour, const float* motion,
-                                  const float* history_colour, const float* history_surface,
-                                  const float* history_length, const float* albedo,
-                                  const float* history_moments, int32_t width, int32_t height,
-                                  const vcrt_reproject_moments_params& pr, float* out,
-                                  float* out_length, float* out_moments,
-                                  vcrt_reproject_stats* stats) {
-    vcrt::ReprojectMomentsParams p{};
-    p.colour = colour;
-    p.motion = motion;
-    p.history_colour = history_colour;
-    p.history_surface = history_surface;
-    p.history_length = history_length;
-    p.albedo = albedo;
-    p.history_moments = history_moments;
-    p.out = out;
-    p.out_length = out_length;
-    p.out_moments = out_moments;
-    p.width = static_cast<uint32_t>(width);
-    p.height = static_cast<uint32_t>(height);
-    p.alpha = pr.alpha;
-    p.max_history = pr.max_history;
-    p.depth_tolerance = pr.depth_tolerance;
-    p.alpha_moments = pr.alpha_moments;
-    p.tiles_x = (p.width + vcrt::kMomentsRowW - 1u) / vcrt::kMomentsRowW;
-    const uint32_t tiles_y = (p.height + vcrt::kMomentsRowH - 1u) / vcrt::kMomentsRowH;
-    if (!stats) {  // nothing to count or time
-        const VkResult r = launch(g.k_reproject_moments_pass, p.tiles_x * tiles_y,
-                                  vcrt::kMomentsThreads, 0, p);
-        if (r != VK_SUCCESS) return r;
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-        return VK_SUCCESS;
-    }
-    std::vector<unsigned long long> slots(kMomentsCounterWords);
-    float ms = 0.f;
-    const VkResult r = timed_launch(
-        g.k_reproject_moments_pass, p.tiles_x * tiles_y, vcrt::kMomentsThreads, p,
-        g.d_rp_counters, kMomentsCounterWords, [&p](unsigned long long* c) { p.tallies = c; },
-        slots.data(), &ms);
-    if (r != VK_SUCCESS) return r;
-    *stats = vcrt_reproject_stats{};
-    std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_reproject_moments_pass");
-    stats->kernel_ms = ms;
-    for (size_t s = 0; s < vcrt::kMomentsTallySlots; s++) stats->accepted_pixels += slots[8 * s];
-    return VK_SUCCESS;
-}
-
-// The variance launch on device planes (checked by the callers); returns when it is done.
-VkResult variance_device(const float* moments, const float* surface, int32_t width, int32_t height,
-                         const vcrt_variance_params& pr, float* variance,
-                         vcrt_variance_stats* stats) {
-    vcrt::VarianceParams p{};
-    p.moments = moments;
-    p.surface = surface;
-    p.variance = variance;
-    p.width = static_cast<uint32_t>(width);
-    p.height = static_cast<uint32_t>(height);
-    p.min_history = pr.min_history;
-    p.alpha = pr.alpha;
-    // VCRT_VARIANCE_LDS=0: the taps read directly; unset or 1, the measured choice
-    // (tools/variance_bench.py, profiles/variance.json): from a staged footprint. Same bits.
-    const char* e = std::getenv("VCRT_VARIANCE_LDS");
-    const bool lds = !e || std::atoi(e) != 0;
-    const uint32_t tw = lds ? vcrt::kVarianceTileW : vcrt::kVarianceRowW;
-    const uint32_t th = lds ? vcrt::kVarianceTileH : vcrt::kVarianceRowH;
-    const hipFunction_t f = lds ? g.k_variance_pass_lds : g.k_variance_pass;
-    const uint32_t lds_bytes = lds ? vcrt::kVarianceLdsBytes : 0u;
-    p.tiles_x = (p.width + tw - 1u) / tw;
-    const uint32_t tiles_y = (p.height + th - 1u) / th;
-    if (stats) {
-        VCRT_TRY(g.d_vr_counters.reserve(kVarianceCounterWords));
-        p.tallies = g.d_vr_counters.data();
-        VCRT_TRY(hipMemsetAsync(p.tallies, 0, kVarianceCounterWords * sizeof(unsigned long long),
-                                g.stream));
-        VCRT_TRY(hipEventRecord(g.ev_start.get(), g.stream));
-    }
-    const VkResult r = launch(f, p.tiles_x * tiles_y, vcrt::kVarianceThreads, lds_bytes, p);
-    if (r != VK_SUCCESS) return r;
-    if (!stats) {
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-        return VK_SUCCESS;
-    }
-    std::vector<unsigned long long> slots(kVarianceCounterWords);
-    float ms = 0.f;
-    VCRT_TRY(hipEventRecord(g.ev_stop.get(), g.stream));
-    VCRT_TRY(hipMemcpyAsync(slots.data(), p.tallies,
-                            kVarianceCounterWords * sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    VCRT_TRY(hipEventElapsedTime(&ms, g.ev_start.get(), g.ev_stop.get()));
-    *stats = vcrt_variance_stats{};
-    std::snprintf(stats->kernel, sizeof(stats->kernel),
-                  lds ? "vcrt_variance_pass_lds" : "vcrt_variance_pass");
-    stats->kernel_ms = ms;
-    for (size_t s = 0; s < vcrt::kVarianceTallySlots; s++) stats->spatial_pixels += slots[8 * s];
-    return VK_SUCCESS;
-}
-
-// The steered passes on device planes (checked by the callers); returns when the last is done.
-// Sequenced as denoise_device's: the scratch planes and events are the denoiser's.
-VkResult denoise_variance_device(const float* colour, const float* albedo,
-                                 const float* normal_depth, const float* variance, int32_t width,
-                                 int32_t height, const vcrt_denoise_params& pr, const float k4[4],
-                                 float* out, float* out_variance, vcrt_denoise_stats* stats) {
-    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    const int32_t levels = pr.levels;
-    for (int32_t b = 0; b < std::min(levels - 1, 2); b++)
-        VCRT_TRY(g.d_dn_scratch[b].reserve(pixels));
-    for (int32_t l = 0; l <= levels; l++) VCRT_TRY(g.ev_dn[l].create());
-    const bool demod = pr.demodulate != 0 && albedo;
-    uint32_t terms = 0;
-    if (normal_depth && k4[0] != 0.0f) terms |= vcrt::kDenoiseNormal;
-    if (normal_depth && k4[1] != 0.0f) terms |= vcrt::kDenoiseDepth;
-    if (albedo && k4[2] != 0.0f) terms |= vcrt::kDenoiseAlbedo;
-    if (pr.sigma_colour != 0.0f) terms |= vcrt::kDenoiseColour;
-    const int32_t lds_passes = std::min(denoise_lds_passes(), levels);
-    const float* in = colour;
-    VCRT_TRY(hipEventRecord(g.ev_dn[0].get(), g.stream));
-    for (int32_t l = 0; l < levels; l++) {
-        vcrt::DenoiseVarParams p{};
-        p.in = in;
-        p.colour = colour;
-        p.albedo = albedo;
-        p.normal_depth = normal_depth;
-        p.variance = variance;
-        p.out = l == levels - 1 ? out : reinterpret_cast<float*>(g.d_dn_scratch[l & 1].data());
-        p.out_variance = out_variance;
-        p.width = static_cast<uint32_t>(width);
-        p.height = static_cast<uint32_t>(height);
-        p.step = 1u << l;
-        p.flags = terms | (l == 0 ? vcrt::kDenoiseVarIn : 0u) |
-                  (demod && l == 0 ? vcrt::kDenoiseDemodIn : 0u) |
-                  (demod && l == levels - 1 ? vcrt::kDenoiseModOut : 0u) |
-                  (l == levels - 1 ? vcrt::kDenoiseLast : 0u);
-        p.k_normal = k4[0];
-        p.k_depth = k4[1];
-        p.k_albedo = k4[2];
-        p.sc2 = pr.sigma_colour * pr.sigma_colour;
-        VkResult r;
-        if (l < lds_passes) {
-            const uint32_t halo = 2u * p.step;
-            const uint32_t entries =
-                (vcrt::kDenoiseTileW + 2u * halo) * (vcrt::kDenoiseTileH + 2u * halo);
-            const bool guides = (terms & (vcrt::kDenoiseNormal | vcrt::kDenoiseDepth)) != 0;
-            const uint32_t planes =
-                1u + ((terms & vcrt::kDenoiseAlbedo) ? 1u : 0u) + (guides ? 1u : 0u);
-            p.tiles_x = (p.width + vcrt::kDenoiseTileW - 1u) / vcrt::kDenoiseTileW;
-            const uint32_t tiles_y = (p.height + vcrt::kDenoiseTileH - 1u) / vcrt::kDenoiseTileH;
-            r = launch(g.k_denoise_var_pass_lds, p.tiles_x * tiles_y, vcrt::kDenoiseThreads,
-                       entries * planes * static_cast<uint32_t>(sizeof(float4)), p);
-        } else {
-            p.tiles_x = (p.width + vcrt::kDenoiseRowW - 1u) / vcrt::kDenoiseRowW;
-            const uint32_t tiles_y = (p.height + vcrt::kDenoiseRowH - 1u) / vcrt::kDenoiseRowH;
-            r = launch(g.k_denoise_var_pass, p.tiles_x * tiles_y, vcrt::kDenoiseThreads, 0, p);
-        }
-        if (r != VK_SUCCESS) return r;
-        VCRT_TRY(hipEventRecord(g.ev_dn[l + 1].get(), g.stream));
-        in = p.out;
-    }
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) {
-        *stats = vcrt_denoise_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_denoise_var_pass");
-        stats->passes = levels;
-        stats->lds_passes = lds_passes;
-        float ms = 0.f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[0].get(), g.ev_dn[levels].get()));
-        stats->kernel_ms = ms;
-        for (int32_t l = 0; l < levels; l++) {
-            VCRT_TRY(hipEventElapsedTime(&ms, g.ev_dn[l].get(), g.ev_dn[l + 1].get()));
-            stats->pass_ms[l] = ms;
-        }
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_reproject_moments_device(const float* colour, const float* motion,
-                                          const float* history_colour,
-                                          const float* history_surface,
-                                          const float* history_length, const float* albedo,
-                                          const float* history_moments, int32_t width,
-                                          int32_t height,
-                                          const vcrt_reproject_moments_params* params, float* out,
-                                          float* out_length, float* out_moments,
-                                          vcrt_reproject_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_reproject_moments_params pr;
-    const vcrt_result a = vcrt::reproject_moments_args(
-        colour, motion, history_colour, history_surface, history_length, albedo, history_moments,
-        width, height, params, out, out_length, out_moments, &pr);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernel's 16-byte loads and stores of the float4 planes, 4-byte ones of the lengths
-    if (misaligned({colour, motion, history_colour, history_surface, albedo, history_moments, out,
-                    out_moments}, 15u) ||
-        misaligned({history_length, out_length}, 3u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_reproject_moments_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = reproject_moments_device(colour, motion, history_colour, history_surface,
-                                                history_length, albedo, history_moments, width,
-                                                height, pr, out, out_length, out_moments, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_reproject_moments(const float* colour, const float* motion,
-                                   const float* history_colour, const float* history_surface,
-                                   const float* history_length, const float* albedo,
-                                   const float* history_moments, int32_t width, int32_t height,
-                                   const vcrt_reproject_moments_params* params, float* out,
-                                   float* out_length, float* out_moments,
-                                   vcrt_reproject_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_reproject_moments_params pr;
-    const vcrt_result a = vcrt::reproject_moments_args(
-        colour, motion, history_colour, history_surface, history_length, albedo, history_moments,
-        width, height, params, out, out_length, out_moments, &pr);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_reproject_moments_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    // vcrt_reproject's staging planes, then albedo, history moments, out moments
-    const float* host[4] = {colour, motion, history_colour, history_surface};
-    for (int k = 0; k < 5; k++) VCRT_TRY(g.d_rp_stage[k].reserve(pixels));
-    for (int k = 0; k < 2; k++) VCRT_TRY(g.d_rp_length[k].reserve(pixels));
-    for (int k = 0; k < 3; k++)
-        if (k != 0 || albedo) VCRT_TRY(g.d_vr_stage[k].reserve(pixels));
-    for (int k = 0; k < 4; k++)
-        VCRT_TRY(hipMemcpyAsync(g.d_rp_stage[k].data(), host[k], sizeof(float4) * pixels,
-                                hipMemcpyHostToDevice, g.stream));
-    VCRT_TRY(hipMemcpyAsync(g.d_rp_length[0].data(), history_length, sizeof(float) * pixels,
-                            hipMemcpyHostToDevice, g.stream));
-    if (albedo)
-        VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[0].data(), albedo, sizeof(float4) * pixels,
-                                hipMemcpyHostToDevice, g.stream));
-    VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[1].data(), history_moments, sizeof(float4) * pixels,
-                            hipMemcpyHostToDevice, g.stream));
-    const VkResult r = reproject_moments_device(
-        plane_of(g.d_rp_stage[0]), plane_of(g.d_rp_stage[1]), plane_of(g.d_rp_stage[2]),
-        plane_of(g.d_rp_stage[3]), g.d_rp_length[0].data(),
-        albedo ? plane_of(g.d_vr_stage[0]) : nullptr, plane_of(g.d_vr_stage[1]), width, height, pr,
-        plane_of(g.d_rp_stage[4]), g.d_rp_length[1].data(), plane_of(g.d_vr_stage[2]), stats);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(out, g.d_rp_stage[4].data(), sizeof(float4) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipMemcpyAsync(out_length, g.d_rp_length[1].data(), sizeof(float) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipMemcpyAsync(out_moments, g.d_vr_stage[2].data(), sizeof(float4) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
-vcrt_result vcrt_variance_device(const float* moments, const float* surface, int32_t width,
-                                 int32_t height, const vcrt_variance_params* params,
-                                 float* variance, vcrt_variance_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_variance_params pr;
-    const vcrt_result a = vcrt::variance_args(moments, surface, width, height, params, variance,
-                                              &pr);
-    if (a != VCRT_SUCCESS) return a;
-    if (misaligned({moments, surface}, 15u) || misaligned({variance}, 3u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_variance_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = variance_device(moments, surface, width, height, pr, variance, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_variance(const float* moments, const float* surface, int32_t width,
-                          int32_t height, const vcrt_variance_params* params, float* variance,
-                          vcrt_variance_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_variance_params pr;
-    const vcrt_result a = vcrt::variance_args(moments, surface, width, height, params, variance,
-                                              &pr);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_variance_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    // the moments and the surface through two of the moments call's planes
-    for (int k = 1; k < 3; k++) VCRT_TRY(g.d_vr_stage[k].reserve(pixels));
-    VCRT_TRY(g.d_vr_plane[1].reserve(pixels));
-    VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[1].data(), moments, sizeof(float4) * pixels,
-                            hipMemcpyHostToDevice, g.stream));
-    VCRT_TRY(hipMemcpyAsync(g.d_vr_stage[2].data(), surface, sizeof(float4) * pixels,
-                            hipMemcpyHostToDevice, g.stream));
-    const VkResult r = variance_device(plane_of(g.d_vr_stage[1]), plane_of(g.d_vr_stage[2]), width,
-                                       height, pr, g.d_vr_plane[1].data(), stats);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(variance, g.d_vr_plane[1].data(), sizeof(float) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
-vcrt_result vcrt_denoise_variance_device(const float* colour, const float* albedo,
-                                         const float* normal_depth, const float* variance,
-                                         int32_t width, int32_t height,
-                                         const vcrt_denoise_params* params, float* out,
-                                         float* out_variance, vcrt_denoise_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_denoise_params pr;
-    float k4[4];
-    const vcrt_result a = vcrt::denoise_variance_args(colour, albedo, normal_depth, variance, width,
-                                                      height, params, out, out_variance, &pr, k4);
-    if (a != VCRT_SUCCESS) return a;
-    if (misaligned({colour, albedo, normal_depth, out}, 15u) ||
-        misaligned({variance, out_variance}, 3u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_denoise_var_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = denoise_variance_device(colour, albedo, normal_depth, variance, width,
-                                               height, pr, k4, out, out_variance, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_denoise_variance(const float* colour, const float* albedo,
-                                  const float* normal_depth, const float* variance, int32_t width,
-                                  int32_t height, const vcrt_denoise_params* params, float* out,
-                                  float* out_variance, vcrt_denoise_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    vcrt_denoise_params pr;
-    float k4[4];
-    const vcrt_result a = vcrt::denoise_variance_args(colour, albedo, normal_depth, variance, width,
-                                                      height, params, out, out_variance, &pr, k4);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_denoise_var_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    // vcrt_denoise's staging planes, then the two variance planes
-    const float* host[3] = {colour, albedo, normal_depth};
-    const float* dev[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; k++)
-        if (k == 3 || host[k]) VCRT_TRY(g.d_dn_stage[k].reserve(pixels));
-    for (int k = 0; k < 2; k++) VCRT_TRY(g.d_vr_plane[k].reserve(pixels));
-    for (int k = 0; k < 3; k++) {
-        if (!host[k]) continue;
-        VCRT_TRY(hipMemcpyAsync(g.d_dn_stage[k].data(), host[k], sizeof(float4) * pixels,
-                                hipMemcpyHostToDevice, g.stream));
-        dev[k] = reinterpret_cast<const float*>(g.d_dn_stage[k].data());
-    }
-    VCRT_TRY(hipMemcpyAsync(g.d_vr_plane[0].data(), variance, sizeof(float) * pixels,
-                            hipMemcpyHostToDevice, g.stream));
-    const VkResult r = denoise_variance_device(
-        dev[0], dev[1], dev[2], g.d_vr_plane[0].data(), width, height, pr, k4,
-        plane_of(g.d_dn_stage[3]), out_variance ? g.d_vr_plane[1].data() : nullptr, stats);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(out, g.d_dn_stage[3].data(), sizeof(float4) * pixels,
-                            hipMemcpyDeviceToHost, g.stream));
-    if (out_variance)
-        VCRT_TRY(hipMemcpyAsync(out_variance, g.d_vr_plane[1].data(), sizeof(float) * pixels,
-                                hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;
 }
 
@@ -3655,36 +2731,6 @@ VkResult draw_samples_device(uint32_t first, uint32_t max_count, const uint16_t*
     return VK_SUCCESS;
 }
 
-// The count rule's launch on device planes (checked by the callers); returns when it is done.
-VkResult sample_counts_device(const float* variance, uint32_t elements, float k,
-                              const vcrt_sample_count_params& pr, uint16_t* counts,
-                              vcrt_sample_count_stats* stats) {
-    vcrt::SampleCountParams p{};
-    p.variance = variance;
-    p.counts = counts;
-    p.elements = elements;
-    p.k = k;
-    p.min_count = pr.min_count;
-    p.max_count = pr.max_count;
-    constexpr size_t words = 8 * vcrt::kSampleCountTallySlots;
-    const uint32_t grid = std::min<uint32_t>(
-        (elements + vcrt::kSampleCountThreads - 1u) / vcrt::kSampleCountThreads,
-        vcrt::kSampleCountMaxBlocks);
-    std::vector<unsigned long long> slots(words);
-    float ms = 0.f;
-    const VkResult r = timed_launch(
-        g.k_sample_counts_pass, grid, vcrt::kSampleCountThreads, p, g.d_vr_counters, words,
-        [&p](unsigned long long* c) { p.tallies = c; }, stats ? slots.data() : nullptr, &ms);
-    if (r != VK_SUCCESS) return r;
-    if (stats) {
-        *stats = vcrt_sample_count_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_sample_counts_pass");
-        stats->kernel_ms = ms;
-        for (size_t s = 0; s < words; s += 8) stats->total += slots[s];
-    }
-    return VK_SUCCESS;
-}
-
 }  // namespace
 
 vcrt_result vcrt_draw_samples_device(uint32_t first, uint32_t max_count, const uint16_t* counts,
@@ -3737,45 +2783,6 @@ vcrt_result vcrt_draw_samples(uint32_t first, uint32_t max_count, const uint16_t
                                     hipMemcpyDeviceToHost, g.stream));
         VCRT_TRY(hipStreamSynchronize(g.stream));
     }
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
-vcrt_result vcrt_sample_counts_device(const float* variance, uint32_t elements,
-                                      const vcrt_sample_count_params* params, uint16_t* counts,
-                                      vcrt_sample_count_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    float k;
-    const vcrt_result a = vcrt::sample_count_args(variance, elements, params, counts, &k);
-    if (a != VCRT_SUCCESS) return a;
-    if (misaligned({variance}, 3u) || misaligned({counts}, 1u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_sample_counts_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = sample_counts_device(variance, elements, k, *params, counts, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_sample_counts(const float* variance, uint32_t elements,
-                               const vcrt_sample_count_params* params, uint16_t* counts,
-                               vcrt_sample_count_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    float k;
-    const vcrt_result a = vcrt::sample_count_args(variance, elements, params, counts, &k);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_sample_counts_pass) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    VCRT_TRY(g.d_sm_variance.reserve(elements));
-    VCRT_TRY(g.d_sm_counts.reserve(elements));
-    VCRT_TRY(hipMemcpyAsync(g.d_sm_variance.data(), variance, sizeof(float) * elements,
-                            hipMemcpyHostToDevice, g.stream));
-    const VkResult r = sample_counts_device(g.d_sm_variance.data(), elements, k, *params,
-                                            g.d_sm_counts.data(), stats);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipMemcpyAsync(counts, g.d_sm_counts.data(), sizeof(uint16_t) * elements,
-                            hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;
 }

@@ -1,5 +1,6 @@
 // denoise_abi.h -- the argument block of the denoise kernels (denoise.hip), shared with the host
-// (capi.cpp vcrt_denoise). One struct for both kernels; one launch per pass.
+// (image_passes.cpp vcrt_denoise; the launches: image_pass_plan.hpp). One struct for both kernels;
+// one launch per pass.
 #pragma once
 
 #include <cstdint>

@@ -1,6 +1,6 @@
 // device_resources.hpp -- move-only owners of the HIP resources the host library keeps
-// (capi.cpp RendererState): device buffers, pinned host buffers and events. Header-only, never
-// throws; errors come back as hipError_t. Each owner releases what it holds in its destructor, in
+// (renderer_state.hpp RendererState): device buffers, pinned host buffers and events. Header-only,
+// never throws; errors come back as hipError_t. Each owner releases what it holds in its destructor, in
 // reset() and when it is move-assigned, so a state struct of them is torn down by assigning a
 // fresh one: no list of frees to keep in step with the members. Unit-tested on the CPU against
 // counting stand-ins of the HIP calls (tests/test_device_resources_cpu.py).

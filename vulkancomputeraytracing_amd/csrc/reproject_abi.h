@@ -1,5 +1,6 @@
 // reproject_abi.h -- the argument block of the temporal accumulation kernel (reproject.hip), shared
-// with the host (capi.cpp vcrt_reproject). One launch per call.
+// with the host (image_passes.cpp vcrt_reproject; the launch: image_pass_plan.hpp). One launch per
+// call.
 #pragma once
 
 #include <cstdint>

@@ -1,5 +1,6 @@
 // variance_abi.h -- the argument blocks of the variance-guided kernels (variance.hip), shared with
-// the host (capi.cpp vcrt_reproject_moments, vcrt_variance, vcrt_denoise_variance), and the checks
+// the host (image_passes.cpp vcrt_reproject_moments, vcrt_variance, vcrt_denoise_variance; the
+// launches: image_pass_plan.hpp), and the checks
 // every form of the three calls shares (variance.cpp).
 #pragma once
 

@@ -177,6 +177,7 @@ def ambient_dirs(first: int, count: int) -> np.ndarray:
 
 DENOISE_FIELDS = ("levels", "sigma_normal", "sigma_depth", "sigma_albedo", "sigma_colour",
                   "demodulate")
+_DENOISE_INTEGER_FIELDS = ("levels", "demodulate")
 
 
 def default_denoise_params() -> dict:
@@ -187,20 +188,8 @@ def default_denoise_params() -> dict:
 
 
 def _denoise_params(given: dict) -> N.vcrt_denoise_params:
-    """The C parameter block: the defaults with the fields `given` names (None: the default)."""
-    unknown = set(given) - set(DENOISE_FIELDS)
-    if unknown:
-        raise TypeError(f"denoise: unexpected parameters {sorted(unknown)}")
-    p = N.vcrt_denoise_params()
-    N.check("vcrt_default_denoise_params", N.lib().vcrt_default_denoise_params(ctypes.byref(p)))
-    for name, v in given.items():
-        if v is None:
-            continue
-        try:
-            setattr(p, name, int(v) if name in ("levels", "demodulate") else float(v))
-        except (TypeError, ValueError, OverflowError) as e:
-            raise ValueError(f"denoise: {name}: a number expected ({e})") from None
-    return p
+    return _float_params("denoise", N.vcrt_denoise_params, "vcrt_default_denoise_params",
+                         DENOISE_FIELDS, given, integer=_DENOISE_INTEGER_FIELDS)
 
 
 def denoise_scales(**params) -> np.ndarray:
@@ -212,39 +201,6 @@ def denoise_scales(**params) -> np.ndarray:
     return k
 
 
-def _check_planes(colour, albedo, normal_depth):
-    """The planes of a denoise call, validated before any native call: numpy float32
-    C-contiguous [height, width, 4] (converted), or torch float32 contiguous tensors of that shape
-    on one CUDA device (as they are); the guides may be None. Raises ValueError."""
-    planes = {"colour": colour, "albedo": albedo, "normal_depth": normal_depth}
-    if colour is None:
-        raise ValueError("colour: a plane expected")
-    torch_in = _is_torch(colour)
-    out = {}
-    for name, a in planes.items():
-        if a is None:
-            out[name] = None
-            continue
-        if _is_torch(a) != torch_in:
-            raise ValueError("the planes must all be numpy arrays or all torch tensors")
-        if torch_in:
-            import torch
-            if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous():
-                raise ValueError(f"{name}: a contiguous float32 CUDA tensor expected")
-            if a.device != colour.device:
-                raise ValueError(f"{name}: torch tensors must be on one CUDA device")
-        else:
-            try:
-                a = np.ascontiguousarray(a, dtype=np.float32)
-            except (TypeError, ValueError) as e:
-                raise ValueError(f"{name}: not convertible to a float32 array ({e})") from None
-        if a.ndim != 3 or a.shape[2] != 4 or tuple(a.shape) != tuple(out.get("colour", a).shape):
-            raise ValueError(f"{name}: shape [height, width, 4] of the colour plane expected, "
-                             f"got {tuple(a.shape)}")
-        out[name] = a
-    return out["colour"], out["albedo"], out["normal_depth"]
-
-
 def denoise_host(colour, albedo=None, normal_depth=None, **params) -> np.ndarray:
     """The denoiser's definition on the host (vcrt_denoise_host: no GPU): the edge-avoiding
     a-trous filter of vcrt.h over numpy planes [height, width, 4]; Renderer.denoise computes the
@@ -252,7 +208,9 @@ def denoise_host(colour, albedo=None, normal_depth=None, **params) -> np.ndarray
     demodulate (omitted: default_denoise_params)."""
     if _is_torch(colour):
         raise ValueError("denoise_host takes numpy planes")
-    colour, albedo, normal_depth = _check_planes(colour, albedo, normal_depth)
+    colour, albedo, normal_depth = _check_image_planes(
+        dict(colour=colour, albedo=albedo, normal_depth=normal_depth),
+        optional=("albedo", "normal_depth")).values()
     p = _denoise_params(params)
     out = np.empty_like(colour)
     N.check("vcrt_denoise_host", N.lib().vcrt_denoise_host(
@@ -274,62 +232,11 @@ def default_reproject_params() -> dict:
 
 
 def _reproject_params(given: dict) -> N.vcrt_reproject_params:
-    """The C parameter block: the defaults with the fields `given` names (None: the default)."""
-    unknown = set(given) - set(REPROJECT_FIELDS)
-    if unknown:
-        raise TypeError(f"reproject: unexpected parameters {sorted(unknown)}")
-    p = N.vcrt_reproject_params()
-    N.check("vcrt_default_reproject_params",
-            N.lib().vcrt_default_reproject_params(ctypes.byref(p)))
-    for name, v in given.items():
-        if v is None:
-            continue
-        try:
-            setattr(p, name, float(v))
-        except (TypeError, ValueError, OverflowError) as e:
-            raise ValueError(f"reproject: {name}: a number expected ({e})") from None
-    return p
+    return _float_params("reproject", N.vcrt_reproject_params, "vcrt_default_reproject_params",
+                         REPROJECT_FIELDS, given)
 
 
 REPROJECT_PLANES = ("colour", "motion", "history_colour", "history_surface", "history_length")
-
-
-def _check_reproject_planes(planes: dict) -> dict:
-    """The planes of a reproject call, validated before any native call: numpy float32
-    C-contiguous (converted) or torch float32 contiguous tensors on one CUDA device (as they
-    are); [height, width, 4] each, history_length [height, width]. Raises ValueError."""
-    colour = planes["colour"]
-    if colour is None:
-        raise ValueError("colour: a plane expected")
-    torch_in = _is_torch(colour)
-    out = {}
-    for name in REPROJECT_PLANES:
-        a = planes[name]
-        if a is None:
-            raise ValueError(f"{name}: a plane expected")
-        if _is_torch(a) != torch_in:
-            raise ValueError("the planes must all be numpy arrays or all torch tensors")
-        if torch_in:
-            import torch
-            if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous():
-                raise ValueError(f"{name}: a contiguous float32 CUDA tensor expected")
-            if a.device != colour.device:
-                raise ValueError(f"{name}: torch tensors must be on one CUDA device")
-        else:
-            try:
-                a = np.ascontiguousarray(a, dtype=np.float32)
-            except (TypeError, ValueError) as e:
-                raise ValueError(f"{name}: not convertible to a float32 array ({e})") from None
-        first = out.get("colour", a)
-        if name == "history_length":
-            if a.ndim != 2 or tuple(a.shape) != tuple(first.shape[:2]):
-                raise ValueError(f"{name}: shape [height, width] of the colour plane expected, "
-                                 f"got {tuple(a.shape)}")
-        elif a.ndim != 3 or a.shape[2] != 4 or tuple(a.shape) != tuple(first.shape):
-            raise ValueError(f"{name}: shape [height, width, 4] of the colour plane expected, "
-                             f"got {tuple(a.shape)}")
-        out[name] = a
-    return out
 
 
 def reproject_host(colour, motion, history_colour, history_surface, history_length, **params):
@@ -339,9 +246,9 @@ def reproject_host(colour, motion, history_colour, history_surface, history_leng
     depth_tolerance (omitted: default_reproject_params)."""
     if _is_torch(colour):
         raise ValueError("reproject_host takes numpy planes")
-    pl = _check_reproject_planes(dict(colour=colour, motion=motion, history_colour=history_colour,
-                                      history_surface=history_surface,
-                                      history_length=history_length))
+    pl = _check_image_planes(dict(colour=colour, motion=motion, history_colour=history_colour,
+                                  history_surface=history_surface,
+                                  history_length=history_length), scalar=("history_length",))
     p = _reproject_params(params)
     c = pl["colour"]
     out, length = np.empty_like(c), np.empty(c.shape[:2], np.float32)
@@ -355,9 +262,9 @@ REPROJECT_MOMENTS_FIELDS = REPROJECT_FIELDS + ("alpha_moments",)
 VARIANCE_FIELDS = ("min_history", "alpha")
 
 
-def _float_params(call: str, struct, default_fn: str, fields, given: dict):
-    """The C parameter block `struct` of float fields: the defaults with the fields `given` names
-    (None: the default)."""
+def _float_params(call: str, struct, default_fn: str, fields, given: dict, integer=()):
+    """The C parameter block `struct`: the defaults with the fields `given` names (None: the
+    default), floats but for the names in `integer`."""
     unknown = set(given) - set(fields)
     if unknown:
         raise TypeError(f"{call}: unexpected parameters {sorted(unknown)}")
@@ -367,7 +274,7 @@ def _float_params(call: str, struct, default_fn: str, fields, given: dict):
         if v is None:
             continue
         try:
-            setattr(p, name, float(v))
+            setattr(p, name, int(v) if name in integer else float(v))
         except (TypeError, ValueError, OverflowError) as e:
             raise ValueError(f"{call}: {name}: a number expected ({e})") from None
     return p
@@ -384,21 +291,9 @@ def _variance_params(given: dict) -> N.vcrt_variance_params:
 
 
 def _denoise_variance_params(given: dict) -> N.vcrt_denoise_params:
-    """vcrt_default_denoise_variance_params with the fields `given` names (None: the default)."""
-    unknown = set(given) - set(DENOISE_FIELDS)
-    if unknown:
-        raise TypeError(f"denoise_variance: unexpected parameters {sorted(unknown)}")
-    p = N.vcrt_denoise_params()
-    N.check("vcrt_default_denoise_variance_params",
-            N.lib().vcrt_default_denoise_variance_params(ctypes.byref(p)))
-    for name, v in given.items():
-        if v is None:
-            continue
-        try:
-            setattr(p, name, int(v) if name in ("levels", "demodulate") else float(v))
-        except (TypeError, ValueError, OverflowError) as e:
-            raise ValueError(f"denoise_variance: {name}: a number expected ({e})") from None
-    return p
+    return _float_params("denoise_variance", N.vcrt_denoise_params,
+                         "vcrt_default_denoise_variance_params", DENOISE_FIELDS, given,
+                         integer=_DENOISE_INTEGER_FIELDS)
 
 
 def default_reproject_moments_params() -> dict:
@@ -1202,8 +1097,10 @@ class Renderer:
                                     else torch.cuda.current_device()))  # receives the result
         elif frame is None:
             frame = self.read_framebuffer()
-        colour, albedo, nd = _check_planes(frame, guides.get("albedo"),
-                                           guides.get("normal_depth"))
+        colour, albedo, nd = _check_image_planes(
+            dict(colour=frame, albedo=guides.get("albedo"),
+                 normal_depth=guides.get("normal_depth")),
+            optional=("albedo", "normal_depth")).values()
         st = N.vcrt_denoise_stats()
         h, w = int(colour.shape[0]), int(colour.shape[1])
         if _is_torch(colour):
@@ -1345,10 +1242,11 @@ class Renderer:
             return out, hist
         if not isinstance(history, dict) or set(history) < {"colour", "surface", "length"}:
             raise ValueError('history: a dict with "colour", "surface" and "length" expected')
-        pl = _check_reproject_planes(dict(colour=frame, motion=motion,
-                                          history_colour=history["colour"],
-                                          history_surface=history["surface"],
-                                          history_length=history["length"]))
+        pl = _check_image_planes(dict(colour=frame, motion=motion,
+                                      history_colour=history["colour"],
+                                      history_surface=history["surface"],
+                                      history_length=history["length"]),
+                                 scalar=("history_length",))
         c = pl["colour"]
         h, w = int(c.shape[0]), int(c.shape[1])
         if _is_torch(c):
