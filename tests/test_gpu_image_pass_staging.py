@@ -1,5 +1,5 @@
-"""The host forms of the five image passes share one pool of staging planes (csrc/image_passes.cpp,
-RendererState.d_stage4 / d_stage1), kept and grown only. One renderer runs reproject,
+"""The host forms of the five image passes share one pool of staging planes (csrc/pass_staging.hpp,
+RendererState.staging), kept and grown only. One renderer runs reproject,
 reproject_moments, variance, denoise and denoise_variance in turn on host planes, at the largest
 shape of variance_ref.SHAPES, then the smallest, then the largest again; every output equals the
 corresponding *_host function's bit for bit. A plane left at a stale size, an output sharing a

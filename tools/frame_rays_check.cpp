@@ -7,8 +7,8 @@
 // -fsanitize=address,undefined, from the repository root (ROCM=/opt/rocm):
 //   cd vulkancomputeraytracing_amd && g++ -O1 -g -std=c++17 -fsanitize=address,undefined \
 //     -fno-sanitize-recover=undefined -ffp-contract=off -D__HIP_PLATFORM_AMD__ -I../include \
-//     -Icsrc -I$ROCM/include ../tools/frame_rays_check.cpp csrc/capi.cpp csrc/image_passes.cpp \
-//     csrc/denoise.cpp csrc/reproject.cpp csrc/variance.cpp csrc/cluster.cpp \
+//     -Icsrc -I$ROCM/include ../tools/frame_rays_check.cpp csrc/capi.cpp csrc/ray_passes.cpp \
+//     csrc/image_passes.cpp csrc/denoise.cpp csrc/reproject.cpp csrc/variance.cpp csrc/cluster.cpp \
 //     csrc/primary.cpp csrc/shader.cpp csrc/scene.cpp lib/obj/embed_code_object.o \
 //     -L$ROCM/lib -Wl,-rpath,$ROCM/lib -lamdhip64 -lrccl -ldl -pthread -o frame_rays_check
 #include <cmath>

@@ -7,8 +7,10 @@
 // (renderer_state.hpp), as in the reference (Renderer.cpp:13-33): one renderer per process. Its
 // device buffers, pinned buffers and events are owners (device_resources.hpp) that free
 // themselves, so teardown is an assignment of a fresh state (vcrt_end) and there is no list of
-// frees to maintain. The passes over caller-supplied planes (vcrt_denoise, vcrt_reproject, the
-// variance chain, vcrt_sample_counts) are in image_passes.cpp.
+// frees to maintain. The ray and occlusion queries and the passes that trace the frame's own rays
+// (vcrt_draw_features, vcrt_draw_occlusion, vcrt_draw_motion, vcrt_draw_samples) are in
+// ray_passes.cpp, the passes over caller-supplied planes (vcrt_denoise, vcrt_reproject, the
+// variance chain, vcrt_sample_counts) in image_passes.cpp.
 #include <dlfcn.h>
 #include <unistd.h>
 
@@ -47,14 +49,14 @@ namespace {
 
 using vcrt::DeviceBuffer;
 using vcrt::Event;
+using vcrt::camera_array;
+using vcrt::camera_of;
 using vcrt::g;
 using vcrt::launch;
-using vcrt::misaligned;
-using vcrt::ms_since;
+using vcrt::lens_on;
+using vcrt::make_jitter;
 using vcrt::PinnedBuffer;
-using vcrt::plane_of;
 using vcrt::RendererState;
-using vcrt::timed_launch;
 using vcrt::to_vk;
 
 // segments (u64 at 8), work_done[2] (u64 at 16), then the work-queue counters from 256
@@ -240,15 +242,6 @@ uint32_t division_magic(uint32_t n) {
     return static_cast<uint32_t>(m);
 }
 
-// Jitter of sample indices base .. base+n-1 (shader.comp:48 depends only on the index).
-void make_jitter(uint64_t base, int n, float2* out) {
-    for (int k = 0; k < n; k++) {
-        const float i = static_cast<float>(base + k), i1 = static_cast<float>(base + k + 1);
-        out[k].x = vcrt::kJitterOffset + vcrt::rand2(i, i);  // shader.comp:48
-        out[k].y = vcrt::kJitterOffset + vcrt::rand2(i1, i1);
-    }
-}
-
 // sRGB8 thresholds: T_k = the smallest float >= the linear value whose exact sRGB encode is
 // (k - 0.5) / 255, k = 1..255, so that #{k : c >= T_k} is round-to-nearest of 255 * encode(c).
 void srgb_thresholds(float out[255]) {
@@ -270,28 +263,6 @@ std::string library_dir() {
         if (slash != std::string::npos) return p.substr(0, slash);
     }
     return ".";
-}
-
-// pixel00, delta_u, delta_v, centre: TraceParams.cam
-std::array<float, 12> camera_array() {
-    const vcrt::f3 v[4] = {g.cam.pixel00, g.cam.delta_u, g.cam.delta_v, g.cam.center};
-    std::array<float, 12> c{};
-    for (int i = 0; i < 4; i++) {
-        c[3 * i + 0] = v[i].x;
-        c[3 * i + 1] = v[i].y;
-        c[3 * i + 2] = v[i].z;
-    }
-    return c;
-}
-
-// Whether a frame of camera `cam` (camera_array) gets the camera-ray lists. The camera phase of
-// the flat scans traces a fresh camera ray from its quarter's list when the ray is in the guarded
-// range. Its origin is the camera centre, a frame constant, so that half of the guard (every
-// |component| <= 2^30, in a bounded scene; also rejects NaN) is decided here: a frame that fails
-// it gets no lists, and its camera rays take the main scan, which tests their origin itself.
-bool lists_allowed(const std::array<float, 12>& cam) {
-    return g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
-           std::fabs(cam[11]) <= 0x1p30f;
 }
 
 void free_scene() {
@@ -583,7 +554,6 @@ bool read_desc(const vcrt_render_desc* in, vcrt_render_desc& out) {
     return true;
 }
 
-bool lens_on() { return g.desc.lens_radius > 0.0f; }
 bool lens_kernels_bound() {
     return g.k_smem_lens && g.k_flat_lens && g.k_flat_lens_cost && g.k_flat_global_lens &&
            g.k_flat_global_lens_cost && g.k_flat_boxes_lens && g.k_flat_boxes_lens_cost;
@@ -626,23 +596,6 @@ VkResult nccl_vk(ncclResult_t e) {
                                                              : VK_ERROR_UNKNOWN;
 }
 
-// FeatureParams.tallies, OcclusionBufferParams.tallies: slots of 64 B, summed by the callers
-constexpr size_t kFeatureCounterWords = 8 * vcrt::kFeatureTallySlots;  // u64
-
-// The timed launch of a kernel that traces the frame's own camera rays (vcrt_draw_features,
-// vcrt_draw_occlusion): one wave per local tile, its tallies' slots in d_ft_counters. A rank
-// without tiles launches nothing, and *ms stays 0.
-template <typename Params>
-VkResult frame_ray_launch(hipFunction_t f, Params& p, unsigned long long* slots, float* ms) {
-    if (g.local_tiles == 0) {
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-        return VK_SUCCESS;
-    }
-    return timed_launch(f, (g.local_tiles + 3u) / 4u, 256, 0, p, g.d_ft_counters,
-                        kFeatureCounterWords, [&p](unsigned long long* c) { p.tallies = c; },
-                        slots, ms);
-}
-
 // Zero the pixels' sums and their outlier record (a new scene, vcrt_begin, a reset): every
 // pixel starts again at the scale 2^32 (vcrt_math.h "Accumulation"). On the render stream, and
 // waited for: the render stream is non-blocking, so a memset on the null stream would not be
@@ -673,42 +626,16 @@ hipError_t reset_sums() {
 
 // TraceParams.jitter (vcrt_kernel_abi.h SetupJitterParams): the jitter term of the frame's
 // sample indices base .. base + spp - 1 (shader.comp:48), on the device with the tracer's own
-// operations.
+// operations, and TraceParams.lens of a lens renderer.
 VkResult setup_jitter(uint64_t base, bool corners = false) {
-    const int spp = g.desc.samples_per_pixel;
     const int slot = g.jitter_slot;
     g.jitter_slot ^= 1;
     // its last copy (two frames ago) is done
     VCRT_TRY(hipEventSynchronize(g.ev_jitter[slot].get()));
-    make_jitter(base, spp, g.h_jitter[slot].data());
-    VCRT_TRY(hipMemcpyAsync(g.d_jitter_in.data(), g.h_jitter[slot].data(), sizeof(float2) * spp,
-                            hipMemcpyHostToDevice, g.stream));
-    if (g.d_lens.data()) {  // the lens origins of the same sample indices: centre + offset_i
-        float4* lens = g.h_lens[slot].data();
-        for (int k = 0; k < spp; k++) {
-            const vcrt::f3 o = vcrt::add(
-                g.cam.center, vcrt::lens_offset(static_cast<uint32_t>(base + k),
-                                                g.desc.lens_radius, g.cam.u, g.cam.v));
-            lens[k] = make_float4(o.x, o.y, o.z, 0.0f);
-        }
-        VCRT_TRY(hipMemcpyAsync(g.d_lens.data(), lens, sizeof(float4) * spp,
-                                hipMemcpyHostToDevice, g.stream));
-    }
-    VCRT_TRY(hipEventRecord(g.ev_jitter[slot].get(), g.stream));
-    vcrt::SetupJitterParams sp{};
-    sp.jitter_in = g.d_jitter_in.data();
-    sp.jitter = g.d_jitter.data();
-    sp.nsamples = static_cast<uint32_t>(spp);
-    const std::array<float, 12> cam = camera_array();
-    for (int i = 0; i < 12; i++) sp.cam[i] = cam[i];
-    sp.corner = corners ? g.d_corner.data() : nullptr;
-    sp.slots = g.total_pixels;
-    sp.tiles_x = g.tiles_x;
-    sp.rank = static_cast<uint32_t>(g.desc.rank);
-    sp.world = static_cast<uint32_t>(g.desc.world_size);
-    const uint64_t total = static_cast<uint64_t>(spp) + (sp.corner ? sp.slots : 0u);
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((total + 255) / 256, 8192));
-    return launch(g.k_setup_jitter, grid, 256, 0, sp);
+    return vcrt::jitter_tables(
+        base, static_cast<uint32_t>(g.desc.samples_per_pixel),
+        {g.h_jitter[slot].data(), g.h_lens[slot].data(), g.d_jitter_in.data(), g.d_jitter.data(),
+         g.d_lens.data(), corners ? g.d_corner.data() : nullptr, g.ev_jitter[slot].get()});
 }
 
 // State of the non-blocking communicator's last operations (comm_wait.hpp): done, still in
@@ -1098,6 +1025,144 @@ VkResult build_camera_lists_device() {
 }
 
 }  // namespace
+
+// ---- what ray_passes.cpp uses too (declared in renderer_state.hpp) -----------------------------
+
+namespace vcrt {
+
+bool lens_on() { return g.desc.lens_radius > 0.0f; }
+
+void make_jitter(uint64_t base, int n, float2* out) {
+    for (int k = 0; k < n; k++) {
+        const float i = static_cast<float>(base + k), i1 = static_cast<float>(base + k + 1);
+        out[k].x = kJitterOffset + rand2(i, i);  // shader.comp:48
+        out[k].y = kJitterOffset + rand2(i1, i1);
+    }
+}
+
+std::array<float, 12> camera_array() {
+    const f3 v[4] = {g.cam.pixel00, g.cam.delta_u, g.cam.delta_v, g.cam.center};
+    std::array<float, 12> c{};
+    for (int i = 0; i < 4; i++) {
+        c[3 * i + 0] = v[i].x;
+        c[3 * i + 1] = v[i].y;
+        c[3 * i + 2] = v[i].z;
+    }
+    return c;
+}
+
+// The camera phase of the flat scans traces a fresh camera ray from its quarter's list when the
+// ray is in the guarded range. Its origin is the camera centre, a frame constant, so that half of
+// the guard (every |component| <= 2^30, in a bounded scene; also rejects NaN) is decided here: a
+// frame that fails it gets no lists, and its camera rays take the main scan, which tests their
+// origin itself.
+bool lists_allowed(const std::array<float, 12>& cam) {
+    return g.scene_bounded && std::fabs(cam[9]) <= 0x1p30f && std::fabs(cam[10]) <= 0x1p30f &&
+           std::fabs(cam[11]) <= 0x1p30f;
+}
+
+Camera camera_of(int32_t width, int32_t height, const vcrt_camera& c) {
+    return make_camera(width, height, mk(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]),
+                       mk(c.lookat[0], c.lookat[1], c.lookat[2]), mk(c.vup[0], c.vup[1], c.vup[2]),
+                       c.vfov, [](double x) { return std::tan(x); });
+}
+
+// The scene's part of a kernel's argument block: the scan tables, the shading rows, the margins
+// and the flags' scene bits (frames and ray queries).
+void scene_params(TraceParams& p) {
+    p.geom = g.d_geom.data();
+    p.center_radius = g.d_center_radius.data();
+    p.shade = g.d_shade.data();
+    p.material = g.d_material.data();
+    p.cgroup = g.d_cgroup.data();
+    p.cbound = g.d_cbound.data();
+    p.cbound_nf = g.d_cbound_nf.data();
+    p.cnode = g.d_cnode.data();
+    p.cnode_nf = g.d_cnode_nf.data();
+    p.ctop = g.d_ctop.data();
+    p.ncgroups = g.ncgroups;
+    p.nbig = g.ncbig;
+    for (int k = 0; k < 4; k++) p.box_margin[k] = g.cmargin[k];
+    p.slab[0] = g.cslab[0];
+    p.slab[1] = g.cslab[1];
+    p.fp_tab = g.d_fp_tab.data();
+    for (int k = 0; k < 2; k++) {
+        p.fp_x[k] = g.cfp_x[k];
+        p.fp_z[k] = g.cfp_z[k];
+        p.fp_y[k] = g.cfp_y[k];
+    }
+    p.fp_k2 = g.cfp_k2;
+    p.fp_always = g.cfp_always;
+    p.gf_tab = g.d_gf_tab.data();
+    for (int k = 0; k < 2; k++) {
+        p.gf_x[k] = g.cgf_x[k];
+        p.gf_z[k] = g.cgf_z[k];
+    }
+    p.gf_k2 = g.cgf_k2;
+    p.gf_n = g.cgf_n;
+    for (int k = 0; k < 4; k++) p.gf_always[k] = g.cgf_always[k];
+    p.nspheres = g.nspheres;
+    p.flags = (g.scene_bounded ? kFlagSceneBounded : 0u) |
+              (g.radii_safe ? kFlagRadiiSafe : 0u) |
+              (g.ncgroups > 0 && g.cslab_on ? kFlagSlab : 0u);
+    for (int j = 0; j < 13; j++) p.sin_c[j] = kSinC[j];
+}
+
+void frame_params(TraceParams& p, const float4* jitter, const float4* lens, int32_t spp,
+                  int32_t max_depth) {
+    scene_params(p);
+    p.jitter = jitter;
+    p.lens = lens;
+    p.corner = g.d_corner.data();
+    p.prim_info = g.d_prim_info.data();
+    p.prim_ids = g.d_prim_ids.data();
+    p.cam_rec = reinterpret_cast<const float4*>(g.d_cam_rec.data());
+    p.width = g.desc.width;
+    p.height = g.desc.height;
+    p.spp = spp;
+    p.max_depth = max_depth;
+    p.rank = g.desc.rank;
+    p.world = g.desc.world_size;
+    p.tiles_x = g.tiles_x;
+    p.local_tiles = g.local_tiles;
+    const std::array<float, 12> cam = camera_array();
+    for (int i = 0; i < 12; i++) p.cam[i] = cam[i];
+    // (The group footprint keeps to the lists the scene has: a frame without them sends no
+    // camera ray to a culled scan.)
+    if (!lists_allowed(cam)) p.prim_info = nullptr;
+}
+
+VkResult jitter_tables(uint64_t base, uint32_t n, const JitterTables& t) {
+    make_jitter(base, static_cast<int>(n), t.h_jitter);
+    VCRT_TRY(hipMemcpyAsync(t.d_jitter_in, t.h_jitter, sizeof(float2) * n, hipMemcpyHostToDevice,
+                            g.stream));
+    if (t.d_lens) {  // the lens origins of the same sample indices: centre + offset_i
+        for (uint32_t k = 0; k < n; k++) {
+            const f3 o = add(g.cam.center, lens_offset(static_cast<uint32_t>(base + k),
+                                                       g.desc.lens_radius, g.cam.u, g.cam.v));
+            t.h_lens[k] = make_float4(o.x, o.y, o.z, 0.0f);
+        }
+        VCRT_TRY(hipMemcpyAsync(t.d_lens, t.h_lens, sizeof(float4) * n, hipMemcpyHostToDevice,
+                                g.stream));
+    }
+    if (t.copied) VCRT_TRY(hipEventRecord(t.copied, g.stream));
+    SetupJitterParams sp{};
+    sp.jitter_in = t.d_jitter_in;
+    sp.jitter = t.d_jitter;
+    sp.nsamples = n;
+    const std::array<float, 12> cam = camera_array();
+    for (int i = 0; i < 12; i++) sp.cam[i] = cam[i];
+    sp.corner = t.d_corner;
+    sp.slots = g.total_pixels;
+    sp.tiles_x = g.tiles_x;
+    sp.rank = static_cast<uint32_t>(g.desc.rank);
+    sp.world = static_cast<uint32_t>(g.desc.world_size);
+    const uint64_t total = static_cast<uint64_t>(n) + (sp.corner ? sp.slots : 0u);
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((total + 255) / 256, 8192));
+    return launch(g.k_setup_jitter, grid, 256, 0, sp);
+}
+
+}  // namespace vcrt
 
 extern "C" {
 
@@ -1530,54 +1595,11 @@ VkResult build_block_order(uint32_t total_blocks) {
 // resolve pass) on the render stream, waited for; *outlier_max receives the float bits of the
 // largest |quantum sum| that did not fit its pixel's scale (0: none; vcrt_math.h
 // "Accumulation").
-// The scene's part of a kernel's argument block: the scan tables, the shading rows, the margins
-// and the flags' scene bits (frames and ray queries).
-static void scene_params(vcrt::TraceParams& p) {
-    p.geom = g.d_geom.data();
-    p.center_radius = g.d_center_radius.data();
-    p.shade = g.d_shade.data();
-    p.material = g.d_material.data();
-    p.cgroup = g.d_cgroup.data();
-    p.cbound = g.d_cbound.data();
-    p.cbound_nf = g.d_cbound_nf.data();
-    p.cnode = g.d_cnode.data();
-    p.cnode_nf = g.d_cnode_nf.data();
-    p.ctop = g.d_ctop.data();
-    p.ncgroups = g.ncgroups;
-    p.nbig = g.ncbig;
-    for (int k = 0; k < 4; k++) p.box_margin[k] = g.cmargin[k];
-    p.slab[0] = g.cslab[0];
-    p.slab[1] = g.cslab[1];
-    p.fp_tab = g.d_fp_tab.data();
-    for (int k = 0; k < 2; k++) {
-        p.fp_x[k] = g.cfp_x[k];
-        p.fp_z[k] = g.cfp_z[k];
-        p.fp_y[k] = g.cfp_y[k];
-    }
-    p.fp_k2 = g.cfp_k2;
-    p.fp_always = g.cfp_always;
-    p.gf_tab = g.d_gf_tab.data();
-    for (int k = 0; k < 2; k++) {
-        p.gf_x[k] = g.cgf_x[k];
-        p.gf_z[k] = g.cgf_z[k];
-    }
-    p.gf_k2 = g.cgf_k2;
-    p.gf_n = g.cgf_n;
-    for (int k = 0; k < 4; k++) p.gf_always[k] = g.cgf_always[k];
-    p.nspheres = g.nspheres;
-    p.flags = (g.scene_bounded ? vcrt::kFlagSceneBounded : 0u) |
-              (g.radii_safe ? vcrt::kFlagRadiiSafe : 0u) |
-              (g.ncgroups > 0 && g.cslab_on ? vcrt::kFlagSlab : 0u);
-    for (int j = 0; j < 13; j++) p.sin_c[j] = vcrt::kSinC[j];
-}
-
 static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     const uint32_t pixels = g.total_pixels;
     vcrt::TraceParams p{};
-    scene_params(p);
-    p.jitter = g.d_jitter.data();
-    p.lens = g.d_lens.data();
-    p.corner = g.d_corner.data();
+    vcrt::frame_params(p, g.d_jitter.data(), g.d_lens.data(), g.desc.samples_per_pixel,
+                       g.desc.max_depth);
     p.out = g.d_fb;
     p.accum = g.d_accum.data();
     unsigned long long* const counters64 = g.d_counters.data();  // (the layout: kCounterBytes)
@@ -1585,17 +1607,6 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.segments = counters64 + 1;
     p.debug = g.d_debug.data();
     p.work_done = counters64 + 2;
-    p.prim_info = g.d_prim_info.data();
-    p.prim_ids = g.d_prim_ids.data();
-    p.cam_rec = reinterpret_cast<const float4*>(g.d_cam_rec.data());
-    p.width = g.desc.width;
-    p.height = g.desc.height;
-    p.spp = g.desc.samples_per_pixel;
-    p.max_depth = g.desc.max_depth;
-    p.rank = g.desc.rank;
-    p.world = g.desc.world_size;
-    p.tiles_x = g.tiles_x;
-    p.local_tiles = g.local_tiles;
     p.total_items = g.total_items;
     p.chunk = g.chunk;
     p.quantum_mask = static_cast<uint32_t>(g.quantum - 1);
@@ -1622,11 +1633,6 @@ static VkResult trace_frame(uint64_t spp_total, uint32_t* outlier_max) {
     p.region = nullptr;
     p.nch_magic[0] = g.nch_magic[0];
     p.nch_magic[1] = g.nch_magic[1];
-    const std::array<float, 12> cam = camera_array();
-    for (int i = 0; i < 12; i++) p.cam[i] = cam[i];
-    // (The group footprint keeps to the lists the scene has: a frame without them sends no
-    // camera ray to a culled scan.)
-    if (!lists_allowed(cam)) p.prim_info = nullptr;
     const KernelChoice kc = select_kernel();
     hipFunction_t f = g.debug_stats == 1 ? kc.stats : kc.f;
     if (f == nullptr) return VK_ERROR_FEATURE_NOT_PRESENT;  // (a lens, no lens kernels loaded)
@@ -1949,616 +1955,6 @@ vcrt_result vcrt_end(void) {
     return VCRT_SUCCESS;
 }
 
-// ---- ray queries --------------------------------------------------------------------------
-
-namespace {
-
-constexpr uint32_t kRayQueryMax = 1u << 30;
-constexpr size_t kRayCounterWords = 4;  // u64: the u32 work index in [0], tallies in [1..3]
-
-// The arguments every form of the call checks, in the order of the header's table.
-vcrt_result ray_query_args(const float* origins, const float* dirs, uint32_t count,
-                           int32_t max_depth, const void* radiance, const void* hits) {
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (count > 0 && (!origins || !dirs)) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!radiance && !hits) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (max_depth < 0 || count > kRayQueryMax) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
-    if (!g.k_trace_rays) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    return VCRT_SUCCESS;
-}
-
-// A query's grid: the blocks of kQueryBlock threads the occupancy query admits per CU, on every
-// CU, capped at the blocks the batch fills.
-constexpr uint32_t kQueryBlock = 256;
-uint32_t query_grid(hipFunction_t f, uint32_t count) {
-    int per_cu = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, kQueryBlock, 0) !=
-            hipSuccess ||
-        per_cu <= 0)
-        per_cu = 1;
-    return std::min<uint32_t>(static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(g.num_cus),
-                              (count + kQueryBlock - 1) / kQueryBlock);
-}
-
-// The launch on device pointers (checked by the callers): a persistent grid sized from the
-// occupancy query as a frame's is, capped at the batch; returns when the kernel is done.
-VkResult ray_query_device(const float* origins, const float* dirs, uint32_t count,
-                          int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
-                          vcrt_ray_stats* stats) {
-    if (stats) {
-        *stats = vcrt_ray_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_trace_rays");
-    }
-    if (count == 0) return VK_SUCCESS;
-    vcrt::RayQueryParams p{};
-    scene_params(p.scene);
-    p.scene.max_depth = max_depth;
-    p.origins = origins;
-    p.dirs = dirs;
-    p.radiance = reinterpret_cast<float4*>(radiance);
-    p.hits = reinterpret_cast<uint4*>(hits);
-    p.count = count;
-    unsigned long long counters[kRayCounterWords] = {};
-    float ms = 0.f;
-    const VkResult r = timed_launch(
-        g.k_trace_rays, query_grid(g.k_trace_rays, count), kQueryBlock, 0, p, g.d_rq_counters,
-        kRayCounterWords,
-        [&p](unsigned long long* c) {
-            p.work = reinterpret_cast<uint32_t*>(c);
-            p.tallies = c + 1;
-        },
-        stats ? counters : nullptr, &ms);
-    if (r != VK_SUCCESS) return r;
-    if (stats) {
-        stats->kernel_ms = ms;
-        stats->segments = counters[1];
-        stats->group_tests = counters[2];
-        stats->bound_tests = counters[3];
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_trace_rays_device(const float* origins, const float* dirs, uint32_t count,
-                                   int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
-                                   vcrt_ray_stats* stats) {
-    const vcrt_result a = ray_query_args(origins, dirs, count, max_depth, radiance, hits);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernel's 16-byte stores
-    if (misaligned({radiance, hits}, 15u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    return ray_query_device(origins, dirs, count, max_depth, radiance, hits, stats);
-}
-
-vcrt_result vcrt_trace_rays(const float* origins, const float* dirs, uint32_t count,
-                            int32_t max_depth, float* radiance, vcrt_ray_hit* hits,
-                            vcrt_ray_stats* stats) {
-    static_assert(sizeof(vcrt_ray_hit) == 32, "two 16-byte stores per record");
-    const vcrt_result a = ray_query_args(origins, dirs, count, max_depth, radiance, hits);
-    if (a != VCRT_SUCCESS) return a;
-    const size_t n = count, in_bytes = 3 * sizeof(float) * n;
-    VCRT_TRY(g.d_rq_rays.reserve(6 * n));
-    if (radiance) VCRT_TRY(g.d_rq_radiance.reserve(n));
-    if (hits) VCRT_TRY(g.d_rq_hits.reserve(n));
-    float* d_origins = g.d_rq_rays.data();
-    float* d_dirs = g.d_rq_rays.data() + 3 * n;
-    if (n) {
-        VCRT_TRY(hipMemcpyAsync(d_origins, origins, in_bytes, hipMemcpyHostToDevice, g.stream));
-        VCRT_TRY(hipMemcpyAsync(d_dirs, dirs, in_bytes, hipMemcpyHostToDevice, g.stream));
-    }
-    const VkResult r = ray_query_device(
-        d_origins, d_dirs, count, max_depth,
-        radiance ? reinterpret_cast<float*>(g.d_rq_radiance.data()) : nullptr,
-        hits ? g.d_rq_hits.data() : nullptr, stats);
-    if (r != VK_SUCCESS || n == 0) return r;
-    if (radiance)
-        VCRT_TRY(hipMemcpyAsync(radiance, g.d_rq_radiance.data(), sizeof(float4) * n,
-                                hipMemcpyDeviceToHost, g.stream));
-    if (hits)
-        VCRT_TRY(hipMemcpyAsync(hits, g.d_rq_hits.data(), sizeof(vcrt_ray_hit) * n,
-                                hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    return VCRT_SUCCESS;
-}
-
-// ---- occlusion queries --------------------------------------------------------------------
-
-namespace {
-
-vcrt_result occlusion_args(const float* origins, const float* dirs, uint32_t count,
-                           const uint8_t* occluded) {
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (count > 0 && (!origins || !dirs || !occluded)) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (count > kRayQueryMax) return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
-    if (!g.k_occlude_rays) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    return VCRT_SUCCESS;
-}
-
-// The launch on device pointers (checked by the callers): every ray is one scan, so the grid
-// holds no more waves than the occupancy query admits and no more blocks than the batch fills;
-// returns when the kernel is done.
-VkResult occlusion_device(const float* origins, const float* dirs, const float* tmax,
-                          uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats) {
-    if (stats) {
-        *stats = vcrt_ray_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_occlude_rays");
-    }
-    if (count == 0) return VK_SUCCESS;
-    vcrt::OcclusionParams p{};
-    scene_params(p.scene);
-    p.origins = origins;
-    p.dirs = dirs;
-    p.tmax = tmax;
-    p.occluded = occluded;
-    p.count = count;
-    unsigned long long counters[kRayCounterWords] = {};
-    float ms = 0.f;
-    const VkResult r = timed_launch(
-        g.k_occlude_rays, query_grid(g.k_occlude_rays, count), kQueryBlock, 0, p,
-        g.d_rq_counters, kRayCounterWords, [&p](unsigned long long* c) { p.tallies = c + 1; },
-        stats ? counters : nullptr, &ms);
-    if (r != VK_SUCCESS) return r;
-    if (stats) {
-        stats->kernel_ms = ms;
-        stats->segments = count;  // one scan per ray
-        stats->group_tests = counters[1];
-        stats->bound_tests = counters[2];
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_occlude_rays_device(const float* origins, const float* dirs, const float* tmax,
-                                     uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats) {
-    const vcrt_result a = occlusion_args(origins, dirs, count, occluded);
-    if (a != VCRT_SUCCESS) return a;
-    return occlusion_device(origins, dirs, tmax, count, occluded, stats);
-}
-
-vcrt_result vcrt_occlude_rays(const float* origins, const float* dirs, const float* tmax,
-                              uint32_t count, uint8_t* occluded, vcrt_ray_stats* stats) {
-    const vcrt_result a = occlusion_args(origins, dirs, count, occluded);
-    if (a != VCRT_SUCCESS) return a;
-    const size_t n = count, in_bytes = 3 * sizeof(float) * n;
-    VCRT_TRY(g.d_rq_rays.reserve(6 * n));
-    if (tmax) VCRT_TRY(g.d_oq_tmax.reserve(n));
-    VCRT_TRY(g.d_oq_occluded.reserve(n));
-    float* d_origins = g.d_rq_rays.data();
-    float* d_dirs = g.d_rq_rays.data() + 3 * n;
-    if (n) {
-        VCRT_TRY(hipMemcpyAsync(d_origins, origins, in_bytes, hipMemcpyHostToDevice, g.stream));
-        VCRT_TRY(hipMemcpyAsync(d_dirs, dirs, in_bytes, hipMemcpyHostToDevice, g.stream));
-        if (tmax)
-            VCRT_TRY(hipMemcpyAsync(g.d_oq_tmax.data(), tmax, sizeof(float) * n,
-                                    hipMemcpyHostToDevice, g.stream));
-    }
-    const VkResult r = occlusion_device(d_origins, d_dirs, tmax ? g.d_oq_tmax.data() : nullptr,
-                                        count, g.d_oq_occluded.data(), stats);
-    if (r != VK_SUCCESS || n == 0) return r;
-    VCRT_TRY(hipMemcpyAsync(occluded, g.d_oq_occluded.data(), n, hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    return VCRT_SUCCESS;
-}
-
-// ---- feature buffers ----------------------------------------------------------------------
-
-namespace {
-
-constexpr uint64_t kFeatureMaxIndex = uint64_t{1} << 19;  // vcrt_lens_offsets' index bound
-
-// The arguments both forms of the call check, before anything touches the GPU. The arguments'
-// own faults come first, so that they read the same with and without a renderer.
-vcrt_result feature_args(uint32_t first, uint32_t n, const void* albedo, const void* normal_depth,
-                         const void* sphere) {
-    if (!albedo && !normal_depth && !sphere) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (n == 0 || static_cast<uint64_t>(first) + n > kFeatureMaxIndex)
-        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    return VCRT_SUCCESS;
-}
-
-// The jitter terms (vcrt_setup_jitter, the frame's kernel) and, for a lens renderer, the lens
-// origins (the frame's host operations: setup_jitter above) of sample indices first .. first +
-// n - 1 in the call's own tables.
-VkResult feature_tables(uint32_t first, uint32_t n) {
-    VCRT_TRY(g.d_ft_jitter_in.reserve(n));
-    VCRT_TRY(g.d_ft_jitter.reserve(n));
-    g.h_ft_jitter.resize(n);
-    make_jitter(first, static_cast<int>(n), g.h_ft_jitter.data());
-    VCRT_TRY(hipMemcpyAsync(g.d_ft_jitter_in.data(), g.h_ft_jitter.data(), sizeof(float2) * n,
-                            hipMemcpyHostToDevice, g.stream));
-    if (lens_on()) {
-        VCRT_TRY(g.d_ft_lens.reserve(n));
-        g.h_ft_lens.resize(n);
-        for (uint32_t k = 0; k < n; k++) {
-            const vcrt::f3 o = vcrt::add(
-                g.cam.center, vcrt::lens_offset(first + k, g.desc.lens_radius, g.cam.u, g.cam.v));
-            g.h_ft_lens[k] = make_float4(o.x, o.y, o.z, 0.0f);
-        }
-        VCRT_TRY(hipMemcpyAsync(g.d_ft_lens.data(), g.h_ft_lens.data(), sizeof(float4) * n,
-                                hipMemcpyHostToDevice, g.stream));
-    }
-    vcrt::SetupJitterParams sp{};
-    sp.jitter_in = g.d_ft_jitter_in.data();
-    sp.jitter = g.d_ft_jitter.data();
-    sp.nsamples = n;
-    const std::array<float, 12> cam = camera_array();
-    for (int i = 0; i < 12; i++) sp.cam[i] = cam[i];
-    sp.corner = nullptr;
-    sp.slots = g.total_pixels;
-    sp.tiles_x = g.tiles_x;
-    sp.rank = static_cast<uint32_t>(g.desc.rank);
-    sp.world = static_cast<uint32_t>(g.desc.world_size);
-    return launch(g.k_setup_jitter, std::min<uint32_t>((n + 255u) / 256u, 8192u), 256, 0, sp);
-}
-
-// The scene block of the kernels that trace the frame's own camera rays (FeatureParams,
-// OcclusionBufferParams): a frame's, with the call's own jitter and lens tables of n samples.
-void frame_ray_scene(vcrt::TraceParams& s, uint32_t n) {
-    scene_params(s);
-    s.jitter = g.d_ft_jitter.data();
-    s.lens = lens_on() ? g.d_ft_lens.data() : nullptr;
-    s.corner = g.d_corner.data();
-    s.prim_info = g.d_prim_info.data();
-    s.prim_ids = g.d_prim_ids.data();
-    s.cam_rec = reinterpret_cast<const float4*>(g.d_cam_rec.data());
-    s.width = g.desc.width;
-    s.height = g.desc.height;
-    s.spp = static_cast<int32_t>(n);
-    s.max_depth = 1;
-    s.rank = g.desc.rank;
-    s.world = g.desc.world_size;
-    s.tiles_x = g.tiles_x;
-    s.local_tiles = g.local_tiles;
-    const std::array<float, 12> cam = camera_array();
-    for (int i = 0; i < 12; i++) s.cam[i] = cam[i];
-    // the lists go to a frame whose camera centre passes the range guard (trace_frame)
-    if (!lists_allowed(cam)) s.prim_info = nullptr;
-}
-
-// The launch on device pointers (checked by the callers): one wave per local tile; returns when
-// the kernel is done.
-VkResult draw_features_device(uint32_t first, uint32_t n, float* albedo, float* normal_depth,
-                              int32_t* sphere, vcrt_feature_stats* stats) {
-    if (stats) {
-        *stats = vcrt_feature_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_features");
-    }
-    const VkResult t = feature_tables(first, n);
-    if (t != VK_SUCCESS) return t;
-    vcrt::FeatureParams p{};
-    frame_ray_scene(p.scene, n);
-    p.albedo = reinterpret_cast<float4*>(albedo);
-    p.normal_depth = reinterpret_cast<float4*>(normal_depth);
-    p.sphere = sphere;
-    p.n = n;
-    p.use_lists = g.feature_lists ? 1u : 0u;
-    unsigned long long slots[kFeatureCounterWords] = {};
-    float ms = 0.f;
-    const VkResult r = frame_ray_launch(g.k_frame_features, p, stats ? slots : nullptr, &ms);
-    if (r != VK_SUCCESS) return r;
-    if (stats) {
-        unsigned long long counters[3] = {0, 0, 0};
-        for (size_t s = 0; s < kFeatureCounterWords; s += 8)
-            for (int c = 0; c < 3; c++) counters[c] += slots[s + c];
-        stats->kernel_ms = ms;
-        stats->rays = g.local_pixels * n;
-        stats->listed_rays = counters[0];
-        stats->group_tests = counters[1];
-        stats->bound_tests = counters[2];
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_draw_features_device(uint32_t first, uint32_t n, float* albedo,
-                                      float* normal_depth, int32_t* sphere,
-                                      vcrt_feature_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = feature_args(first, n, albedo, normal_depth, sphere);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernel's 16-byte stores (and the ids' 4-byte ones)
-    if (misaligned({albedo, normal_depth}, 15u) || misaligned({sphere}, 3u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_frame_features) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = draw_features_device(first, n, albedo, normal_depth, sphere, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_draw_features(uint32_t first, uint32_t n, float* albedo, float* normal_depth,
-                               int32_t* sphere, vcrt_feature_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = feature_args(first, n, albedo, normal_depth, sphere);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.k_frame_features) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t elems = g.local_elems;
-    if (albedo) VCRT_TRY(g.d_ft_albedo.reserve(elems));
-    if (normal_depth) VCRT_TRY(g.d_ft_normal_depth.reserve(elems));
-    if (sphere) VCRT_TRY(g.d_ft_sphere.reserve(elems));
-    // packed tiles: the slots outside the frame keep what the caller's planes hold
-    if (g.desc.world_size > 1 && elems) {
-        if (albedo)
-            VCRT_TRY(hipMemcpyAsync(g.d_ft_albedo.data(), albedo, sizeof(float4) * elems,
-                                    hipMemcpyHostToDevice, g.stream));
-        if (normal_depth)
-            VCRT_TRY(hipMemcpyAsync(g.d_ft_normal_depth.data(), normal_depth,
-                                    sizeof(float4) * elems, hipMemcpyHostToDevice, g.stream));
-        if (sphere)
-            VCRT_TRY(hipMemcpyAsync(g.d_ft_sphere.data(), sphere, sizeof(int32_t) * elems,
-                                    hipMemcpyHostToDevice, g.stream));
-    }
-    const VkResult r = draw_features_device(
-        first, n, albedo ? reinterpret_cast<float*>(g.d_ft_albedo.data()) : nullptr,
-        normal_depth ? reinterpret_cast<float*>(g.d_ft_normal_depth.data()) : nullptr,
-        sphere ? g.d_ft_sphere.data() : nullptr, stats);
-    if (r != VK_SUCCESS) return r;
-    if (elems) {
-        if (albedo)
-            VCRT_TRY(hipMemcpyAsync(albedo, g.d_ft_albedo.data(), sizeof(float4) * elems,
-                                    hipMemcpyDeviceToHost, g.stream));
-        if (normal_depth)
-            VCRT_TRY(hipMemcpyAsync(normal_depth, g.d_ft_normal_depth.data(),
-                                    sizeof(float4) * elems, hipMemcpyDeviceToHost, g.stream));
-        if (sphere)
-            VCRT_TRY(hipMemcpyAsync(sphere, g.d_ft_sphere.data(), sizeof(int32_t) * elems,
-                                    hipMemcpyDeviceToHost, g.stream));
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-    }
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
-// ---- the ambient visibility buffer ----------------------------------------------------------
-
-namespace {
-
-constexpr uint64_t kAmbientMaxRays = 4096;               // n * m of one call
-constexpr uint64_t kAmbientMaxIndex = uint64_t{1} << 22;  // j + 0.5f is exact below 2^23
-
-// The arguments both forms of the call check, before anything touches the GPU: the ranges
-// first, so that they read the same with and without a renderer.
-vcrt_result ambient_args(uint32_t first, uint32_t n, uint32_t m, float reach,
-                         const void* visibility) {
-    const uint64_t end = static_cast<uint64_t>(first) + n;
-    if (n == 0 || m == 0 || m > 256 || end > kFeatureMaxIndex ||
-        static_cast<uint64_t>(n) * m > kAmbientMaxRays || end * m > kAmbientMaxIndex)
-        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
-    if (!visibility || std::isnan(reach)) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    return VCRT_SUCCESS;
-}
-
-// The launch on a device plane (checked by the callers): one wave per local tile; returns when
-// the kernel is done.
-VkResult draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, float reach,
-                               float* visibility, vcrt_occlusion_buffer_stats* stats) {
-    if (stats) {
-        *stats = vcrt_occlusion_buffer_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_occlusion");
-    }
-    const VkResult t = feature_tables(first, n);
-    if (t != VK_SUCCESS) return t;
-    // u_j of j = first m .. (first + n) m - 1, sample-major (vcrt_ambient_dirs' values)
-    const uint32_t ndirs = n * m;
-    VCRT_TRY(g.d_ao_dirs.reserve(ndirs));
-    g.h_ao_dirs.resize(ndirs);
-    for (uint32_t k = 0; k < ndirs; k++) {
-        const vcrt::f3 u = vcrt::ambient_dir(first * m + k);
-        g.h_ao_dirs[k] = make_float4(u.x, u.y, u.z, 0.0f);
-    }
-    VCRT_TRY(hipMemcpyAsync(g.d_ao_dirs.data(), g.h_ao_dirs.data(), sizeof(float4) * ndirs,
-                            hipMemcpyHostToDevice, g.stream));
-    vcrt::OcclusionBufferParams p{};
-    frame_ray_scene(p.scene, n);
-    p.visibility = reinterpret_cast<float4*>(visibility);
-    p.dirs = g.d_ao_dirs.data();
-    p.n = n;
-    p.m = m;
-    p.reach = reach;
-    p.use_lists = g.feature_lists ? 1u : 0u;
-    unsigned long long slots[kFeatureCounterWords] = {};
-    float ms = 0.f;
-    const VkResult r = frame_ray_launch(g.k_frame_occlusion, p, stats ? slots : nullptr, &ms);
-    if (r != VK_SUCCESS) return r;
-    if (stats) {
-        unsigned long long counters[5] = {0, 0, 0, 0, 0};
-        for (size_t s = 0; s < kFeatureCounterWords; s += 8)
-            for (int c = 0; c < 5; c++) counters[c] += slots[s + c];
-        stats->kernel_ms = ms;
-        stats->rays = g.local_pixels * n;
-        stats->hit_rays = counters[3];
-        stats->secondary_rays = counters[3] * m;
-        stats->occluded = counters[4];
-        stats->listed_rays = counters[0];
-        stats->group_tests = counters[1];
-        stats->bound_tests = counters[2];
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_draw_occlusion_device(uint32_t first, uint32_t n, uint32_t m, float reach,
-                                       float* visibility, vcrt_occlusion_buffer_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = ambient_args(first, n, m, reach, visibility);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernel's 16-byte stores
-    if (misaligned({visibility}, 15u)) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_frame_occlusion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = draw_occlusion_device(first, n, m, reach, visibility, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_draw_occlusion(uint32_t first, uint32_t n, uint32_t m, float reach,
-                                float* visibility, vcrt_occlusion_buffer_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = ambient_args(first, n, m, reach, visibility);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.k_frame_occlusion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t elems = g.local_elems;
-    VCRT_TRY(g.d_ao_plane.reserve(elems));
-    // packed tiles: the slots outside the frame keep what the caller's plane holds
-    if (g.desc.world_size > 1 && elems)
-        VCRT_TRY(hipMemcpyAsync(g.d_ao_plane.data(), visibility, sizeof(float4) * elems,
-                                hipMemcpyHostToDevice, g.stream));
-    const VkResult r = draw_occlusion_device(first, n, m, reach,
-                                             reinterpret_cast<float*>(g.d_ao_plane.data()), stats);
-    if (r != VK_SUCCESS) return r;
-    if (elems) {
-        VCRT_TRY(hipMemcpyAsync(visibility, g.d_ao_plane.data(), sizeof(float4) * elems,
-                                hipMemcpyDeviceToHost, g.stream));
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-    }
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
-// ---- the reprojection map ---------------------------------------------------------------------
-
-namespace {
-
-constexpr int64_t kMotionMaxSpheres = (int64_t{1} << 24) - 2;  // key = (float)(s + 2) stays exact
-
-vcrt::Camera camera_of(int32_t width, int32_t height, const vcrt_camera& c) {
-    return vcrt::make_camera(width, height, vcrt::mk(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]),
-                             vcrt::mk(c.lookat[0], c.lookat[1], c.lookat[2]),
-                             vcrt::mk(c.vup[0], c.vup[1], c.vup[2]), c.vfov,
-                             [](double x) { return std::tan(x); });
-}
-
-// The arguments both forms of the call check, before anything touches the GPU.
-vcrt_result motion_args(const vcrt_sphere* prev_spheres, int32_t count, const void* motion,
-                        const void* surface) {
-    if (!motion && !surface) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if ((prev_spheres && count != g.nspheres) || g.nspheres >= kMotionMaxSpheres)
-        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
-    return VCRT_SUCCESS;
-}
-
-// The launch on device pointers (checked by the callers): one wave per local tile; returns when
-// the kernel is done. prev: null (the current values), else `stride` floats a sphere.
-VkResult draw_motion_device(const vcrt_camera* prev_camera, const float* prev, uint32_t stride,
-                            float* motion, float* surface, vcrt_motion_stats* stats) {
-    if (stats) {
-        *stats = vcrt_motion_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_frame_motion");
-    }
-    vcrt::MotionParams p{};
-    frame_ray_scene(p.scene, 1);
-    p.scene.jitter = nullptr;  // the centre ray has no jitter and no lens offset
-    p.scene.lens = nullptr;
-    p.motion = reinterpret_cast<float4*>(motion);
-    p.surface = reinterpret_cast<float4*>(surface);
-    p.prev = prev ? prev : reinterpret_cast<const float*>(g.d_center_radius.data());
-    p.prev_stride = prev ? stride : 4u;
-    p.same_camera =
-        !prev_camera || std::memcmp(prev_camera, &g.desc.camera, sizeof(vcrt_camera)) == 0;
-    // (a lens renderer has no lists: its rays do not share an origin)
-    p.use_lists = g.feature_lists && !lens_on() ? 1u : 0u;
-    const vcrt::MotionCamera mc = vcrt::motion_camera(
-        p.same_camera ? g.cam : camera_of(g.desc.width, g.desc.height, *prev_camera));
-    const vcrt::f3 v[5] = {mc.center, mc.e, mc.nw, mc.nu, mc.nv};
-    for (int i = 0; i < 5; i++) {
-        p.prev_cam[3 * i + 0] = v[i].x;
-        p.prev_cam[3 * i + 1] = v[i].y;
-        p.prev_cam[3 * i + 2] = v[i].z;
-    }
-    p.prev_cam[15] = mc.num;
-    unsigned long long slots[kFeatureCounterWords] = {};
-    float ms = 0.f;
-    const VkResult r = frame_ray_launch(g.k_frame_motion, p, stats ? slots : nullptr, &ms);
-    if (r != VK_SUCCESS) return r;
-    if (stats) {
-        unsigned long long counters[6] = {0, 0, 0, 0, 0, 0};
-        for (size_t s = 0; s < kFeatureCounterWords; s += 8)
-            for (int c = 0; c < 6; c++) counters[c] += slots[s + c];
-        stats->kernel_ms = ms;
-        stats->rays = g.local_pixels;
-        stats->hit_rays = counters[3];
-        stats->projected = counters[4];
-        stats->identity = counters[5];
-        stats->listed_rays = counters[0];
-        stats->group_tests = counters[1];
-        stats->bound_tests = counters[2];
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_draw_motion_device(const vcrt_camera* prev_camera,
-                                    const vcrt_sphere* prev_spheres, int32_t count, float* motion,
-                                    float* surface, vcrt_motion_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = motion_args(prev_spheres, count, motion, surface);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernel's 16-byte stores and its 4-byte loads of the records
-    if (misaligned({motion, surface}, 15u) || misaligned({prev_spheres}, 3u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_frame_motion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    static_assert(sizeof(vcrt_sphere) == 40 && offsetof(vcrt_sphere, radius) == 12,
-                  "the kernel reads centre and radius at the head of a 10-float record");
-    const VkResult r = draw_motion_device(prev_camera, reinterpret_cast<const float*>(prev_spheres),
-                                          10u, motion, surface, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_draw_motion(const vcrt_camera* prev_camera, const vcrt_sphere* prev_spheres,
-                             int32_t count, float* motion, float* surface,
-                             vcrt_motion_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = motion_args(prev_spheres, count, motion, surface);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.k_frame_motion) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t elems = g.local_elems;
-    if (motion) VCRT_TRY(g.d_mo_motion.reserve(elems));
-    if (surface) VCRT_TRY(g.d_mo_surface.reserve(elems));
-    // packed tiles: the slots outside the frame keep what the caller's planes hold
-    if (g.desc.world_size > 1 && elems) {
-        if (motion)
-            VCRT_TRY(hipMemcpyAsync(g.d_mo_motion.data(), motion, sizeof(float4) * elems,
-                                    hipMemcpyHostToDevice, g.stream));
-        if (surface)
-            VCRT_TRY(hipMemcpyAsync(g.d_mo_surface.data(), surface, sizeof(float4) * elems,
-                                    hipMemcpyHostToDevice, g.stream));
-    }
-    // the previous centres and radii, packed
-    const float* prev = nullptr;
-    if (prev_spheres && count > 0) {
-        VCRT_TRY(g.d_mo_prev.reserve(static_cast<size_t>(count)));
-        g.h_mo_prev.resize(static_cast<size_t>(count));
-        for (int32_t s = 0; s < count; s++)
-            g.h_mo_prev[s] = make_float4(prev_spheres[s].center[0], prev_spheres[s].center[1],
-                                         prev_spheres[s].center[2], prev_spheres[s].radius);
-        VCRT_TRY(hipMemcpyAsync(g.d_mo_prev.data(), g.h_mo_prev.data(), sizeof(float4) * count,
-                                hipMemcpyHostToDevice, g.stream));
-        prev = reinterpret_cast<const float*>(g.d_mo_prev.data());
-    }
-    const VkResult r = draw_motion_device(
-        prev_camera, prev, 4u, motion ? reinterpret_cast<float*>(g.d_mo_motion.data()) : nullptr,
-        surface ? reinterpret_cast<float*>(g.d_mo_surface.data()) : nullptr, stats);
-    if (r != VK_SUCCESS) return r;
-    if (elems) {
-        if (motion)
-            VCRT_TRY(hipMemcpyAsync(motion, g.d_mo_motion.data(), sizeof(float4) * elems,
-                                    hipMemcpyDeviceToHost, g.stream));
-        if (surface)
-            VCRT_TRY(hipMemcpyAsync(surface, g.d_mo_surface.data(), sizeof(float4) * elems,
-                                    hipMemcpyDeviceToHost, g.stream));
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-    }
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
-}
-
 vcrt_result vcrt_motion_project(const vcrt_render_desc* desc, const vcrt_camera* prev_camera,
                                 const float* points, int32_t count, float* out) {
     vcrt_render_desc dv;
@@ -2575,215 +1971,6 @@ vcrt_result vcrt_motion_project(const vcrt_render_desc* desc, const vcrt_camera*
         out[3 * i + 1] = r.y;
         out[3 * i + 2] = r.z;
     }
-    return VCRT_SUCCESS;
-}
-
-// ---- adaptive sampling -------------------------------------------------------------------------
-
-namespace {
-
-// d_sm_counters: the scan's totals (4 u64), the tracer's work index (u32, a slot of its own),
-// then the tally slots
-constexpr size_t kSampleTotalsWord = 0, kSampleWorkWord = 8, kSampleTallyWord = 16;
-constexpr size_t kSampleCounterWords = kSampleTallyWord + kFeatureCounterWords;
-
-// The arguments both forms of vcrt_draw_samples check, before anything touches the GPU. The
-// format errors come first, so that they read the same with and without a renderer.
-vcrt_result sample_args(uint32_t first, uint32_t max_count, const void* counts, const void* sums,
-                        const void* mean) {
-    if (max_count == 0 || max_count > vcrt::kSampleMaxCount ||
-        static_cast<uint64_t>(first) + max_count > kFeatureMaxIndex)
-        return VCRT_ERROR_FORMAT_NOT_SUPPORTED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!counts || !sums || mean == sums) return VCRT_ERROR_INITIALIZATION_FAILED;
-    return VCRT_SUCCESS;
-}
-
-// The three kernels on device planes (checked by the callers); returns when the resolve is done.
-VkResult draw_samples_device(uint32_t first, uint32_t max_count, const uint16_t* counts,
-                             int32_t accumulate, float* sums, float* mean,
-                             vcrt_sample_stats* stats) {
-    if (stats) {
-        *stats = vcrt_sample_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_trace_samples");
-    }
-    if (g.local_tiles == 0) {  // a rank without tiles has no slot to write
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-        return VK_SUCCESS;
-    }
-    for (Event& e : g.ev_sm) VCRT_TRY(e.create());
-    const uint32_t blocks =
-        (g.total_pixels + vcrt::kSampleScanSlots - 1u) / vcrt::kSampleScanSlots;
-    VCRT_TRY(g.d_sm_block_sums.reserve(blocks));
-    VCRT_TRY(g.d_sm_offsets.reserve(g.total_pixels));
-    VCRT_TRY(g.d_sm_counters.reserve(kSampleCounterWords));
-    unsigned long long* counters = g.d_sm_counters.data();
-    VCRT_TRY(hipMemsetAsync(counters, 0, kSampleCounterWords * sizeof(unsigned long long),
-                            g.stream));
-    // ---- the scan: block sums, their prefix and the totals; one read-back sizes the rest ----
-    vcrt::SampleScanParams sp{};
-    sp.counts = counts;
-    sp.block_sums = g.d_sm_block_sums.data();
-    sp.totals = counters + kSampleTotalsWord;
-    sp.offsets = g.d_sm_offsets.data();
-    sp.blocks = blocks;
-    sp.max_count = max_count;
-    sp.total_pixels = g.total_pixels;
-    sp.width = g.desc.width;
-    sp.height = g.desc.height;
-    sp.rank = g.desc.rank;
-    sp.world = g.desc.world_size;
-    sp.tiles_x = g.tiles_x;
-    VCRT_TRY(hipEventRecord(g.ev_sm[0].get(), g.stream));
-    sp.phase = 0;
-    VkResult r = launch(g.k_sample_scan, blocks, vcrt::kSampleScanBlock, 0, sp);
-    if (r != VK_SUCCESS) return r;
-    sp.phase = 1;
-    r = launch(g.k_sample_scan, 1, vcrt::kSampleScanBlock, 0, sp);
-    if (r != VK_SUCCESS) return r;
-    unsigned long long totals[4] = {};
-    VCRT_TRY(hipMemcpyAsync(totals, sp.totals, sizeof(totals), hipMemcpyDeviceToHost, g.stream));
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    const uint64_t items = totals[2];
-    if (items > vcrt::kSampleMaxItems) return VK_ERROR_FORMAT_NOT_SUPPORTED;
-    VCRT_TRY(g.d_sm_items.reserve(items));
-    VCRT_TRY(g.d_sm_scratch.reserve(items));
-    if (items) {
-        sp.items = g.d_sm_items.data();
-        sp.phase = 2;
-        r = launch(g.k_sample_scan, blocks, vcrt::kSampleScanBlock, 0, sp);
-        if (r != VK_SUCCESS) return r;
-    }
-    VCRT_TRY(hipEventRecord(g.ev_sm[1].get(), g.stream));
-    // ---- the tracer: the tables of [first, first + max_count), then the persistent grid ----
-    vcrt::SampleTraceParams tp{};
-    if (items) {
-        const VkResult t = feature_tables(first, max_count);
-        if (t != VK_SUCCESS) return t;
-        frame_ray_scene(tp.scene, max_count);
-        tp.scene.max_depth = g.desc.max_depth;
-        tp.items = g.d_sm_items.data();
-        tp.scratch = g.d_sm_scratch.data();
-        tp.count = static_cast<uint32_t>(items);
-        tp.use_lists = g.feature_lists ? 1u : 0u;
-        tp.work = reinterpret_cast<uint32_t*>(counters + kSampleWorkWord);
-        tp.tallies = counters + kSampleTallyWord;
-        int per_cu = 0;
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g.k_trace_samples,
-                                                               kQueryBlock, 0) != hipSuccess ||
-            per_cu <= 0)
-            per_cu = 1;
-        if (g.desc.blocks_per_cu > 0) per_cu = std::min(per_cu, g.desc.blocks_per_cu);
-        const uint32_t grid = std::min<uint32_t>(
-            static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(g.num_cus),
-            (tp.count + kQueryBlock - 1) / kQueryBlock);
-        VCRT_TRY(hipEventRecord(g.ev_sm[2].get(), g.stream));
-        r = launch(g.k_trace_samples, grid, kQueryBlock, 0, tp);
-        if (r != VK_SUCCESS) return r;
-    } else {
-        VCRT_TRY(hipEventRecord(g.ev_sm[2].get(), g.stream));
-    }
-    VCRT_TRY(hipEventRecord(g.ev_sm[3].get(), g.stream));
-    // ---- the resolve ----
-    vcrt::SampleResolveParams rp{};
-    rp.counts = counts;
-    rp.offsets = g.d_sm_offsets.data();
-    rp.scratch = g.d_sm_scratch.data();
-    rp.sums = reinterpret_cast<float4*>(sums);
-    rp.mean = reinterpret_cast<float4*>(mean);
-    rp.max_count = max_count;
-    rp.accumulate = accumulate != 0 ? 1u : 0u;
-    rp.total_pixels = g.total_pixels;
-    rp.width = g.desc.width;
-    rp.height = g.desc.height;
-    rp.rank = g.desc.rank;
-    rp.world = g.desc.world_size;
-    rp.tiles_x = g.tiles_x;
-    r = launch(g.k_sample_resolve, (g.total_pixels + 255u) / 256u, 256, 0, rp);
-    if (r != VK_SUCCESS) return r;
-    VCRT_TRY(hipEventRecord(g.ev_sm[4].get(), g.stream));
-    std::vector<unsigned long long> slots;
-    if (stats && items) {
-        slots.resize(kFeatureCounterWords);
-        VCRT_TRY(hipMemcpyAsync(slots.data(), counters + kSampleTallyWord,
-                                kFeatureCounterWords * sizeof(unsigned long long),
-                                hipMemcpyDeviceToHost, g.stream));
-    }
-    VCRT_TRY(hipStreamSynchronize(g.stream));
-    if (stats) {
-        stats->samples = totals[0];
-        stats->pixels = totals[1];
-        stats->items = items;
-        for (size_t s = 0; s < slots.size(); s += 8) {
-            stats->listed_rays += slots[s];
-            stats->group_tests += slots[s + 1];
-            stats->bound_tests += slots[s + 2];
-            stats->segments += slots[s + 3];
-        }
-        float ms = 0.f;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_sm[0].get(), g.ev_sm[1].get()));
-        stats->scan_ms = ms;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_sm[2].get(), g.ev_sm[3].get()));
-        stats->kernel_ms = ms;
-        VCRT_TRY(hipEventElapsedTime(&ms, g.ev_sm[3].get(), g.ev_sm[4].get()));
-        stats->resolve_ms = ms;
-    }
-    return VK_SUCCESS;
-}
-
-}  // namespace
-
-vcrt_result vcrt_draw_samples_device(uint32_t first, uint32_t max_count, const uint16_t* counts,
-                                     int32_t accumulate, float* sums, float* mean,
-                                     vcrt_sample_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = sample_args(first, max_count, counts, sums, mean);
-    if (a != VCRT_SUCCESS) return a;
-    // the kernels' 16-byte loads and stores, 2-byte loads of the counts
-    if (misaligned({sums, mean}, 15u) || misaligned({counts}, 1u))
-        return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.k_trace_samples) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const VkResult r = draw_samples_device(first, max_count, counts, accumulate, sums, mean, stats);
-    if (r == VK_SUCCESS && stats) stats->host_ms = ms_since(t0);
-    return r;
-}
-
-vcrt_result vcrt_draw_samples(uint32_t first, uint32_t max_count, const uint16_t* counts,
-                              int32_t accumulate, float* sums, float* mean,
-                              vcrt_sample_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const vcrt_result a = sample_args(first, max_count, counts, sums, mean);
-    if (a != VCRT_SUCCESS) return a;
-    if (!g.k_trace_samples) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    const size_t elems = g.local_elems;
-    VCRT_TRY(g.d_sm_counts.reserve(elems));
-    VCRT_TRY(g.d_sm_stage[0].reserve(elems));
-    if (mean) VCRT_TRY(g.d_sm_stage[1].reserve(elems));
-    if (elems) {
-        VCRT_TRY(hipMemcpyAsync(g.d_sm_counts.data(), counts, sizeof(uint16_t) * elems,
-                                hipMemcpyHostToDevice, g.stream));
-        // the slots the call leaves alone keep what the caller's planes hold: those outside the
-        // frame (packed tiles) and, accumulating, every pixel's old sums
-        if (accumulate != 0 || g.desc.world_size > 1)
-            VCRT_TRY(hipMemcpyAsync(g.d_sm_stage[0].data(), sums, sizeof(float4) * elems,
-                                    hipMemcpyHostToDevice, g.stream));
-        if (mean && g.desc.world_size > 1)
-            VCRT_TRY(hipMemcpyAsync(g.d_sm_stage[1].data(), mean, sizeof(float4) * elems,
-                                    hipMemcpyHostToDevice, g.stream));
-    }
-    const VkResult r = draw_samples_device(first, max_count, g.d_sm_counts.data(), accumulate,
-                                           plane_of(g.d_sm_stage[0]),
-                                           mean ? plane_of(g.d_sm_stage[1]) : nullptr, stats);
-    if (r != VK_SUCCESS) return r;
-    if (elems) {
-        VCRT_TRY(hipMemcpyAsync(sums, g.d_sm_stage[0].data(), sizeof(float4) * elems,
-                                hipMemcpyDeviceToHost, g.stream));
-        if (mean)
-            VCRT_TRY(hipMemcpyAsync(mean, g.d_sm_stage[1].data(), sizeof(float4) * elems,
-                                    hipMemcpyDeviceToHost, g.stream));
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-    }
-    if (stats) stats->host_ms = ms_since(t0);
     return VCRT_SUCCESS;
 }
 

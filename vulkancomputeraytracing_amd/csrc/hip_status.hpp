@@ -27,3 +27,9 @@ inline VkResult to_vk(hipError_t e) {
 }
 
 }  // namespace vcrt
+
+#define VCRT_TRY(expr)                                  \
+    do {                                                \
+        hipError_t e_ = (expr);                         \
+        if (e_ != hipSuccess) return ::vcrt::to_vk(e_); \
+    } while (0)

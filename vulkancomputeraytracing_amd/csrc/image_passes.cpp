@@ -2,10 +2,10 @@
 // vcrt_denoise, vcrt_reproject, vcrt_reproject_moments, vcrt_variance, vcrt_denoise_variance, and
 // the element-wise vcrt_sample_counts. They touch neither the scene nor the frame. What a pass
 // launches is image_pass_plan.hpp's; here are the executor that makes a plan's launches on the
-// renderer's stream, the staging of the host forms, and one body per pass behind both exported
-// forms. Every form checks in the same order, which the refused-call tests pin: the pass's own
-// argument check (denoise.cpp, reproject.cpp, variance.cpp), for the device form the alignment,
-// then the renderer and its module, then the kernel.
+// renderer's stream and one body per pass behind both exported forms (their staging:
+// pass_staging.hpp). Every form checks in the same order, which the refused-call tests pin: the
+// pass's own argument check (denoise.cpp, reproject.cpp, variance.cpp), for the device form the
+// alignment, then the renderer and its module, then the kernel.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -21,9 +21,16 @@ namespace {
 
 using vcrt::DeviceBuffer;
 using vcrt::g;
+using vcrt::in1;
+using vcrt::in4;
 using vcrt::misaligned;
-using vcrt::ms_since;
+using vcrt::name_stats;
+using vcrt::out1;
+using vcrt::out4;
+using vcrt::pass_ready;
+using vcrt::Plane;
 using vcrt::plane_of;
+using vcrt::Staging;
 using Clock = std::chrono::steady_clock;
 
 // ---- the executor ------------------------------------------------------------------------------
@@ -85,8 +92,7 @@ VkResult run(hipFunction_t direct, hipFunction_t lds, vcrt::AtrousPlan<Params>& 
     }
     VCRT_TRY(hipStreamSynchronize(g.stream));
     if (stats) {
-        *stats = vcrt_denoise_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "%s", name);
+        name_stats(stats, name);
         stats->passes = plan.passes;
         stats->lds_passes = plan.lds_passes;
         float ms = 0.f;
@@ -98,92 +104,6 @@ VkResult run(hipFunction_t direct, hipFunction_t lds, vcrt::AtrousPlan<Params>& 
         }
     }
     return VK_SUCCESS;
-}
-
-// ---- the two forms of a call -------------------------------------------------------------------
-
-// One plane of a call as the caller passed it: null when the plane is optional and left out.
-struct Plane {
-    const void* host;
-    size_t elem;  // bytes per element: 16 (a float4 plane), 4 or 2
-    bool out;
-};
-Plane in4(const float* p) { return {p, 16, false}; }
-Plane out4(float* p) { return {p, 16, true}; }
-Plane in1(const float* p) { return {p, 4, false}; }
-Plane out1(float* p) { return {p, 4, true}; }
-
-// The planes a pass runs on. The device form runs on the caller's. The host form takes a device
-// plane from the state's pool for every plane that is there (d_stage4 for float4 planes, d_stage1
-// for narrower ones, in the order listed: no two planes of a call share a buffer), uploads the
-// inputs, and after the run downloads the outputs and synchronises once.
-class Staging {
-public:
-    VkResult begin(bool host_form, size_t count, std::initializer_list<Plane> planes) {
-        host_form_ = host_form;
-        count_ = count;
-        size_t n4 = 0, n1 = 0;
-        for (const Plane& p : planes) {
-            void* d = const_cast<void*>(p.host);
-            if (n_ == kMaxPlanes) return VK_ERROR_UNKNOWN;  // a call wider than the pool: a bug
-            if (host_form && p.host) {
-                if (p.elem == sizeof(float4)) {
-                    if (n4 == std::size(g.d_stage4)) return VK_ERROR_UNKNOWN;
-                    VCRT_TRY(g.d_stage4[n4].reserve(count));
-                    d = g.d_stage4[n4++].data();
-                } else {
-                    if (n1 == std::size(g.d_stage1)) return VK_ERROR_UNKNOWN;
-                    VCRT_TRY(g.d_stage1[n1].reserve((count * p.elem + 3) / 4));
-                    d = g.d_stage1[n1++].data();
-                }
-                if (!p.out)
-                    VCRT_TRY(hipMemcpyAsync(d, p.host, count * p.elem, hipMemcpyHostToDevice,
-                                            g.stream));
-            }
-            plane_[n_] = p;
-            dev_[n_++] = d;
-        }
-        return VK_SUCCESS;
-    }
-    // plane i of the list, on the device
-    template <typename T = float>
-    T* at(size_t i) const {
-        return static_cast<T*>(dev_[i]);
-    }
-    VkResult end() {
-        if (!host_form_) return VK_SUCCESS;
-        for (size_t i = 0; i < n_; i++)
-            if (plane_[i].out && plane_[i].host)
-                VCRT_TRY(hipMemcpyAsync(const_cast<void*>(plane_[i].host), dev_[i],
-                                        count_ * plane_[i].elem, hipMemcpyDeviceToHost, g.stream));
-        VCRT_TRY(hipStreamSynchronize(g.stream));
-        return VK_SUCCESS;
-    }
-
-private:
-    static constexpr size_t kMaxPlanes = 10;  // d_stage4's and d_stage1's
-    bool host_form_ = false;
-    size_t count_ = 0, n_ = 0;
-    Plane plane_[kMaxPlanes];
-    void* dev_[kMaxPlanes];
-};
-
-// What every form checks after the pass's own argument check, in this order.
-vcrt_result pass_ready(bool device_planes_misaligned, hipFunction_t kernel) {
-    if (device_planes_misaligned) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!g.begun || !g.stage.module) return VCRT_ERROR_INITIALIZATION_FAILED;
-    if (!kernel) return VCRT_ERROR_FEATURE_NOT_PRESENT;
-    return VCRT_SUCCESS;
-}
-
-// The end of every form: after a good run the outputs come back and the call's time is taken.
-template <typename Stats>
-vcrt_result finish(VkResult ran, Staging& s, Stats* stats, Clock::time_point t0) {
-    if (ran != VK_SUCCESS) return ran;
-    const VkResult r = s.end();
-    if (r != VK_SUCCESS) return r;
-    if (stats) stats->host_ms = ms_since(t0);
-    return VCRT_SUCCESS;
 }
 
 // ---- the passes: host = the form that takes host planes ----------------------------------------
@@ -198,11 +118,11 @@ vcrt_result denoise(bool host, const float* colour, const float* albedo, const f
                                              out, &pr, k4);
     if (a != VCRT_SUCCESS) return a;
     // the kernels' 16-byte loads and stores
-    const vcrt_result c = pass_ready(
-        !host && misaligned({colour, albedo, normal_depth, out}, 15u), g.k_denoise_pass);
+    const vcrt_result c = pass_ready(!host && misaligned({colour, albedo, normal_depth, out}, 15u),
+                                     g.begun && g.stage.module, g.k_denoise_pass);
     if (c != VCRT_SUCCESS) return c;
     const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    Staging s;
+    Staging s(g.staging, g.stream);
     float* scratch[2];
     VkResult r = s.begin(host, pixels, {in4(colour), in4(albedo), in4(normal_depth), out4(out)});
     if (r == VK_SUCCESS) r = atrous_scratch(pr.levels, pixels, scratch);
@@ -228,9 +148,9 @@ vcrt_result reproject(bool host, const float* colour, const float* motion,
     const vcrt_result c = pass_ready(
         !host && (misaligned({colour, motion, history_colour, history_surface, out}, 15u) ||
                   misaligned({history_length, out_length}, 3u)),
-        g.k_reproject_pass);
+        g.begun && g.stage.module, g.k_reproject_pass);
     if (c != VCRT_SUCCESS) return c;
-    Staging s;
+    Staging s(g.staging, g.stream);
     VkResult r = s.begin(host, static_cast<size_t>(width) * static_cast<size_t>(height),
                          {in4(colour), in4(motion), in4(history_colour), in4(history_surface),
                           in1(history_length), out4(out), out1(out_length)});
@@ -242,8 +162,7 @@ vcrt_result reproject(bool host, const float* colour, const float* motion,
     r = run(g.k_reproject_pass, l, g.d_rp_counters, vcrt::kReprojectTallySlots, stats != nullptr,
             false, &accepted, &ms);
     if (r == VK_SUCCESS && stats) {
-        *stats = vcrt_reproject_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_reproject_pass");
+        name_stats(stats, "vcrt_reproject_pass");
         stats->kernel_ms = ms;
         stats->accepted_pixels = accepted;
     }
@@ -268,9 +187,9 @@ vcrt_result reproject_moments(bool host, const float* colour, const float* motio
         !host && (misaligned({colour, motion, history_colour, history_surface, albedo,
                               history_moments, out, out_moments}, 15u) ||
                   misaligned({history_length, out_length}, 3u)),
-        g.k_reproject_moments_pass);
+        g.begun && g.stage.module, g.k_reproject_moments_pass);
     if (c != VCRT_SUCCESS) return c;
-    Staging s;
+    Staging s(g.staging, g.stream);
     VkResult r = s.begin(host, static_cast<size_t>(width) * static_cast<size_t>(height),
                          {in4(colour), in4(motion), in4(history_colour), in4(history_surface),
                           in1(history_length), in4(albedo), in4(history_moments), out4(out),
@@ -283,8 +202,7 @@ vcrt_result reproject_moments(bool host, const float* colour, const float* motio
     r = run(g.k_reproject_moments_pass, l, g.d_rp_counters, vcrt::kMomentsTallySlots,
             stats != nullptr, false, &accepted, &ms);
     if (r == VK_SUCCESS && stats) {
-        *stats = vcrt_reproject_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_reproject_moments_pass");
+        name_stats(stats, "vcrt_reproject_moments_pass");
         stats->kernel_ms = ms;
         stats->accepted_pixels = accepted;
     }
@@ -301,9 +219,9 @@ vcrt_result variance(bool host, const float* moments, const float* surface, int3
     if (a != VCRT_SUCCESS) return a;
     const vcrt_result c = pass_ready(
         !host && (misaligned({moments, surface}, 15u) || misaligned({variance_out}, 3u)),
-        g.k_variance_pass);
+        g.begun && g.stage.module, g.k_variance_pass);
     if (c != VCRT_SUCCESS) return c;
-    Staging s;
+    Staging s(g.staging, g.stream);
     VkResult r = s.begin(host, static_cast<size_t>(width) * static_cast<size_t>(height),
                          {in4(moments), in4(surface), out1(variance_out)});
     if (r != VK_SUCCESS) return r;
@@ -317,9 +235,7 @@ vcrt_result variance(bool host, const float* moments, const float* surface, int3
     r = run(lds ? g.k_variance_pass_lds : g.k_variance_pass, l, g.d_vr_counters,
             vcrt::kVarianceTallySlots, stats != nullptr, false, &spatial, &ms);
     if (r == VK_SUCCESS && stats) {
-        *stats = vcrt_variance_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel),
-                      lds ? "vcrt_variance_pass_lds" : "vcrt_variance_pass");
+        name_stats(stats, lds ? "vcrt_variance_pass_lds" : "vcrt_variance_pass");
         stats->kernel_ms = ms;
         stats->spatial_pixels = spatial;
     }
@@ -340,10 +256,10 @@ vcrt_result denoise_variance(bool host, const float* colour, const float* albedo
     const vcrt_result c = pass_ready(
         !host && (misaligned({colour, albedo, normal_depth, out}, 15u) ||
                   misaligned({variance_in, out_variance}, 3u)),
-        g.k_denoise_var_pass);
+        g.begun && g.stage.module, g.k_denoise_var_pass);
     if (c != VCRT_SUCCESS) return c;
     const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
-    Staging s;
+    Staging s(g.staging, g.stream);
     float* scratch[2];
     VkResult r = s.begin(host, pixels, {in4(colour), in4(albedo), in4(normal_depth),
                                         in1(variance_in), out4(out), out1(out_variance)});
@@ -366,9 +282,9 @@ vcrt_result sample_counts(bool host, const float* variance_in, uint32_t elements
     // the kernel's 4-byte loads of the variance, 2-byte stores of the counts
     const vcrt_result c = pass_ready(
         !host && (misaligned({variance_in}, 3u) || misaligned({counts}, 1u)),
-        g.k_sample_counts_pass);
+        g.begun && g.stage.module, g.k_sample_counts_pass);
     if (c != VCRT_SUCCESS) return c;
-    Staging s;
+    Staging s(g.staging, g.stream);
     VkResult r = s.begin(host, elements, {in1(variance_in), Plane{counts, 2, true}});
     if (r != VK_SUCCESS) return r;
     vcrt::PassLaunch<vcrt::SampleCountParams> l{};
@@ -387,8 +303,7 @@ vcrt_result sample_counts(bool host, const float* variance_in, uint32_t elements
     r = run(g.k_sample_counts_pass, l, g.d_vr_counters, vcrt::kSampleCountTallySlots,
             stats != nullptr, true, &total, &ms);
     if (r == VK_SUCCESS && stats) {
-        *stats = vcrt_sample_count_stats{};
-        std::snprintf(stats->kernel, sizeof(stats->kernel), "vcrt_sample_counts_pass");
+        name_stats(stats, "vcrt_sample_counts_pass");
         stats->kernel_ms = ms;
         stats->total = total;
     }

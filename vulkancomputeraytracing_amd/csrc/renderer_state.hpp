@@ -1,12 +1,15 @@
 // renderer_state.hpp -- the host library's one RendererState and the launch helpers on its
 // stream, shared by the translation units behind the C ABI: capi.cpp (the renderer, the scene and
-// the frame) and image_passes.cpp (the passes over caller-supplied planes). The state's device
-// buffers, pinned buffers and events are owners (device_resources.hpp) that free themselves, so
-// teardown is an assignment of a fresh state (vcrt_end) and there is no list of frees to maintain.
+// the frame), ray_passes.cpp (the queries and the passes that trace the frame's own rays) and
+// image_passes.cpp (the passes over caller-supplied planes). The state's device buffers, pinned
+// buffers and events are owners (device_resources.hpp) that free themselves, so teardown is an
+// assignment of a fresh state (vcrt_end) and there is no list of frees to maintain.
 #pragma once
 
+#include <array>
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <initializer_list>
 #include <vector>
 
@@ -17,6 +20,7 @@
 #include "cluster.hpp"
 #include "device_resources.hpp"
 #include "hip_status.hpp"
+#include "pass_staging.hpp"
 #include "scene_update_abi.h"
 #include "vcrt.h"
 #include "vcrt_kernel_abi.h"
@@ -46,55 +50,48 @@ struct RendererState {
     // the flat scans' cost-order builds (null: the code object predates them; no cost order)
     hipFunction_t k_trace_cull_flat_cost = nullptr, k_trace_cull_flat_global_cost = nullptr,
                   k_trace_cull_flat_boxes_cost = nullptr;
-    // ray queries (vcrt_trace_rays; null: the code object predates them). The host call stages
-    // through device buffers kept and grown between calls; the counters (the work index at 0,
-    // three u64 tallies from 8) are the query's own, so a frame's are left alone.
+    // ray queries (vcrt_trace_rays; null: the code object predates them). The counters (the work
+    // index at 0, three u64 tallies from 8) are the query's own, so a frame's are left alone.
     hipFunction_t k_trace_rays = nullptr;
     // the thin-lens frame kernels (desc.lens_radius > 0; null: the code object predates them):
     // the SMEM scan, then the three flat scans and their cost-order builds
     hipFunction_t k_smem_lens = nullptr, k_flat_lens = nullptr, k_flat_lens_cost = nullptr,
                   k_flat_global_lens = nullptr, k_flat_global_lens_cost = nullptr,
                   k_flat_boxes_lens = nullptr, k_flat_boxes_lens_cost = nullptr;
-    DeviceBuffer<float> d_rq_rays;  // [n][3] the origins, then [n][3] the directions
-    DeviceBuffer<float4> d_rq_radiance;
-    DeviceBuffer<vcrt_ray_hit> d_rq_hits;
     DeviceBuffer<unsigned long long> d_rq_counters;
-    // occlusion queries (vcrt_occlude_rays; null: the code object predates them): the host call
-    // stages its rays in d_rq_rays and the reaches and answers here; tallies in d_rq_counters
+    // occlusion queries (vcrt_occlude_rays; null: the code object predates them): tallies in
+    // d_rq_counters
     hipFunction_t k_occlude_rays = nullptr;
-    DeviceBuffer<float> d_oq_tmax;
-    DeviceBuffer<uint8_t> d_oq_occluded;
     // feature buffers (vcrt_draw_features; null: the code object predates them): the jitter
     // terms and lens origins of the call's own sample indices (the frame's tables are left
-    // alone), the host call's staging planes and the tallies' slots; kept and grown only
+    // alone) and the tallies' slots; kept and grown only
     hipFunction_t k_frame_features = nullptr;
     bool feature_lists = true;  // VCRT_FEATURE_LISTS=0: no ray takes the camera-ray lists
     DeviceBuffer<float2> d_ft_jitter_in;
     DeviceBuffer<float4> d_ft_jitter, d_ft_lens;
     std::vector<float2> h_ft_jitter;
     std::vector<float4> h_ft_lens;
-    DeviceBuffer<float4> d_ft_albedo, d_ft_normal_depth;
-    DeviceBuffer<int32_t> d_ft_sphere;
     DeviceBuffer<unsigned long long> d_ft_counters;
     // the ambient visibility buffer (vcrt_draw_occlusion; null: the code object predates it): the
-    // u_j table of the call and the host call's staging plane, kept and grown only; the jitter and
-    // lens tables and the tallies' slots are the feature buffers'
+    // u_j table of the call, kept and grown only; the jitter and lens tables and the tallies'
+    // slots are the feature buffers'
     hipFunction_t k_frame_occlusion = nullptr;
-    DeviceBuffer<float4> d_ao_dirs, d_ao_plane;
+    DeviceBuffer<float4> d_ao_dirs;
     std::vector<float4> h_ao_dirs;
     // the reprojection map (vcrt_draw_motion; null: the code object predates it): the host call's
-    // staging planes and its packed table of the previous centres and radii, kept and grown only;
-    // the tallies' slots are the feature buffers'
+    // packed table of the previous centres and radii, kept and grown only; the tallies' slots are
+    // the feature buffers'
     hipFunction_t k_frame_motion = nullptr;
-    DeviceBuffer<float4> d_mo_motion, d_mo_surface, d_mo_prev;
+    DeviceBuffer<float4> d_mo_prev;
     std::vector<float4> h_mo_prev;
-    // the image passes (image_passes.cpp; a null kernel: the code object predates the pass).
-    // The host forms stage the caller's planes through one pool, kept and grown only: a call
-    // takes its float4 planes from d_stage4 and its narrower ones from d_stage1 in the order it
-    // lists them, so within a call no two planes share a buffer and nothing outlives the call.
-    // The widest call is vcrt_reproject_moments: six float4 planes in, two out, and two lengths.
-    DeviceBuffer<float4> d_stage4[8];
-    DeviceBuffer<float> d_stage1[2];
+    // The one staging storage of the host forms (pass_staging.hpp; ray_passes.cpp and
+    // image_passes.cpp), kept and grown only: a call takes its planes of 16-byte multiples from
+    // staging.wide and its narrower ones from staging.narrow in the order it lists them, so
+    // within a call no two planes share a buffer and nothing outlives the call. The widest calls:
+    // vcrt_reproject_moments takes eight wide planes (six float4 planes in, two out) and two
+    // lengths; vcrt_occlude_rays takes four narrow ones (origins, directions, reaches, answers).
+    StagingPool staging;
+    // the image passes (image_passes.cpp; a null kernel: the code object predates the pass)
     // the denoiser (vcrt_denoise): the two scratch planes the passes between the first and the
     // last go through and the events around the passes
     hipFunction_t k_denoise_pass = nullptr, k_denoise_pass_lds = nullptr;
@@ -112,9 +109,8 @@ struct RendererState {
     DeviceBuffer<unsigned long long> d_vr_counters;
     // adaptive sampling (vcrt_draw_samples, vcrt_sample_counts; null: the code object predates
     // them): the scan's block sums, offsets and item table, the tracer's scratch (16 B per
-    // item), the counters (totals, work index, tally slots), vcrt_draw_samples' staging planes
-    // and the events around the three kernels; kept and grown only. The jitter and lens tables
-    // are the feature buffers'.
+    // item), the counters (totals, work index, tally slots) and the events around the three
+    // kernels; kept and grown only. The jitter and lens tables are the feature buffers'.
     hipFunction_t k_sample_scan = nullptr, k_trace_samples = nullptr, k_sample_resolve = nullptr,
                   k_sample_counts_pass = nullptr;
     DeviceBuffer<uint4> d_sm_block_sums;
@@ -122,8 +118,6 @@ struct RendererState {
     DeviceBuffer<uint2> d_sm_items;
     DeviceBuffer<float4> d_sm_scratch;
     DeviceBuffer<unsigned long long> d_sm_counters;
-    DeviceBuffer<uint16_t> d_sm_counts;
-    DeviceBuffer<float4> d_sm_stage[2];  // sums, mean
     Event ev_sm[5];
     // VCRT_CULL_LANE_TABLES: 0 = auto, 1 = LDS, 2 = global, 3 = boxes in LDS (flat scan)
     int cull_lane_tables = 0;
@@ -273,12 +267,6 @@ struct RendererState {
 // vcrt_end alone, by move-assigning a fresh state. Defined once, in capi.cpp.
 extern RendererState& g;
 
-#define VCRT_TRY(expr)                                  \
-    do {                                                \
-        hipError_t e_ = (expr);                         \
-        if (e_ != hipSuccess) return ::vcrt::to_vk(e_); \
-    } while (0)
-
 template <typename Params>
 VkResult launch(hipFunction_t f, uint32_t grid, uint32_t block, uint32_t lds, Params& params) {
     void* args[] = {&params};
@@ -322,5 +310,62 @@ inline bool misaligned(std::initializer_list<const void*> planes, uintptr_t mask
 }
 
 inline float* plane_of(const DeviceBuffer<float4>& b) { return reinterpret_cast<float*>(b.data()); }
+
+// The stats preamble of a pass: the struct zeroed, the kernel named.
+template <typename Stats>
+void name_stats(Stats* stats, const char* kernel) {
+    if (!stats) return;
+    *stats = Stats{};
+    std::snprintf(stats->kernel, sizeof(stats->kernel), "%s", kernel);
+}
+
+// ---- what capi.cpp defines for the frame and ray_passes.cpp uses too ---------------------------
+
+bool lens_on();  // desc.lens_radius > 0
+// Jitter of sample indices base .. base+n-1 (shader.comp:48 depends only on the index).
+void make_jitter(uint64_t base, int n, float2* out);
+// pixel00, delta_u, delta_v, centre: TraceParams.cam
+std::array<float, 12> camera_array();
+// Whether a frame of camera `cam` (camera_array) gets the camera-ray lists (the range guard).
+bool lists_allowed(const std::array<float, 12>& cam);
+// The camera of a width x height frame as vcrt_begin builds it.
+Camera camera_of(int32_t width, int32_t height, const vcrt_camera& c);
+// The scene's part of a kernel's argument block: the scan tables, the shading rows, the margins
+// and the flags' scene bits (frames and ray queries).
+void scene_params(TraceParams& p);
+// The scene's and the frame's part of the argument block of a kernel that traces the frame's own
+// camera rays: scene_params, the jitter and lens tables given (of `spp` samples), the corners,
+// the camera-ray lists (null when the camera fails lists_allowed), size, rank, tiles and camera.
+void frame_params(TraceParams& p, const float4* jitter, const float4* lens, int32_t spp,
+                  int32_t max_depth);
+// The jitter terms (and, with d_lens, the lens origins: centre + lens_offset) of sample indices
+// base .. base + n - 1 into tables the caller owns: built on the host in h_jitter (and h_lens),
+// copied to d_jitter_in (and d_lens), `copied` (may be null) recorded behind the copies, then
+// vcrt_setup_jitter's launch into d_jitter (and, when d_corner is given, the pixels' corners).
+struct JitterTables {
+    float2* h_jitter;
+    float4* h_lens;
+    float2* d_jitter_in;
+    float4 *d_jitter, *d_lens, *d_corner;
+    hipEvent_t copied;
+};
+VkResult jitter_tables(uint64_t base, uint32_t n, const JitterTables& t);
+
+// FeatureParams.tallies and its like: slots of 64 B, summed by the callers (sum_tallies)
+constexpr size_t kFeatureCounterWords = 8 * kFeatureTallySlots;  // u64
+
+// The timed launch of a kernel that traces the frame's own camera rays (vcrt_draw_features,
+// vcrt_draw_occlusion, vcrt_draw_motion): one wave per local tile, its tallies' slots in
+// d_ft_counters. A rank without tiles launches nothing, and *ms stays 0.
+template <typename Params>
+VkResult frame_ray_launch(hipFunction_t f, Params& p, unsigned long long* slots, float* ms) {
+    if (g.local_tiles == 0) {
+        VCRT_TRY(hipStreamSynchronize(g.stream));
+        return VK_SUCCESS;
+    }
+    return timed_launch(f, (g.local_tiles + 3u) / 4u, 256, 0, p, g.d_ft_counters,
+                        kFeatureCounterWords, [&p](unsigned long long* c) { p.tallies = c; },
+                        slots, ms);
+}
 
 }  // namespace vcrt

@@ -372,6 +372,14 @@ def _ptr(a):
     return a.data_ptr() if _is_torch(a) else a.ctypes.data
 
 
+def _stats_dict(st, keys=None, unnamed: str = "") -> dict:
+    """A stats struct as a dict: `keys` in their order (None: the struct's fields in theirs), then
+    "kernel" (`unnamed` when the call launched nothing and left the name empty)."""
+    if keys is None:
+        keys = [f for f, _ in st._fields_ if f != "kernel"]
+    return {**{k: getattr(st, k) for k in keys}, "kernel": st.kernel.decode() or unnamed}
+
+
 def reproject_moments_host(colour, motion, history_colour, history_surface, history_length,
                            history_moments, albedo=None, **params):
     """Temporal accumulation with luminance moments, the definition on the host
@@ -888,6 +896,36 @@ class Renderer:
             ctypes.c_void_p(gathered_ptr), ctypes.c_void_p(frame_ptr), d.width, d.height,
             d.world_size, tiles_per_rank))
 
+    def _local_lead(self) -> tuple[int, ...]:
+        """The leading shape of the rank-local framebuffer's planes: [height, width] at world 1,
+        else the packed tiles [tiles, 64]."""
+        elems, tiles = self.local_layout()
+        return ((self.desc.height, self.desc.width) if self.desc.world_size == 1
+                else (tiles, 64))
+
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self.desc.device if self.desc.device >= 0
+                            else torch.cuda.current_device())
+
+    def _frame_planes(self, device: bool, channels) -> list:
+        """Zero-filled output planes of a frame pass in the rank-local leading shape, one per
+        entry of `channels`: c > 0 a float32 [..., c] plane, 0 an int32 [...] one, None none.
+        numpy, or with device=True torch tensors on the renderer's device, the caller's current
+        stream synchronised behind them: the device call may follow."""
+        lead = self._local_lead()
+        if not device:
+            return [None if c is None else
+                    np.zeros(lead + ((c,) if c else ()), np.float32 if c else np.int32)
+                    for c in channels]
+        import torch
+        dev = self._torch_device()
+        planes = [None if c is None else
+                  torch.zeros(lead + ((c,) if c else ()), device=dev,
+                              dtype=torch.float32 if c else torch.int32) for c in channels]
+        torch.cuda.current_stream(dev).synchronize()
+        return planes
+
     def trace_rays(self, origins, dirs, max_depth: int | None = None, hits: bool = False,
                    stats: bool = False):
         """Radiance and first hit of caller-supplied rays against the current scene
@@ -937,9 +975,8 @@ class Renderer:
         if hits:
             out.append(rec)
         if stats:
-            out.append({"segments": st.segments, "group_tests": st.group_tests,
-                        "bound_tests": st.bound_tests, "kernel_ms": st.kernel_ms,
-                        "kernel": st.kernel.decode() or "vcrt_trace_rays"})
+            out.append(_stats_dict(st, ("segments", "group_tests", "bound_tests", "kernel_ms"),
+                                   "vcrt_trace_rays"))
         return out[0] if len(out) == 1 else tuple(out)
 
     def draw_features(self, samples: int | None = None, first: int = 0, albedo: bool = True,
@@ -965,37 +1002,16 @@ class Renderer:
         if not (albedo or normal or sphere):
             raise ValueError("at least one of albedo, normal, sphere")
         lib = self._L()
-        elems, tiles = self.local_layout()
-        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
-                else (tiles, 64))
-        want = (("albedo", albedo, 4), ("normal_depth", normal, 4), ("sphere", sphere, 0))
         st = N.vcrt_feature_stats()
-        out, ptrs = {}, []
-        if device:
-            import torch
-            dev = torch.device("cuda", self.desc.device if self.desc.device >= 0
-                               else torch.cuda.current_device())
-            for name, on, c in want:
-                if on:
-                    out[name] = torch.zeros(lead + ((c,) if c else ()), device=dev,
-                                            dtype=torch.float32 if c else torch.int32)
-                ptrs.append(out[name].data_ptr() if on else None)
-            torch.cuda.current_stream(dev).synchronize()
-            N.check("vcrt_draw_features_device", lib.vcrt_draw_features_device(
-                first, n, *ptrs, ctypes.byref(st)))
-        else:
-            for name, on, c in want:
-                if on:
-                    out[name] = np.zeros(lead + ((c,) if c else ()),
-                                         dtype=np.float32 if c else np.int32)
-                ptrs.append(out[name].ctypes.data if on else None)
-            N.check("vcrt_draw_features", lib.vcrt_draw_features(
-                first, n, *ptrs, ctypes.byref(st)))
+        planes = self._frame_planes(device, (4 if albedo else None, 4 if normal else None,
+                                             0 if sphere else None))
+        name = "vcrt_draw_features_device" if device else "vcrt_draw_features"
+        N.check(name, getattr(lib, name)(first, n, *map(_ptr, planes), ctypes.byref(st)))
+        out = {k: p for k, p in zip(("albedo", "normal_depth", "sphere"), planes)
+               if p is not None}
         if stats:
-            out["stats"] = {"rays": st.rays, "listed_rays": st.listed_rays,
-                            "group_tests": st.group_tests, "bound_tests": st.bound_tests,
-                            "kernel_ms": st.kernel_ms, "host_ms": st.host_ms,
-                            "kernel": st.kernel.decode()}
+            out["stats"] = _stats_dict(st, ("rays", "listed_rays", "group_tests", "bound_tests",
+                                            "kernel_ms", "host_ms"))
         return out
 
     def draw_occlusion(self, samples: int | None = None, first: int = 0, rays: int = 8,
@@ -1032,26 +1048,11 @@ class Renderer:
         if reach != reach:
             raise ValueError("reach must not be NaN")
         lib = self._L()
-        elems, tiles = self.local_layout()
-        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
-                else (tiles, 64))
         st = N.vcrt_occlusion_buffer_stats()
-        if device:
-            import torch
-            dev = torch.device("cuda", self.desc.device if self.desc.device >= 0
-                               else torch.cuda.current_device())
-            out = torch.zeros(lead + (4,), device=dev, dtype=torch.float32)
-            torch.cuda.current_stream(dev).synchronize()
-            N.check("vcrt_draw_occlusion_device", lib.vcrt_draw_occlusion_device(
-                first, n, m, reach, out.data_ptr(), ctypes.byref(st)))
-        else:
-            out = np.zeros(lead + (4,), dtype=np.float32)
-            N.check("vcrt_draw_occlusion", lib.vcrt_draw_occlusion(
-                first, n, m, reach, out.ctypes.data, ctypes.byref(st)))
-        if stats:
-            names = [f for f, _ in N.vcrt_occlusion_buffer_stats._fields_ if f != "kernel"]
-            return out, {**{f: getattr(st, f) for f in names}, "kernel": st.kernel.decode()}
-        return out
+        out, = self._frame_planes(device, (4,))
+        name = "vcrt_draw_occlusion_device" if device else "vcrt_draw_occlusion"
+        N.check(name, getattr(lib, name)(first, n, m, reach, _ptr(out), ctypes.byref(st)))
+        return (out, _stats_dict(st)) if stats else out
 
     def denoise(self, frame=None, guides=None, *, levels=None, sigma_normal=None,
                 sigma_depth=None, sigma_albedo=None, sigma_colour=None, demodulate=None,
@@ -1147,9 +1148,6 @@ class Renderer:
         statistics are left alone."""
         lib = self._L()
         cam = None if prev_camera is None else ctypes.byref(_camera_c(self.desc, prev_camera))
-        elems, tiles = self.local_layout()
-        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
-                else (tiles, 64))
         st = N.vcrt_motion_stats()
         prev_ptr, count = None, 0
         if prev_spheres is not None and _is_torch(prev_spheres):
@@ -1176,29 +1174,19 @@ class Renderer:
                 arr = arr.view(SPHERE_DTYPE).reshape(-1)
             arr = np.ascontiguousarray(arr)
             count = len(arr)
-        out = {}
-        if device:
-            import torch
-            dev = torch.device("cuda", self.desc.device if self.desc.device >= 0
-                               else torch.cuda.current_device())
-            for name in ("motion", "surface"):
-                out[name] = torch.zeros(lead + (4,), device=dev, dtype=torch.float32)
-            if prev_spheres is not None and prev_ptr is None:  # host values: to the device
-                staged = torch.from_numpy(arr.view(np.float32).reshape(-1, 10).copy()).to(dev)
+            prev_ptr = arr.ctypes.data
+            if device:  # host values: to the device
+                import torch
+                staged = torch.from_numpy(arr.view(np.float32).reshape(-1, 10).copy()).to(
+                    self._torch_device())
                 prev_ptr = staged.data_ptr()
-            torch.cuda.current_stream(dev).synchronize()
-            N.check("vcrt_draw_motion_device", lib.vcrt_draw_motion_device(
-                cam, prev_ptr, count, out["motion"].data_ptr(), out["surface"].data_ptr(),
-                ctypes.byref(st)))
-        else:
-            for name in ("motion", "surface"):
-                out[name] = np.zeros(lead + (4,), dtype=np.float32)
-            N.check("vcrt_draw_motion", lib.vcrt_draw_motion(
-                cam, None if prev_spheres is None else arr.ctypes.data, count,
-                out["motion"].ctypes.data, out["surface"].ctypes.data, ctypes.byref(st)))
+        motion, surface = self._frame_planes(device, (4, 4))
+        name = "vcrt_draw_motion_device" if device else "vcrt_draw_motion"
+        N.check(name, getattr(lib, name)(cam, prev_ptr, count, _ptr(motion), _ptr(surface),
+                                         ctypes.byref(st)))
+        out = {"motion": motion, "surface": surface}
         if stats:
-            names = [f for f, _ in N.vcrt_motion_stats._fields_ if f != "kernel"]
-            out["stats"] = {**{f: getattr(st, f) for f in names}, "kernel": st.kernel.decode()}
+            out["stats"] = _stats_dict(st)
         return out
 
     def reproject(self, frame, motion, history=None, *, surface=None, alpha=None,
@@ -1301,9 +1289,7 @@ class Renderer:
         if max_count > SAMPLE_MAX_COUNT:
             raise ValueError(f"max_count must not exceed {SAMPLE_MAX_COUNT}")
         lib = self._L()
-        elems, tiles = self.local_layout()
-        lead = ((self.desc.height, self.desc.width) if self.desc.world_size == 1
-                else (tiles, 64))
+        lead = self._local_lead()
         on_device = _is_torch(counts)
         if sums is not None and _is_torch(sums) != on_device:
             raise ValueError("counts and sums must both be numpy arrays or both torch tensors")
@@ -1357,11 +1343,9 @@ class Renderer:
         if mean:
             out["mean"] = mean_plane
         if stats:
-            out["stats"] = {k: getattr(st, k) for k in
-                            ("pixels", "samples", "items", "segments", "listed_rays",
-                             "group_tests", "bound_tests", "scan_ms", "kernel_ms", "resolve_ms",
-                             "host_ms")}
-            out["stats"]["kernel"] = st.kernel.decode()
+            out["stats"] = _stats_dict(st, ("pixels", "samples", "items", "segments",
+                                            "listed_rays", "group_tests", "bound_tests",
+                                            "scan_ms", "kernel_ms", "resolve_ms", "host_ms"))
         return out
 
     def sample_counts(self, variance, target: float, min_count: int = 0, max_count: int = 64,
@@ -1582,9 +1566,8 @@ class Renderer:
                     ctypes.byref(st)))
             occ = occ.view(np.bool_)
         if stats:
-            return occ, {"segments": st.segments, "group_tests": st.group_tests,
-                         "bound_tests": st.bound_tests, "kernel_ms": st.kernel_ms,
-                         "kernel": st.kernel.decode() or "vcrt_occlude_rays"}
+            return occ, _stats_dict(st, ("segments", "group_tests", "bound_tests", "kernel_ms"),
+                                    "vcrt_occlude_rays")
         return occ
 
     def visible(self, a, b):
